@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- CG iterations/sec + SpMV GB/s against the HBM roofline on synthetic 3-D 7-point Poisson CSR.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
         N > 1 started PLAINLY (no WORLD_SIZE in the environment): this process launches N rank processes of itself, one per GPU (self_launch below);
         under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_* set) it is one rank.
 
@@ -9,6 +9,11 @@ A "step" is ONE iteration of the reference's unpreconditioned CG (src/solver/cg.
 right-hand side and iterate that are already resident in HBM.  W warm-up iterations and three batches of exactly K timed iterations run inside one
 stepping session (tol = 0, so the device never stops early); every batch is bracketed by device synchronize + barrier on both sides, the maximum over
 ranks is taken per batch and the MEAN of the batches is the headline (their median when one batch is disturbed: slowest > 1.1 x fastest).  One JSON line on rank 0.  (--solver pcg / gmres: Jacobi-PCG / GMRES(30) + Jacobi.)
+`ms_per_step` in the line is the headline's milliseconds per iteration.  --dump-outputs DIR writes what those timed iterations handed back after their
+last step -- x (whole, or a fixed seeded sample beside its row numbers x_index) and the residual history -- as float64 DIR/<name>.npy: the inputs
+(b = A*1, x0 = 0) are the same on every run with the same arguments, so two builds can be compared output for output.  N > 1: the dump comes from
+the first timed run, RCCL all-gather + RCCL halo; the headline may be a later form of the same iterations (mailboxes, another halo form) whose
+final residual is bit-identical to it.
 
 Workload: ONE fixed 512^3 system for every N (BASELINE.json's metric is quoted on 256^3 / 512^3; north_star asks for strong scaling of CG iterations/sec
 on 512^3, which fits a single 288 GB GPU).  N > 1: row-partitioned in k-slabs over the ranks, halo planes and inner products over xGMI (hipIpc peer
@@ -550,12 +555,13 @@ class env_override:
         self._sync()
 
 
-def stepped(K, ctx, group, method, a, pc, b, warmup, steps, batches=3):
+def stepped(K, ctx, group, method, a, pc, b, warmup, steps, batches=3, keep=None):
     """W warm-up iterations, then `batches` batches of exactly K iterations of one stepping session (tol = 0), each bracketed by device
     synchronize + barrier on both sides, the maximum over ranks per batch; -> (headline batch seconds, stats, all batch seconds).  The headline
     is the MEAN of the batches when they agree within 10 % -- the steady-state rate: with x updated in batches of 8 iterations a window of K = 20
     iterations holds two or three batch passes, and the median would always pick a window with three -- and the MEDIAN when they do not: one
-    disturbed batch must not become the headline."""
+    disturbed batch must not become the headline.  `keep` (a dict) receives what the session handed back after its
+    last step: x on the host and the residual history."""
     def barrier():
         ctx.synchronize()
         group.barrier()
@@ -570,6 +576,9 @@ def stepped(K, ctx, group, method, a, pc, b, warmup, steps, batches=3):
             barrier()
             dts.append(group.allreduce_max(time.perf_counter() - t0))
         stats = sess.end()
+        if keep is not None:
+            import numpy as np
+            keep.update(x=x.to_host(), residual_history=np.array(sess.residual_history, dtype=np.float64))
     assert stats.iterations == warmup + batches * steps, stats
     return batch_headline(dts), stats, dts
 
@@ -582,12 +591,13 @@ def batch_headline(dts):
 GMRES_RESTART = 30
 
 
-def timed_gmres(K, ctx, group, a, pc, b, warmup, steps, batches=3):
+def timed_gmres(K, ctx, group, a, pc, b, warmup, steps, batches=3, keep=None):
     """GmresSolver (gmres.rs:216-402; restart 30, the reference's default Left form with `pc`) has no stepping session -- its unit of
     work is the restart cycle -- so a batch is one device-resident SOLVE of exactly K iterations from x0 = 0 with tol = 0 (the iteration cap
     ends it: convergence.rs:25), after one warm-up solve of W iterations; every batch is bracketed by device synchronize + barrier on
     both sides, the maximum over ranks per batch; -> (median batch seconds, stats, all batch seconds).  The solve's own set-up (the
-    initial residual, one small allocation) is inside the timed region, as SURVEY 8(d) words it: iterations / wall time of `solve`."""
+    initial residual, one small allocation) is inside the timed region, as SURVEY 8(d) words it: iterations / wall time of `solve`.
+    `keep` (a dict) receives what the last solve handed back: x on the host and its residual history."""
     def barrier():
         ctx.synchronize()
         group.barrier()
@@ -603,13 +613,17 @@ def timed_gmres(K, ctx, group, a, pc, b, warmup, steps, batches=3):
         st = s.solve(a, pc, b, x)
         barrier()
         dts.append(group.allreduce_max(time.perf_counter() - t0))
+    if keep is not None:
+        import numpy as np
+        keep.update(x=x.to_host(), residual_history=np.array(s.residual_history, dtype=np.float64))
     assert st.iterations == steps, st
     return sorted(dts)[len(dts) // 2], st, dts
 
 
-def measure(K, ctx, group, grid, solver, warmup, steps, phase_iters, batches=3, gmres_steps=0, provisional=None):
+def measure(K, ctx, group, grid, solver, warmup, steps, phase_iters, batches=3, gmres_steps=0, provisional=None, keep=None):
     """Everything measured on one grid size -> dict (the operator is built once; the plain-CSR figures re-run the same
-    iterations with KRYST_SPMV_COMPRESS=0, which the library reads per session step)."""
+    iterations with KRYST_SPMV_COMPRESS=0, which the library reads per session step).  `keep` (a dict) receives the outputs of the
+    headline's timed iterations (stepped / timed_gmres)."""
     def barrier():
         ctx.synchronize()
         group.barrier()
@@ -623,10 +637,10 @@ def measure(K, ctx, group, grid, solver, warmup, steps, phase_iters, batches=3, 
     b = a.spmv(ctx.vec(nloc).fill(1.0))                      # b = A*1 (tests/preconditioner_integration.rs:25-31 convention)
     pc = K.Jacobi().setup(a) if solver in ("pcg", "gmres") else None
 
-    def timed_iterations():
+    def timed_iterations(keep=None):
         if solver == "gmres":
-            return timed_gmres(K, ctx, group, a, pc, b, warmup, steps, batches)
-        return stepped(K, ctx, group, solver, a, pc, b, warmup, steps, batches)
+            return timed_gmres(K, ctx, group, a, pc, b, warmup, steps, batches, keep)
+        return stepped(K, ctx, group, solver, a, pc, b, warmup, steps, batches, keep)
 
     # N > 1: what the library chose by itself for this context and this operator (mailboxes / peer stores when their set-up and their checked
     # test reduction / test exchange succeed on every rank), then the conservative pair FIRST -- RCCL all-gather + grouped ncclSend / ncclRecv --
@@ -637,18 +651,25 @@ def measure(K, ctx, group, grid, solver, warmup, steps, phase_iters, batches=3, 
         ctx.scalar_reduce("rccl")
         a.halo_mode("rccl")
     stage(rank, "warm-up + timed iterations" + (" (RCCL all-gather + RCCL halo)" if world > 1 else ""))
-    dt, stats, dts = timed_iterations()
+    dt, stats, dts = timed_iterations(keep)
     if provisional is not None:
         provisional(dt, stats, a.encoding(), "RCCL all-gather + RCCL halo exchange only" if world > 1 else "headline iterations only")
     # N > 1: the same K iterations with the inner products crossing the ranks through the hipIpc mailboxes instead of two RCCL
     # all-gathers per iteration (kryst_ctx_scalar_reduce).  The faster path that reproduces the other's residual BIT FOR BIT is the
     # headline; both figures are reported.  (Every rank takes the same decision: times are max-reduced, scalars are identical.)
+    # Not between rank threads that share one device (--ranks-per-process > 1, a rehearsal): one rank's mailbox kernel polls for its
+    # sibling's, which can sit behind it in the same hardware queue when the process has fewer hardware queues than streams, and it then
+    # spins until the poll budget runs out (tests/multirank_worker.py skips the path there too).
     reduce_info = None
     if world > 1:
-        stage(rank, "mailbox setup + timed iterations (scalar all-reduce through hipIpc mailboxes)")
+        threads = isinstance(group, ThreadedGroup)
+        stage(rank, "timed iterations: mailboxes not tried between rank threads" if threads else
+              "mailbox setup + timed iterations (scalar all-reduce through hipIpc mailboxes)")
         reduce_info = {"path": "rccl", "value_rccl": steps / dt, "value_ipc": None, "ipc": "unavailable on this node (hipIpc export / mapping / test reduction failed)",
                        "library_defaults": defaults}
-        if ctx.scalar_reduce("ipc") == "ipc":
+        if threads:
+            reduce_info["ipc"] = "not tried: rank threads that share one device"
+        elif ctx.scalar_reduce("ipc") == "ipc":
             try:
                 dt_ipc, stats_ipc, dts_ipc = timed_iterations()
                 failed = 0.0
@@ -1155,6 +1176,29 @@ def self_launch(argv, procs, limit_s):
     return rc
 
 
+DUMP_X_FULL = 1 << 22            # x is dumped whole up to this many rows (32 MiB of float64) ...
+DUMP_X_SAMPLE = 1 << 21          # ... else at this many rows, one at a seeded offset in each of as many equal strides (16 + 16 MiB with the index);
+                                 # N > 1: both divided among the ranks
+
+
+def dump_outputs(d, keep, rank, world):
+    """--dump-outputs DIR: what the headline's timed iterations handed back after their last step, as float64 .npy files -- x (whole, or a
+    fixed seeded sample with x_index, the sampled row numbers) and the residual history.  N > 1: every rank writes its own slice (_rank<r>)
+    of the first timed run, the one over RCCL all-gather + RCCL halo."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    x = keep["x"]
+    if len(x) > DUMP_X_FULL // world:
+        k = DUMP_X_SAMPLE // world
+        stride = len(x) // k
+        idx = np.arange(k, dtype=np.int64) * stride + np.random.default_rng(1234 + rank).integers(0, stride, k)
+        np.save(os.path.join(d, f"x_index{sfx}.npy"), idx.astype(np.float64))
+        x = x[idx]
+    np.save(os.path.join(d, f"x{sfx}.npy"), np.ascontiguousarray(x, dtype=np.float64))
+    np.save(os.path.join(d, f"residual_history{sfx}.npy"), keep["residual_history"].astype(np.float64))
+
+
 def rank_main(args, group, rank, world, dev, grid):
     """One rank's whole run (the process's only one, or one of its rank threads)."""
     import kryst_amd as K
@@ -1184,7 +1228,11 @@ def rank_main(args, group, rank, world, dev, grid):
         line.update(roofline=None, provisional=what)
         _PROVISIONAL["line"] = line
 
-    m = measure(K, ctx, group, grid, args.solver, args.warmup, args.steps, args.phase_iters, args.batches, args.gmres_steps, provisional)
+    keep = {} if args.dump_outputs else None
+    m = measure(K, ctx, group, grid, args.solver, args.warmup, args.steps, args.phase_iters, args.batches, args.gmres_steps, provisional, keep)
+    if keep is not None:
+        dump_outputs(args.dump_outputs, keep, rank, world)
+        del keep
     out = headline(m["dt"], m["stats"], m["enc"])
     roof = m["roofline"]
     rc = m["roofline_csr"]
@@ -1285,6 +1333,10 @@ def main():
     ap.add_argument("--ranks-per-process", type=int, default=1,
                     help="REHEARSAL ONLY (one-GPU box, KRYST_BENCH_DEVICE): this many ranks per launched process, a host thread each -- 8 ranks as "
                          "4 processes x 2, because a GPU box admits at most 6 processes on its card; --gpus then counts ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed iterations, write what their last step handed back (x, whole or a fixed seeded sample, and the residual "
+                         "history) to DIR/<name>.npy as float64, at most 64 MiB in all: the inputs are the same on every run with the same arguments "
+                         "(N > 1: from the first timed run, over RCCL)")
     args = ap.parse_args()
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # dmabuf IPC: what RCCL needs between processes on this driver

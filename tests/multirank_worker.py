@@ -176,10 +176,13 @@ def run_rank(rank, P, outdir, N, kind):
     out["sess_x"] = x.to_host()
     # the mailbox path of the scalar all-reduce (kryst_ctx_scalar_reduce: hipIpc-mapped cells written and polled by the kernel that
     # finishes the local fold): every solver again, bit for bit the results of the RCCL all-gather path above
+    # (not between rank THREADS that share the device: one rank's mailbox kernel polls for its sibling's, which can sit behind it in the
+    # same hardware queue when the process has fewer hardware queues than streams -- two per process where GPUs are shared -- and the poll
+    # budget then ends the solve with KRYST_ERR_RCCL; the 2- to 5-process cases carry the mailbox path)
     stage(rank, "scalar_reduce ipc")
-    mode = ctx.scalar_reduce("ipc")
+    mode = "not attempted (rank threads)" if THREADED else ctx.scalar_reduce("ipc")
     out["ipc_active"] = np.array([1 if mode == "ipc" else 0])
-    if mode != "ipc":
+    if mode != "ipc" and not THREADED:
         from kryst_amd._ffi import lib as _lib
         print(f"[rank {rank}] scalar_reduce('ipc') fell back to {mode}: {_lib().kryst_hip_last_error().decode()}", flush=True)
     if mode == "ipc":
