@@ -9,7 +9,7 @@
 //! | reference | here |
 //! |---|---|
 //! | `CsrMatrix::from_csr` src/matrix/sparse.rs:28-46, `SparseMatrix::spmv` :56-67 | [`HipCsrMatrix::from_csr`], `impl MatVec<Vec<f64>>` (operator-level: PCIe both ways) |
-//! | `Preconditioner::{setup,apply}` src/preconditioner/mod.rs:8-13 | [`HipJacobi`], [`HipIlu0`], [`HipChebyshev`] (`impl Preconditioner<HipCsrMatrix, Vec<f64>>`) |
+//! | `Preconditioner::{setup,apply}` src/preconditioner/mod.rs:8-13 | [`HipJacobi`], [`HipIlu0`], [`HipChebyshev`], [`HipBlockJacobi`] (`impl Preconditioner<HipCsrMatrix, Vec<f64>>`) |
 //! | `LinearSolver::solve` src/solver/mod.rs:30-52 | [`HipCgSolver`], [`HipPcgSolver`], [`HipGmresSolver`], [`HipBiCgStabSolver`]: the reference structs' public fields and builders, device-resident iteration |
 //! | `KspContext::solve_context` src/context/ksp_context.rs:88-148 | [`HipKspContext`] |
 //! | `KError` src/error.rs:6-19 | mapped by [`kerr`], `ZeroPivot(row)` from `kryst_hip_last_error_row()` |
@@ -289,6 +289,32 @@ impl HipChebyshev {
     pub fn new(degree: usize, lambda_min: Option<f64>, lambda_max: Option<f64>) -> Self { Self::empty(degree, lambda_min, lambda_max) }
 }
 
+device_pc! {
+    /// `BlockJacobi::setup` + `apply` (src/preconditioner/block_jacobi.rs:39-106) as a device `Preconditioner` on the CSR operator
+    /// (the reference's `apply` is an inherent method no solver can take).  `blocks`: index sets in the given order, the last block
+    /// that contains a row decides it, rows in no block give 0; `bsize > 0`: contiguous blocks of `bsize` rows instead (an extension).
+    /// Labelled deviations (include/kryst_hip.h, kryst_pc_block_jacobi): explicit Gauss-Jordan inverses, sorted index sets, errors
+    /// (`ZeroPivot(row)`, `FactorError`, `Unsupported` for blocks of more than 64 rows) where the reference gives non-finite z or panics.
+    /// Unverified source like the rest of this crate (never compiled).
+    HipBlockJacobi { blocks: Vec<Vec<usize>> = Vec::new(), bsize: usize = 0 } setup(s, a, out) {
+        if s.bsize > 0 {
+            ffi::kryst_pc_block_jacobi_uniform(a.h, s.bsize.min(i32::MAX as usize) as i32, &mut out)
+        } else {
+            let mut ptr: Vec<i64> = vec![0];
+            let mut idx: Vec<i64> = Vec::new();
+            for g in &s.blocks {
+                idx.extend(g.iter().map(|&i| i as i64));
+                ptr.push(idx.len() as i64);
+            }
+            ffi::kryst_pc_block_jacobi(a.h, ptr.as_ptr(), idx.as_ptr(), s.blocks.len() as i64, &mut out)
+        }
+    }
+}
+impl HipBlockJacobi {
+    pub fn new(blocks: Vec<Vec<usize>>) -> Self { Self::empty(blocks, 0) }
+    pub fn uniform(bsize: usize) -> Self { Self::empty(Vec::new(), bsize) }
+}
+
 // ------------------------------------------------------------------------------------------------------------------ solvers
 /// `CgNormType` (src/solver/cg.rs:35, the same enum again in pcg.rs:25).
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
@@ -316,7 +342,7 @@ fn device_solve(f: HostSolveFn, a: &HipCsrMatrix, pc: Option<&dyn Preconditioner
     assert_eq!(b.len(), x.len());
     let pch = match pc {
         Some(p) if uses_pc => probe_device_pc(p).ok_or(KError::Unsupported(
-            "kryst-hip: the preconditioner is not a device preconditioner of this crate (HipJacobi / HipIlu0 / HipChebyshev)"))?,
+            "kryst-hip: the preconditioner is not a device preconditioner of this crate (HipJacobi / HipIlu0 / HipChebyshev / HipBlockJacobi)"))?,
         _ => std::ptr::null_mut(),                                        // CgSolver / BiCgStabSolver ignore pc (cg.rs:115, bicgstab.rs:70)
     };
     let cap = (c.params.max_iters.max(0) as usize).saturating_add(c.params.restart.max(1) as usize + 8).min((1usize << 22) + 8);

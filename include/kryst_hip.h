@@ -215,6 +215,19 @@ int32_t kryst_pc_chebyshev(kryst_csr_t a, double alpha, double beta, int32_t deg
  * product z = M r, i.e. kryst_spmv with M.  m is borrowed (must outlive the preconditioner).  ApproxInv::setup -- a
  * least-squares fit per column through faer's QR (approxinv.rs:129-264) -- stays on the host with the reference. */
 int32_t kryst_pc_approx_inverse(kryst_csr_t m, kryst_pc_t* out);
+/* BlockJacobi::setup (src/preconditioner/block_jacobi.rs:39-62) + apply (:69-106) as a device Preconditioner on the CSR operator.
+ * blk_ptr / blk_idx: the index sets packed like CSR rows (blk_ptr[0] = 0, nblocks + 1 entries), in the given order, each unsorted.
+ * z = 0, then every block in order writes z[g[i]] = (B^-1 r|_g)[i]: the last block that contains a row decides it, a row in no block
+ * stays +0.0; empty blocks do nothing.  Labelled deviations: each block is inverted explicitly by Gauss-Jordan with full pivoting
+ * (the reference keeps faer's FullPivLu); each index set is sorted ascending first; KRYST_ZERO_PIVOT (kryst_hip_last_error_row() =
+ * the global row of the smallest block position not yet pivoted), KRYST_FACTOR_ERROR (NaN / Inf in a block), KRYST_ERR_ARG (index out
+ * of range or repeated in a block, non-square operator), KRYST_UNSUPPORTED (a block of more than 64 rows, a distributed operator) where
+ * the reference gives non-finite z or panics.  a is borrowed (must outlive the preconditioner). */
+int32_t kryst_pc_block_jacobi(kryst_csr_t a, const int64_t* blk_ptr, const int64_t* blk_idx, int64_t nblocks, kryst_pc_t* out); /* BlockJacobi::setup block_jacobi.rs:39-62 */
+int32_t kryst_pc_block_jacobi_uniform(kryst_csr_t a, int32_t bsize, kryst_pc_t* out);   /* extension: contiguous blocks of bsize rows, the last one shorter */
+/* the preconditioner as the CSR matrix M with z = M r: row g[i] of the block that owns it stores (g[j], Binv[i][j]) for every j of the
+ * block, ascending; other rows are empty.  row_ptr == NULL: *nnz only; else row_ptr (n + 1), col and val (*nnz each) are filled. */
+int32_t kryst_pc_block_jacobi_export(kryst_pc_t pc, int64_t* nnz, int64_t* row_ptr, int32_t* col, double* val);
 int32_t kryst_pc_apply(kryst_pc_t pc, kryst_vec_t r, kryst_vec_t z);                /* Preconditioner::apply */
 int32_t kryst_pc_destroy(kryst_pc_t pc);
 /* measurement hooks (bench.py): average ms of `reps` back-to-back applies between two HIP events on the compute stream; and what

@@ -14,6 +14,7 @@
 // V is std::vector<double> (the reference's Vec<f64>).  `Result<T, KError>` becomes "return T or throw KError";
 // Rust's assert_eq! panics on length mismatches become KError{ArgumentError}.
 #pragma once
+#include <algorithm>
 #include <functional>
 #include <memory>
 #include <optional>
@@ -179,6 +180,25 @@ private:
     }
     HipCsrMatrix m_;
 };
+// BlockJacobi (block_jacobi.rs:39-106) as a device preconditioner on the CSR operator: `blocks` are index sets in the given order (the last
+// block that contains a row decides it, rows in no block give 0), or contiguous blocks of `bsize` rows (uniform, an extension).  Labelled
+// deviations (kryst_hip.h, kryst_pc_block_jacobi): explicit Gauss-Jordan inverses, sorted index sets, errors instead of non-finite z.
+struct BlockJacobi : DevicePc {
+    explicit BlockJacobi(std::vector<std::vector<size_t>> blocks) : blocks(std::move(blocks)) {}
+    static BlockJacobi uniform(size_t bsize) { BlockJacobi b({}); b.bsize = bsize; return b; }
+    std::vector<std::vector<size_t>> blocks; size_t bsize = 0;
+    void setup(const HipCsrMatrix& a) override {
+        kryst_pc_t h = nullptr;
+        if (bsize > 0) {
+            check(kryst_pc_block_jacobi_uniform(a.handle(), (int32_t)std::min<size_t>(bsize, INT32_MAX), &h));
+        } else {
+            std::vector<int64_t> ptr(1, 0), idx;
+            for (auto& g : blocks) { for (size_t i : g) idx.push_back((int64_t)i); ptr.push_back((int64_t)idx.size()); }
+            check(kryst_pc_block_jacobi(a.handle(), ptr.data(), idx.data(), (int64_t)blocks.size(), &h));
+        }
+        reset(h, a.context()->handle());
+    }
+};
 struct Chebyshev : DevicePc {                                // chebyshev.rs:35-70: the trait apply is a stub returning Err
     size_t degree; std::optional<double> lambda_min, lambda_max;
     Chebyshev(size_t degree, std::optional<double> lmin, std::optional<double> lmax) : degree(degree), lambda_min(lmin), lambda_max(lmax) {}
@@ -299,11 +319,12 @@ protected:
 
 // ---- context/: PC<T> (src/context/pc_context.rs:36-76) and KspContext (src/context/ksp_context.rs:25-148) ---------------------
 // PC<T>: the reference's configuration enum for preconditioners, plus the constructor it lacks -- build(a) returns the set-up
-// device preconditioner.  Kinds outside the hot path (Ssor, ApproxInv setup, BlockJacobi, Multicolor, AMG, AdditiveSchwarz)
-// throw KError{Unsupported}.
+// device preconditioner.  Kinds outside the hot path (Ssor, ApproxInv setup, Multicolor, AMG, AdditiveSchwarz) throw
+// KError{Unsupported}.
 struct PC {
     enum Kind { JacobiKind, SsorKind, Ilu0Kind, IlupKind, IlutKind, ChebyshevKind, ApproxInvKind, BlockJacobiKind, MulticolorKind, AMGKind, AdditiveSchwarzKind };
     Kind kind; size_t fill = 0; double droptol = 0.0; size_t degree = 0; std::optional<double> emin, emax;
+    std::vector<std::vector<size_t>> blocks;
     static PC Jacobi() { return PC{JacobiKind}; }
     static PC Ilu0() { return PC{Ilu0Kind}; }
     static PC Ilup(size_t fill) { PC p{IlupKind}; p.fill = fill; return p; }
@@ -311,6 +332,7 @@ struct PC {
     static PC Chebyshev(size_t degree, std::optional<double> emin = std::nullopt, std::optional<double> emax = std::nullopt) {
         PC p{ChebyshevKind}; p.degree = degree; p.emin = emin; p.emax = emax; return p;
     }
+    static PC BlockJacobi(std::vector<std::vector<size_t>> blocks) { PC p{BlockJacobiKind}; p.blocks = std::move(blocks); return p; }   // pc_context.rs:67
     std::unique_ptr<Preconditioner<HipCsrMatrix, Vec>> build(const HipCsrMatrix& a) const {
         std::unique_ptr<Preconditioner<HipCsrMatrix, Vec>> pc;
         switch (kind) {
@@ -319,6 +341,7 @@ struct PC {
             case IlupKind: pc = std::make_unique<kryst::Ilup>(fill); break;
             case IlutKind: pc = std::make_unique<kryst::Ilut>(fill, droptol); break;
             case ChebyshevKind: pc = std::make_unique<kryst::Chebyshev>(degree, emin, emax); break;     // the trait object: apply is the stub
+            case BlockJacobiKind: pc = std::make_unique<kryst::BlockJacobi>(blocks); break;
             default: throw KError(KRYST_UNSUPPORTED);
         }
         pc->setup(a);
@@ -331,7 +354,7 @@ enum class SolverKind { Cg, Pcg, GmresLeft, GmresRight, Fgmres, Bicgstab, Cgs, Q
 // KspContext { kind, a, pc, flex_pc, tol, max_it, restart } + solve_context (ksp_context.rs:54-148): a fresh solver of `kind` per
 // call, forwarded (a, pc, b, x) exactly as the reference's match does -- FGMRES uses flex_pc, never pc (:101-107); the kinds that
 // need A^T or are outside the accelerated path (Qmr, Minres, Cgnr) throw KError{Unsupported}.  `a` is borrowed (the reference
-// owns an M by value; a device operator is not copyable).
+// owns an M by value; a device operator is not copyable).  `pc` is any device preconditioner, e.g. PC::BlockJacobi(blocks).build(a).
 struct KspContext {
     SolverKind kind;
     const HipCsrMatrix& a;

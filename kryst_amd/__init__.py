@@ -22,7 +22,7 @@ from . import _ffi
 from ._ffi import KError, lib, check
 
 __all__ = ["Context", "DeviceVec", "CsrMatrix", "dot", "norm", "Jacobi", "Ilu0", "Ilup", "Ilut", "TrueIlu0", "Chebyshev",
-           "ChebyshevPc", "IdentityPc", "ApproxInv", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
+           "ChebyshevPc", "IdentityPc", "ApproxInv", "BlockJacobi", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
            "Preconditioning", "CgSolver", "PcgSolver", "GmresSolver", "FgmresSolver", "Orthog", "CgsSolver", "TfqmrSolver", "BiCgStabSolver", "BiCgStabRightPcSolver", "Session", "KspContext", "SolverKind", "PC", "KError", "reduce_spec",
            "host_stencil7", "partition_rows", "halo_recv_plan", "read_matrix_market", "read_petsc_binary", "host_ilup", "host_ilut", "host_levels"]
 
@@ -565,6 +565,58 @@ class ApproxInv(_Pc):
         return self
 
 
+class BlockJacobi(_Pc):
+    """BlockJacobi (src/preconditioner/block_jacobi.rs:39-106) as a device preconditioner on the CSR operator.  `blocks`: a list of
+    index lists, or a (ptr, idx) tuple of numpy arrays packed like CSR rows; the last block that contains a row decides it, rows in no block
+    give z = +0.0.  `BlockJacobi.uniform(bsize)`: contiguous blocks of bsize rows, the last one shorter (an extension).  Labelled
+    deviations: explicit inverses by Gauss-Jordan with full pivoting, index sets sorted ascending, errors (ZeroPivot with `.row`,
+    FactorError, ArgumentError, Unsupported for blocks of more than 64 rows) where the reference gives non-finite z or panics."""
+
+    def __init__(self, blocks=None, bsize=None):
+        super().__init__()
+        self.bsize = bsize
+        if bsize is None:
+            if isinstance(blocks, tuple) and len(blocks) == 2 and all(isinstance(v, np.ndarray) for v in blocks):   # (ptr, idx)
+                self.ptr = np.ascontiguousarray(blocks[0], dtype=np.int64)
+                self.idx = np.ascontiguousarray(blocks[1], dtype=np.int64)
+            else:
+                blocks = [np.asarray(b, dtype=np.int64).ravel() for b in blocks]
+                self.ptr = np.zeros(len(blocks) + 1, dtype=np.int64)
+                np.cumsum([len(b) for b in blocks], out=self.ptr[1:])
+                self.idx = np.concatenate(blocks) if blocks else np.zeros(0, dtype=np.int64)
+            if len(self.ptr) < 1 or int(self.ptr[-1]) != len(self.idx):
+                raise KError(102, "BlockJacobi: inconsistent (ptr, idx)")
+
+    @staticmethod
+    def uniform(bsize):
+        return BlockJacobi(bsize=int(bsize))
+
+    def setup(self, a):
+        h = _ffi.Handle()
+        if self.bsize is not None:
+            check(lib().kryst_pc_block_jacobi_uniform(a.h, self.bsize, C.byref(h)))
+        else:
+            check(lib().kryst_pc_block_jacobi(a.h, self.ptr.ctypes.data_as(_ffi.c_i64p), self.idx.ctypes.data_as(_ffi.c_i64p),
+                                              len(self.ptr) - 1, C.byref(h)))
+        self._set(a.ctx, h)
+        self._a = a
+        return self
+
+    def inverse_csr(self):
+        """The preconditioner as the CSR matrix M with z = M r -> (row_ptr int64, col int32, val float64): row g[i] of the block that
+        owns it holds (g[j], Binv[i][j]) for every j of that block, ascending; other rows are empty."""
+        if self.h is None:
+            raise KError(2, "preconditioner used before setup")
+        nnz = C.c_int64()
+        check(lib().kryst_pc_block_jacobi_export(self.h, C.byref(nnz), None, None, None))
+        rp = np.zeros(self._a.nrows() + 1, dtype=np.int64)
+        ci = np.zeros(nnz.value, dtype=np.int32)
+        va = np.zeros(nnz.value, dtype=np.float64)
+        check(lib().kryst_pc_block_jacobi_export(self.h, C.byref(nnz), rp.ctypes.data_as(_ffi.c_i64p), ci.ctypes.data_as(_ffi.c_i32p),
+                                                 _dp(va)))
+        return rp, ci, va
+
+
 def apply_chebyshev(a, r, z, alpha, beta, m):
     """apply_chebyshev(a, r, z, alpha, beta, m)  src/preconditioner/chebyshev.rs:83-140."""
     if isinstance(r, DeviceVec):
@@ -784,7 +836,7 @@ class BiCgStabRightPcSolver(_Solver):
 class PC:
     """PC<T> (src/context/pc_context.rs:36-76): the reference's configuration enum for preconditioners, plus the constructor it
     lacks -- `PC.Ilut(fill=10, droptol=1e-3).build(a)` returns the set-up device preconditioner.  Kinds outside the hot path
-    (Ssor, ApproxInv setup, BlockJacobi, Multicolor, AMG, AdditiveSchwarz) raise KError(Unsupported)."""
+    (Ssor, ApproxInv setup, Multicolor, AMG, AdditiveSchwarz) raise KError(Unsupported)."""
 
     def __init__(self, kind, **params):
         self.kind, self.params = kind, params
@@ -812,6 +864,10 @@ class PC:
     def Chebyshev(degree, emin=None, emax=None):
         return PC("Chebyshev", degree=degree, emin=emin, emax=emax)
 
+    @staticmethod
+    def BlockJacobi(blocks):                      # pc_context.rs:67 BlockJacobi { blocks }
+        return PC("BlockJacobi", blocks=blocks)
+
     def build(self, a):
         k, q = self.kind, self.params
         if k == "Jacobi":
@@ -824,6 +880,8 @@ class PC:
             return Ilut(q["fill"], q["droptol"]).setup(a)
         if k == "Chebyshev":                         # the trait object of the reference (apply is the stub of chebyshev.rs:68-70)
             return Chebyshev(q["degree"], q["emin"], q["emax"]).setup(a)
+        if k == "BlockJacobi":
+            return BlockJacobi(q["blocks"]).setup(a)
         raise KError(6, f"preconditioner kind {k} is outside the accelerated path")
 
 

@@ -2,7 +2,7 @@
 #pragma once
 #include "csr.h"
 
-enum { KR_PC_IDENTITY = 1, KR_PC_JACOBI = 2, KR_PC_ILU = 3, KR_PC_CHEB_STUB = 6, KR_PC_CHEB = 7, KR_PC_SPAI = 9 };
+enum { KR_PC_IDENTITY = 1, KR_PC_JACOBI = 2, KR_PC_ILU = 3, KR_PC_CHEB_STUB = 6, KR_PC_CHEB = 7, KR_PC_SPAI = 9, KR_PC_BLOCK_JACOBI = 10 };
 
 struct kryst_pc_s {
     kryst_ctx_t ctx = nullptr;
@@ -22,6 +22,15 @@ struct kryst_pc_s {
     // Chebyshev
     double cheb_alpha = 0, cheb_beta = 0; int64_t cheb_degree = 0;
     double* d_v0 = nullptr; double* d_v1 = nullptr; double* d_v2 = nullptr;
+    // block Jacobi (block_jacobi.hip): the inverted tiles block after block, column-major inside a tile
+    int32_t bj_bsize = 0;             // contiguous form: blocks of bj_bsize consecutive rows, the last one shorter; 0: index-set form
+    int64_t bj_nblk = 0;
+    int64_t bj_uncovered = 0;         // rows in no block (index-set form): z = +0.0 there
+    double* d_bj_tile = nullptr;
+    int64_t* d_bj_ptr = nullptr; int64_t* d_bj_toff = nullptr;   // index-set form: block offsets into d_bj_idx, tile offsets
+    int32_t* d_bj_idx = nullptr;      // index-set form: each block's indices, sorted ascending
+    int32_t* d_bj_owner = nullptr;    // index-set form with overlapping blocks or uncovered rows: the last block containing a row, or -1
+    std::vector<int64_t> bj_ptr_h; std::vector<int32_t> bj_idx_h;
 };
 
 namespace kr {
@@ -32,6 +41,8 @@ int32_t pc_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done)
 // that cannot stall, pc_fell_back() reports that switch once, and the caller repeats the work.
 int32_t pc_health(kryst_pc_t pc);
 bool pc_fell_back(kryst_pc_t pc);
+int32_t bj_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done);   // block_jacobi.hip
+void bj_free(kryst_pc_t pc);
 int32_t chebyshev_dev(kryst_csr_t a, const double* r, double* z, double alpha, double beta, int64_t m,
                       double* v0, double* v1, double* v2, const int* done);
 }
