@@ -127,6 +127,8 @@ extern "C" {
     pub fn kryst_pc_block_jacobi(a: Csr, blk_ptr: *const i64, blk_idx: *const i64, nblocks: i64, out: *mut Pc) -> i32;
     pub fn kryst_pc_block_jacobi_uniform(a: Csr, bsize: i32, out: *mut Pc) -> i32;
     pub fn kryst_pc_block_jacobi_export(pc: Pc, nnz: *mut i64, row_ptr: *mut i64, col: *mut i32, val: *mut f64) -> i32;
+    pub fn kryst_pc_spai(a: Csr, pattern_kind: i32, pat_ptr: *const i64, pat_idx: *const i64, pat_n: i64, tol: f64, out: *mut Pc) -> i32;
+    pub fn kryst_pc_spai_export(pc: Pc, nnz: *mut i64, row_ptr: *mut i64, col: *mut i32, val: *mut f64) -> i32;
     pub fn kryst_pc_apply(pc: Pc, r: Vecd, z: Vecd) -> i32;
     pub fn kryst_pc_destroy(pc: Pc) -> i32;
     pub fn kryst_bench_pc_apply(pc: Pc, r: Vecd, z: Vecd, reps: i32, avg_ms: *mut f64) -> i32;

@@ -315,6 +315,37 @@ impl HipBlockJacobi {
     pub fn uniform(bsize: usize) -> Self { Self::empty(Vec::new(), bsize) }
 }
 
+/// `SparsityPattern` (src/preconditioner/mod.rs) for the SPAI set-up: `Manual(pat)` (pat[j] = the rows of column j of M), `Auto` (as
+/// written: `Err(Unsupported)`, approxinv.rs:127-133), `Operator` (extension: the stored columns of row j of A).
+#[derive(Clone, Debug, Default)]
+pub enum SparsityPattern { Manual(Vec<Vec<usize>>), #[default] Auto, Operator }
+
+device_pc! {
+    /// `ApproxInv::new(pattern, tol, max_iter, ..)` + `setup` (src/preconditioner/approxinv.rs:76-264) on the device; the apply is
+    /// `ApproxInv::apply` (z = M r).  Labelled deviations (include/kryst_hip.h, kryst_pc_spai): sorted patterns, the reduced least
+    /// squares by Householder QR, errors (`FactorError`, `Unsupported` over the caps) where the reference panics or gives non-finite
+    /// output.  Unverified source like the rest of this crate (never compiled).
+    HipSpai { pattern: SparsityPattern = SparsityPattern::Auto, tol: f64 = 0.0, max_iter: usize = 0 } setup(s, a, out) {
+        let mut ptr: Vec<i64> = vec![0];
+        let mut idx: Vec<i64> = Vec::new();
+        let (kind, n) = match &s.pattern {
+            SparsityPattern::Manual(pat) => {
+                for c in pat {
+                    idx.extend(c.iter().map(|&i| i as i64));
+                    ptr.push(idx.len() as i64);
+                }
+                (0, pat.len() as i64)
+            }
+            SparsityPattern::Auto => (1, 0),
+            SparsityPattern::Operator => (2, 0),
+        };
+        ffi::kryst_pc_spai(a.h, kind, ptr.as_ptr(), idx.as_ptr(), n, s.tol, &mut out)
+    }
+}
+impl HipSpai {
+    pub fn new(pattern: SparsityPattern, tol: f64, max_iter: usize) -> Self { Self::empty(pattern, tol, max_iter) }
+}
+
 // ------------------------------------------------------------------------------------------------------------------ solvers
 /// `CgNormType` (src/solver/cg.rs:35, the same enum again in pcg.rs:25).
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]

@@ -228,6 +228,24 @@ int32_t kryst_pc_block_jacobi_uniform(kryst_csr_t a, int32_t bsize, kryst_pc_t* 
 /* the preconditioner as the CSR matrix M with z = M r: row g[i] of the block that owns it stores (g[j], Binv[i][j]) for every j of the
  * block, ascending; other rows are empty.  row_ptr == NULL: *nnz only; else row_ptr (n + 1), col and val (*nnz each) are filled. */
 int32_t kryst_pc_block_jacobi_export(kryst_pc_t pc, int64_t* nnz, int64_t* row_ptr, int32_t* col, double* val);
+/* ApproxInv::setup (src/preconditioner/approxinv.rs:123-264) on the device: column j of M minimises || A m_j - e_j ||_2 over the
+ * vectors with support J_j; inv_rows[i] = the (j, M_ij) with |M_ij| > tol (strict: 0 and NaN are dropped), ascending j.  The apply is
+ * kryst_pc_approx_inverse's (approxinv.rs:268-298); M is owned by the preconditioner.  pattern_kind: KRYST_SPAI_MANUAL
+ * (SparsityPattern::Manual(pat), approxinv.rs:125, 146: n = pat.len() = pat_n, J_j = pat_idx[pat_ptr[j] .. pat_ptr[j+1])),
+ * KRYST_SPAI_AUTO (as written: KRYST_UNSUPPORTED, approxinv.rs:127-133 -- its downcasts at :301-323 never succeed), KRYST_SPAI_OPERATOR
+ * (extension: J_j = the stored columns of row j of A, what Auto's code was meant to do; pat_* are ignored).  max_iter, nbsteps and the
+ * other tuning fields of ApproxInv::new are unused, as in the reference.  Labelled deviations: each J_j is sorted ascending; the least
+ * squares is solved on the reduced problem A[I_j, J_j] (I_j = the stored rows of the columns J_j: the same minimiser) by Householder QR
+ * instead of faer's FullPivLu / Qr::solve_lstsq (values agree to rounding); KRYST_ERR_ARG (pattern of the wrong length, index out of
+ * range or repeated within a column, non-square operator), KRYST_FACTOR_ERROR (a zero Householder column, a non-finite A[I_j, J_j] or
+ * m_j; the message names the column), KRYST_UNSUPPORTED (a distributed operator; a column over the caps: |J_j| <= 64, at most 2048
+ * stored entries in A[:, J_j], |I_j| <= 128; or, inside the caps, tiles sized by the widest columns that exceed the device's LDS per
+ * workgroup -- DESIGN.md section 4.6) where the reference panics or gives non-finite output.  a is not kept. */
+enum { KRYST_SPAI_MANUAL = 0, KRYST_SPAI_AUTO = 1, KRYST_SPAI_OPERATOR = 2 };
+int32_t kryst_pc_spai(kryst_csr_t a, int32_t pattern_kind, const int64_t* pat_ptr, const int64_t* pat_idx, int64_t pat_n, double tol,
+                      kryst_pc_t* out);                                                 /* ApproxInv::setup approxinv.rs:123-264 */
+/* inv_rows (approxinv.rs:66) of a SPAI preconditioner as CSR: row_ptr == NULL: *nnz only; else row_ptr (n + 1), col and val (*nnz each) */
+int32_t kryst_pc_spai_export(kryst_pc_t pc, int64_t* nnz, int64_t* row_ptr, int32_t* col, double* val);
 int32_t kryst_pc_apply(kryst_pc_t pc, kryst_vec_t r, kryst_vec_t z);                /* Preconditioner::apply */
 int32_t kryst_pc_destroy(kryst_pc_t pc);
 /* measurement hooks (bench.py): average ms of `reps` back-to-back applies between two HIP events on the compute stream; and what

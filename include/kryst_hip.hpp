@@ -199,6 +199,41 @@ struct BlockJacobi : DevicePc {
         reset(h, a.context()->handle());
     }
 };
+// SparsityPattern (preconditioner/mod.rs) for the SPAI set-up: Manual(pat) (pat[j] = the rows of column j of M, n = pat.size()), Auto (as
+// written: the set-up throws KError{Unsupported}, approxinv.rs:127-133), Operator (extension: the stored columns of row j of A).
+struct SparsityPattern {
+    enum Kind { ManualKind = KRYST_SPAI_MANUAL, AutoKind = KRYST_SPAI_AUTO, OperatorKind = KRYST_SPAI_OPERATOR };
+    Kind kind = AutoKind; std::vector<std::vector<size_t>> pat;
+    static SparsityPattern Manual(std::vector<std::vector<size_t>> pat) { SparsityPattern p; p.kind = ManualKind; p.pat = std::move(pat); return p; }
+    static SparsityPattern Auto() { return SparsityPattern{}; }
+    static SparsityPattern Operator() { SparsityPattern p; p.kind = OperatorKind; return p; }
+};
+// ApproxInv::new(pattern, tol, max_iter, ...) + setup(a) (approxinv.rs:76-264) on the device: the SPAI set-up of kryst_pc_spai (labelled
+// deviations there: sorted patterns, reduced least squares by Householder QR, errors instead of panics); apply is ApproxInv's z = M r.
+// The tuning fields are kept and unused, as in the reference.  export(): M (inv_rows) as CSR.
+struct Spai : DevicePc {
+    Spai(SparsityPattern pattern, double tol, size_t max_iter = 0, size_t nbsteps = 0, size_t max_size = 0, size_t max_new = 0,
+         size_t block_size = 0, size_t cache_size = 0, bool verbose = false, bool sp = false)
+        : pattern(std::move(pattern)), tol(tol), max_iter(max_iter), nbsteps(nbsteps), max_size(max_size), max_new(max_new),
+          block_size(block_size), cache_size(cache_size), verbose(verbose), sp(sp) {}
+    SparsityPattern pattern; double tol; size_t max_iter, nbsteps, max_size, max_new, block_size, cache_size; bool verbose, sp;
+    void setup(const HipCsrMatrix& a) override {
+        kryst_pc_t h = nullptr;
+        std::vector<int64_t> ptr(1, 0), idx;
+        for (auto& c : pattern.pat) { for (size_t i : c) idx.push_back((int64_t)i); ptr.push_back((int64_t)idx.size()); }
+        check(kryst_pc_spai(a.handle(), (int32_t)pattern.kind, ptr.data(), idx.data(), (int64_t)pattern.pat.size(), tol, &h));
+        reset(h, a.context()->handle());
+        n_ = a.nrows();
+    }
+    void export_csr(std::vector<int64_t>& row_ptr, std::vector<int32_t>& col, Vec& val) const {
+        int64_t nnz = 0;
+        check(kryst_pc_spai_export(h_, &nnz, nullptr, nullptr, nullptr));
+        row_ptr.assign(n_ + 1, 0); col.assign((size_t)nnz, 0); val.assign((size_t)nnz, 0.0);
+        check(kryst_pc_spai_export(h_, &nnz, row_ptr.data(), col.data(), val.data()));
+    }
+private:
+    size_t n_ = 0;
+};
 struct Chebyshev : DevicePc {                                // chebyshev.rs:35-70: the trait apply is a stub returning Err
     size_t degree; std::optional<double> lambda_min, lambda_max;
     Chebyshev(size_t degree, std::optional<double> lmin, std::optional<double> lmax) : degree(degree), lambda_min(lmin), lambda_max(lmax) {}
@@ -319,12 +354,13 @@ protected:
 
 // ---- context/: PC<T> (src/context/pc_context.rs:36-76) and KspContext (src/context/ksp_context.rs:25-148) ---------------------
 // PC<T>: the reference's configuration enum for preconditioners, plus the constructor it lacks -- build(a) returns the set-up
-// device preconditioner.  Kinds outside the hot path (Ssor, ApproxInv setup, Multicolor, AMG, AdditiveSchwarz) throw
+// device preconditioner.  Kinds outside the hot path (Ssor, Multicolor, AMG, AdditiveSchwarz) throw
 // KError{Unsupported}.
 struct PC {
     enum Kind { JacobiKind, SsorKind, Ilu0Kind, IlupKind, IlutKind, ChebyshevKind, ApproxInvKind, BlockJacobiKind, MulticolorKind, AMGKind, AdditiveSchwarzKind };
     Kind kind; size_t fill = 0; double droptol = 0.0; size_t degree = 0; std::optional<double> emin, emax;
     std::vector<std::vector<size_t>> blocks;
+    SparsityPattern pattern; double tol = 0.0; size_t max_iter = 0;
     static PC Jacobi() { return PC{JacobiKind}; }
     static PC Ilu0() { return PC{Ilu0Kind}; }
     static PC Ilup(size_t fill) { PC p{IlupKind}; p.fill = fill; return p; }
@@ -333,6 +369,9 @@ struct PC {
         PC p{ChebyshevKind}; p.degree = degree; p.emin = emin; p.emax = emax; return p;
     }
     static PC BlockJacobi(std::vector<std::vector<size_t>> blocks) { PC p{BlockJacobiKind}; p.blocks = std::move(blocks); return p; }   // pc_context.rs:67
+    static PC ApproxInv(SparsityPattern pattern, double tol, size_t max_iter) {                                                          // pc_context.rs:63
+        PC p{ApproxInvKind}; p.pattern = std::move(pattern); p.tol = tol; p.max_iter = max_iter; return p;
+    }
     std::unique_ptr<Preconditioner<HipCsrMatrix, Vec>> build(const HipCsrMatrix& a) const {
         std::unique_ptr<Preconditioner<HipCsrMatrix, Vec>> pc;
         switch (kind) {
@@ -342,6 +381,7 @@ struct PC {
             case IlutKind: pc = std::make_unique<kryst::Ilut>(fill, droptol); break;
             case ChebyshevKind: pc = std::make_unique<kryst::Chebyshev>(degree, emin, emax); break;     // the trait object: apply is the stub
             case BlockJacobiKind: pc = std::make_unique<kryst::BlockJacobi>(blocks); break;
+            case ApproxInvKind: pc = std::make_unique<kryst::Spai>(pattern, tol, max_iter); break;
             default: throw KError(KRYST_UNSUPPORTED);
         }
         pc->setup(a);

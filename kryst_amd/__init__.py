@@ -22,7 +22,7 @@ from . import _ffi
 from ._ffi import KError, lib, check
 
 __all__ = ["Context", "DeviceVec", "CsrMatrix", "dot", "norm", "Jacobi", "Ilu0", "Ilup", "Ilut", "TrueIlu0", "Chebyshev",
-           "ChebyshevPc", "IdentityPc", "ApproxInv", "BlockJacobi", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
+           "ChebyshevPc", "IdentityPc", "ApproxInv", "BlockJacobi", "SparsityPattern", "Spai", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
            "Preconditioning", "CgSolver", "PcgSolver", "GmresSolver", "FgmresSolver", "Orthog", "CgsSolver", "TfqmrSolver", "BiCgStabSolver", "BiCgStabRightPcSolver", "Session", "KspContext", "SolverKind", "PC", "KError", "reduce_spec",
            "host_stencil7", "partition_rows", "halo_recv_plan", "read_matrix_market", "read_petsc_binary", "host_ilup", "host_ilut", "host_levels"]
 
@@ -543,8 +543,8 @@ class IdentityPc(_Pc):
 class ApproxInv(_Pc):
     """ApproxInv (SPAI) with given inverse rows: `inv_rows[i]` = [(col, value), ...] in ascending column order, the layout of
     ApproxInv::inv_rows (src/preconditioner/approxinv.rs:66).  apply (approxinv.rs:268-298) is z = M r on the device.
-    ApproxInv::setup (per-column least squares through faer's QR, approxinv.rs:129-264) stays with the reference: compute the
-    rows there and hand them over; setup() here only checks the size against the operator."""
+    setup() here only checks the size against the operator.  To compute the rows from an operator (ApproxInv::setup,
+    approxinv.rs:123-264) on the device, use `Spai(pattern, tol).setup(a)` or `PC.ApproxInv(pattern, tol, max_iter).build(a)`."""
 
     def __init__(self, inv_rows, ctx=None):
         super().__init__()
@@ -614,6 +614,81 @@ class BlockJacobi(_Pc):
         va = np.zeros(nnz.value, dtype=np.float64)
         check(lib().kryst_pc_block_jacobi_export(self.h, C.byref(nnz), rp.ctypes.data_as(_ffi.c_i64p), ci.ctypes.data_as(_ffi.c_i32p),
                                                  _dp(va)))
+        return rp, ci, va
+
+
+class SparsityPattern:
+    """SparsityPattern (src/preconditioner/mod.rs) for the SPAI set-up.  `SparsityPattern.Manual(pat)`: pat[j] lists the rows of column j
+    of M (n = len(pat)); a list of index lists, or a (ptr, idx) tuple of numpy arrays packed like CSR rows.  `SparsityPattern.Auto`: as
+    written, the set-up raises KError(Unsupported) (approxinv.rs:127-133: the downcasts of :301-323 never succeed).
+    `SparsityPattern.Operator` (extension): column j of M takes the stored columns of row j of A -- what Auto's code was meant to do."""
+    MANUAL, AUTO, OPERATOR = 0, 1, 2
+
+    def __init__(self, kind, ptr=None, idx=None):
+        self.kind, self.ptr, self.idx = kind, ptr, idx
+
+    def __repr__(self):
+        return {0: "SparsityPattern::Manual", 1: "SparsityPattern::Auto", 2: "SparsityPattern::Operator"}[self.kind]
+
+    @staticmethod
+    def Manual(pat):
+        if isinstance(pat, tuple) and len(pat) == 2 and all(isinstance(v, np.ndarray) for v in pat):     # (ptr, idx)
+            ptr = np.ascontiguousarray(pat[0], dtype=np.int64)
+            idx = np.ascontiguousarray(pat[1], dtype=np.int64)
+        else:
+            cols = [np.asarray(c, dtype=np.int64).ravel() for c in pat]
+            ptr = np.zeros(len(cols) + 1, dtype=np.int64)
+            np.cumsum([len(c) for c in cols], out=ptr[1:])
+            idx = np.concatenate(cols) if cols else np.zeros(0, dtype=np.int64)
+        if len(ptr) < 1 or int(ptr[0]) != 0 or int(ptr[-1]) != len(idx):
+            raise KError(102, "SparsityPattern.Manual: inconsistent (ptr, idx)")
+        return SparsityPattern(SparsityPattern.MANUAL, ptr, idx)
+
+
+SparsityPattern.Auto = SparsityPattern(SparsityPattern.AUTO)
+SparsityPattern.Operator = SparsityPattern(SparsityPattern.OPERATOR)
+
+
+class Spai(_Pc):
+    """ApproxInv::new(pattern, tol, max_iter, nbsteps, max_size, max_new, block_size, cache_size, verbose, sp) + setup(a)
+    (src/preconditioner/approxinv.rs:76-264) on the device: column j of M minimises ||A m_j - e_j||_2 over the support J_j of the
+    pattern, and inv_rows[i] keeps the (j, M_ij) with |M_ij| > tol, ascending j.  The apply is ApproxInv's (z = M r).  Only `pattern`
+    and `tol` are used; the other fields are accepted and ignored, as in the reference.  Labelled deviations: each J_j is sorted; the
+    least squares is solved on the reduced problem A[I_j, J_j] (the same minimiser) by Householder QR, so values agree with faer's to
+    rounding; errors (ArgumentError for a bad pattern or a non-square operator, FactorError for a rank-deficient or non-finite column,
+    Unsupported for a distributed operator or a column over the caps |J_j| <= 64, |I_j| <= 128, 2048 stored entries in A[:, J_j])
+    where the reference panics or gives non-finite output.  `export()` returns M as CSR."""
+
+    def __init__(self, pattern, tol, max_iter=0, nbsteps=0, max_size=0, max_new=0, block_size=0, cache_size=0, verbose=False, sp=False):
+        super().__init__()
+        if not isinstance(pattern, SparsityPattern):
+            pattern = SparsityPattern.Manual(pattern)
+        self.pattern, self.tol, self.max_iter = pattern, float(tol), max_iter
+        self.nbsteps, self.max_size, self.max_new, self.block_size = nbsteps, max_size, max_new, block_size
+        self.cache_size, self.verbose, self.sp = cache_size, verbose, sp
+
+    def setup(self, a):
+        h = _ffi.Handle()
+        p = self.pattern
+        if p.kind == SparsityPattern.MANUAL:
+            check(lib().kryst_pc_spai(a.h, p.kind, p.ptr.ctypes.data_as(_ffi.c_i64p), p.idx.ctypes.data_as(_ffi.c_i64p), len(p.ptr) - 1,
+                                      self.tol, C.byref(h)))
+        else:
+            check(lib().kryst_pc_spai(a.h, p.kind, None, None, 0, self.tol, C.byref(h)))
+        self._set(a.ctx, h)
+        self._a = a
+        return self
+
+    def export(self):
+        """M (inv_rows, approxinv.rs:66) as CSR -> (row_ptr int64, col int32, val float64)."""
+        if self.h is None:
+            raise KError(2, "preconditioner used before setup")
+        nnz = C.c_int64()
+        check(lib().kryst_pc_spai_export(self.h, C.byref(nnz), None, None, None))
+        rp = np.zeros(self._a.nrows() + 1, dtype=np.int64)
+        ci = np.zeros(nnz.value, dtype=np.int32)
+        va = np.zeros(nnz.value, dtype=np.float64)
+        check(lib().kryst_pc_spai_export(self.h, C.byref(nnz), rp.ctypes.data_as(_ffi.c_i64p), ci.ctypes.data_as(_ffi.c_i32p), _dp(va)))
         return rp, ci, va
 
 
@@ -836,7 +911,7 @@ class BiCgStabRightPcSolver(_Solver):
 class PC:
     """PC<T> (src/context/pc_context.rs:36-76): the reference's configuration enum for preconditioners, plus the constructor it
     lacks -- `PC.Ilut(fill=10, droptol=1e-3).build(a)` returns the set-up device preconditioner.  Kinds outside the hot path
-    (Ssor, ApproxInv setup, Multicolor, AMG, AdditiveSchwarz) raise KError(Unsupported)."""
+    (Ssor, Multicolor, AMG, AdditiveSchwarz) raise KError(Unsupported)."""
 
     def __init__(self, kind, **params):
         self.kind, self.params = kind, params
@@ -868,6 +943,10 @@ class PC:
     def BlockJacobi(blocks):                      # pc_context.rs:67 BlockJacobi { blocks }
         return PC("BlockJacobi", blocks=blocks)
 
+    @staticmethod
+    def ApproxInv(pattern, tol, max_iter=0):        # pc_context.rs:63 ApproxInv { pattern, tol, max_iter }
+        return PC("ApproxInv", pattern=pattern, tol=tol, max_iter=max_iter)
+
     def build(self, a):
         k, q = self.kind, self.params
         if k == "Jacobi":
@@ -882,6 +961,8 @@ class PC:
             return Chebyshev(q["degree"], q["emin"], q["emax"]).setup(a)
         if k == "BlockJacobi":
             return BlockJacobi(q["blocks"]).setup(a)
+        if k == "ApproxInv":
+            return Spai(q["pattern"], q["tol"], q["max_iter"]).setup(a)
         raise KError(6, f"preconditioner kind {k} is outside the accelerated path")
 
 

@@ -99,6 +99,8 @@ SIGNATURES = {
     "kryst_pc_block_jacobi": (C.c_int32, [Handle, c_i64p, c_i64p, C.c_int64, C.POINTER(Handle)]),
     "kryst_pc_block_jacobi_uniform": (C.c_int32, [Handle, C.c_int32, C.POINTER(Handle)]),
     "kryst_pc_block_jacobi_export": (C.c_int32, [Handle, c_i64p, c_i64p, c_i32p, c_dp]),
+    "kryst_pc_spai": (C.c_int32, [Handle, C.c_int32, c_i64p, c_i64p, C.c_int64, C.c_double, C.POINTER(Handle)]),
+    "kryst_pc_spai_export": (C.c_int32, [Handle, c_i64p, c_i64p, c_i32p, c_dp]),
     "kryst_pc_apply": (C.c_int32, [Handle, Handle, Handle]),
     "kryst_pc_destroy": (C.c_int32, [Handle]),
     "kryst_bench_pc_apply": (C.c_int32, [Handle, Handle, Handle, C.c_int32, c_dp]),

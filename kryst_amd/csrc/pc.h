@@ -8,6 +8,7 @@ struct kryst_pc_s {
     kryst_ctx_t ctx = nullptr;
     int kind = 0;
     kryst_csr_t a = nullptr;          // borrowed: the operator the factors refer to
+    kryst_csr_t spai_m = nullptr;     // owned: M of a SPAI set-up on the device (spai.hip); pc->a is then M too
     int64_t n = 0;
     double* d_inv_diag = nullptr;     // JACOBI
     // ILU kinds: factor values on A's pattern + level schedule (precond.hip)

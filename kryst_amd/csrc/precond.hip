@@ -263,6 +263,7 @@ int32_t kryst_pc_destroy(kryst_pc_t pc) {
     (void)hipFree(pc->d_inv_diag); (void)hipFree(pc->d_v0); (void)hipFree(pc->d_v1); (void)hipFree(pc->d_v2);
     ilu_free(pc);
     bj_free(pc);
+    if (pc->spai_m) kryst_csr_destroy(pc->spai_m);
     delete pc;
     return KRYST_OK;
 }
