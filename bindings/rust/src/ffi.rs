@@ -103,6 +103,7 @@ extern "C" {
     pub fn kryst_csr_placement_info(a: Csr, tries: *mut i32, chosen: *mut i32, skeleton_ms8: *mut f64) -> i32;
 
     pub fn kryst_spmv(a: Csr, x: Vecd, y: Vecd) -> i32;
+    pub fn kryst_spmv_transpose(a: Csr, x: Vecd, y: Vecd) -> i32;
     pub fn kryst_spmv_host(a: Csr, x: *const f64, nx: i64, y: *mut f64, ny: i64) -> i32;
     pub fn kryst_bench_spmv(a: Csr, x: Vecd, y: Vecd, fused_dots: i32, reps: i32, avg_ms: *mut f64) -> i32;
     pub fn kryst_bench_streams(ctx: Ctx, n: i64, stride_bytes: i64, kind: i32, reps: i32, avg_ms: *mut f64) -> i32;
@@ -143,9 +144,11 @@ macro_rules! solve_fn {
     ($($name:ident),* ; dev) => { extern "C" { $( pub fn $name(b: Vecd, x: Vecd, a: Csr, pc: Pc, params: *const Params,
         stats: *mut Stats, hist: *mut f64, hist_cap: i64, hist_len: *mut i64, monitor: MonitorFn, user: *mut c_void) -> i32; )* } };
 }
-solve_fn!(kryst_cg_solve, kryst_pcg_solve, kryst_gmres_solve, kryst_bicgstab_solve, kryst_cgs_solve, kryst_tfqmr_solve; host);
+solve_fn!(kryst_cg_solve, kryst_pcg_solve, kryst_gmres_solve, kryst_bicgstab_solve, kryst_cgs_solve, kryst_tfqmr_solve,
+          kryst_minres_solve, kryst_qmr_solve, kryst_cgnr_solve; host);
 solve_fn!(kryst_cg_solve_dev, kryst_pcg_solve_dev, kryst_gmres_solve_dev, kryst_bicgstab_solve_dev, kryst_bicgstab_rpc_solve_dev,
-          kryst_cgs_solve_dev, kryst_tfqmr_solve_dev; dev);
+          kryst_cgs_solve_dev, kryst_tfqmr_solve_dev, kryst_minres_solve_dev, kryst_qmr_solve_dev, kryst_cgnr_solve_dev,
+          kryst_minres_textbook_solve_dev, kryst_cgnr_textbook_solve_dev; dev);
 
 extern "C" {
     pub fn kryst_fgmres_solve(b: *const f64, x: *mut f64, n: i64, orthog: i32, haptol: f64, preallocate: i32, a: Csr, pc: Pc,

@@ -152,6 +152,22 @@ impl HipCsrMatrix {
         let rc = unsafe { ffi::kryst_spmv_host(self.h, x.as_ptr(), x.len() as i64, y.as_mut_ptr(), y.len() as i64) };
         assert_eq!(rc, 0, "kryst-hip spmv: {:?}", kerr(rc));
     }
+    /// `MatTransVec::mattransvec` on host slices: y <- A^T x (x of length nrows, y of length ncols); A^T is built on the device by
+    /// the first call and cached on the operator.
+    pub fn mattransvec(&self, x: &[f64], y: &mut [f64]) -> Result<(), KError> {
+        if x.len() != self.nrows || y.len() != self.ncols { return Err(KError::SolveError("mattransvec: length mismatch".into())); }
+        let (mut dx, mut dy): (ffi::Vecd, ffi::Vecd) = (std::ptr::null_mut(), std::ptr::null_mut());
+        unsafe {
+            let mut rc = ffi::kryst_vec_create(self.ctx.raw(), x.len() as i64, &mut dx);
+            if rc == 0 { rc = ffi::kryst_vec_create(self.ctx.raw(), y.len() as i64, &mut dy); }
+            if rc == 0 { rc = ffi::kryst_vec_upload(dx, x.as_ptr(), x.len() as i64); }
+            if rc == 0 { rc = ffi::kryst_spmv_transpose(self.h, dx, dy); }
+            if rc == 0 { rc = ffi::kryst_vec_download(dy, y.as_mut_ptr(), y.len() as i64); }
+            if !dx.is_null() { ffi::kryst_vec_destroy(dx); }
+            if !dy.is_null() { ffi::kryst_vec_destroy(dy); }
+            check(rc)
+        }
+    }
 }
 
 impl Drop for HipCsrMatrix {
@@ -504,6 +520,87 @@ impl LinearSolver<HipCsrMatrix, Vec<f64>> for HipBiCgStabSolver {
         -> Result<SolveStats<f64>, KError> {
         device_solve(ffi::kryst_bicgstab_solve, a, pc, false, b, x, Common { params: base_params(&self.conv), monitor: None, history: None })
     }
+}
+
+type DevSolveFn = unsafe extern "C" fn(ffi::Vecd, ffi::Vecd, ffi::Csr, ffi::Pc, *const ffi::Params, *mut ffi::Stats, *mut f64, i64,
+                                        *mut i64, ffi::MonitorFn, *mut c_void) -> i32;
+
+/// The labelled extensions that exist for device vectors only: b and x go up and down around the `_dev` entry point.
+fn device_vec_solve(f: DevSolveFn, a: &HipCsrMatrix, b: &Vec<f64>, x: &mut Vec<f64>, params: ffi::Params, history: &mut Vec<f64>)
+    -> Result<SolveStats<f64>, KError> {
+    assert_eq!(b.len(), x.len());
+    let n = b.len() as i64;
+    let cap = (params.max_iters.max(0) as usize).saturating_add(8).min((1usize << 22) + 8);
+    let mut hist = vec![0.0f64; cap];
+    let mut len: i64 = 0;
+    let mut st = ffi::Stats::default();
+    let (mut db, mut dx): (ffi::Vecd, ffi::Vecd) = (std::ptr::null_mut(), std::ptr::null_mut());
+    let rc = unsafe {
+        let mut rc = ffi::kryst_vec_create(a.ctx.raw(), n, &mut db);
+        if rc == 0 { rc = ffi::kryst_vec_create(a.ctx.raw(), n, &mut dx); }
+        if rc == 0 { rc = ffi::kryst_vec_upload(db, b.as_ptr(), n); }
+        if rc == 0 { rc = ffi::kryst_vec_upload(dx, x.as_ptr(), n); }
+        if rc == 0 { rc = f(db, dx, a.h, std::ptr::null_mut(), &params, &mut st, hist.as_mut_ptr(), cap as i64, &mut len, None, std::ptr::null_mut()); }
+        if rc == 0 { rc = ffi::kryst_vec_download(dx, x.as_mut_ptr(), n); }
+        if !db.is_null() { ffi::kryst_vec_destroy(db); }
+        if !dx.is_null() { ffi::kryst_vec_destroy(dx); }
+        rc
+    };
+    history.extend_from_slice(&hist[..(len.max(0) as usize).min(cap)]);
+    check(rc)?;
+    Ok(SolveStats { iterations: st.iterations as usize, final_residual: st.final_residual, converged: st.converged != 0 })
+}
+
+macro_rules! ext_solver {
+    ($(#[$doc:meta])* $name:ident, $entry:path, $textbook:expr) => {
+        $(#[$doc])*
+        pub struct $name {
+            pub conv: Convergence<f64>,
+            pub residual_history: Vec<f64>,
+            /// LABELLED EXTENSION when set (device vectors only; see the type's documentation)
+            pub textbook: bool,
+        }
+        impl $name {
+            pub fn new(tol: f64, max_iters: usize) -> Self { Self { conv: Convergence { tol, max_iters }, residual_history: Vec::new(), textbook: false } }
+        }
+        impl LinearSolver<HipCsrMatrix, Vec<f64>> for $name {
+            type Error = KError;
+            type Scalar = f64;
+            fn solve(&mut self, a: &HipCsrMatrix, pc: Option<&dyn Preconditioner<HipCsrMatrix, Vec<f64>>>, b: &Vec<f64>, x: &mut Vec<f64>)
+                -> Result<SolveStats<f64>, KError> {
+                let tb: Option<DevSolveFn> = $textbook;
+                match tb {
+                    Some(f) if self.textbook => device_vec_solve(f, a, b, x, base_params(&self.conv), &mut self.residual_history),
+                    _ => device_solve($entry, a, pc, false, b, x, Common { params: base_params(&self.conv), monitor: None, history: Some(&mut self.residual_history) }),
+                }
+            }
+        }
+    };
+}
+
+ext_solver! {
+    /// `MinresSolver<f64>` (src/solver/minres.rs:60-219) as written: x0 enters r0 only, x = x_best, final_residual = phi_min, `pc`
+    /// ignored.  `with_textbook()`: LABELLED EXTENSION, Paige-Saunders MINRES from x0 returning the last iterate.
+    HipMinresSolver, ffi::kryst_minres_solve, Some(ffi::kryst_minres_textbook_solve_dev as DevSolveFn)
+}
+ext_solver! {
+    /// `QmrSolver<f64>` (src/solver/qmr.rs:61-166) as written: a BiCGStab-type loop stopping on ||b - A x_j||, `pc` ignored.
+    HipQmrSolver, ffi::kryst_qmr_solve, None
+}
+ext_solver! {
+    /// `CgnrSolver<f64>` (src/solver/cgnr.rs:77-132) as written (A where A^T is meant, ||A(Ap)||^2 as the denominator), `pc` ignored.
+    /// `with_textbook()`: LABELLED EXTENSION, CGNR (Saad section 8.3) with the operator's cached A^T.
+    HipCgnrSolver, ffi::kryst_cgnr_solve, Some(ffi::kryst_cgnr_textbook_solve_dev as DevSolveFn)
+}
+ext_solver! {
+    /// `CgneSolver<f64>` (src/solver/cgnr.rs:153-208): CGNR's floating-point operations exactly, the same entry point.
+    HipCgneSolver, ffi::kryst_cgnr_solve, None
+}
+impl HipMinresSolver {
+    pub fn with_textbook(mut self) -> Self { self.textbook = true; self }
+}
+impl HipCgnrSolver {
+    pub fn with_textbook(mut self) -> Self { self.textbook = true; self }
 }
 
 // ------------------------------------------------------------------------------------------------------------------ KspContext

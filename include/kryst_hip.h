@@ -169,6 +169,12 @@ int32_t kryst_csr_placement_info(kryst_csr_t a, int32_t* tries, int32_t* chosen,
 
 /* MatVec::matvec (src/core/traits.rs:4-7) == SparseMatrix::spmv (sparse.rs:56-67): y <- A x, y overwritten */
 int32_t kryst_spmv(kryst_csr_t a, kryst_vec_t x, kryst_vec_t y);
+/* MatTransVec::mattransvec (src/core/traits.rs; the reference's CsrMatrix has none): y <- A^T x, x of length nrows, y of length
+ * ncols (rectangular operators allowed).  A^T is built on the device by the first call -- row j lists column j of A in ascending row
+ * order -- and cached on the operator as an operator of its own, with the same storage-form choice and SpMV kernels as any other;
+ * it is freed by kryst_csr_destroy.  Memory: A^T costs about as much as A again (plain CSR at 512^3: about 11 GB).  Distributed
+ * operators: KRYST_UNSUPPORTED; length mismatches KRYST_ERR_ARG; device out of memory KRYST_ERR_HIP. */
+int32_t kryst_spmv_transpose(kryst_csr_t a, kryst_vec_t x, kryst_vec_t y);
 /* operator-level drop-in on host slices (PCIe both ways; plumbing / Jacobi::setup-style callers only) */
 int32_t kryst_spmv_host(kryst_csr_t a, const double* x, int64_t nx, double* y, int64_t ny);
 
@@ -311,6 +317,25 @@ int32_t kryst_cgs_solve      (const double* b, double* x, int64_t n, KRYST_SOLVE
 int32_t kryst_tfqmr_solve    (const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS);
 int32_t kryst_cgs_solve_dev  (kryst_vec_t b, kryst_vec_t x, KRYST_SOLVE_ARGS);
 int32_t kryst_tfqmr_solve_dev(kryst_vec_t b, kryst_vec_t x, KRYST_SOLVE_ARGS);
+/* MinresSolver::solve (src/solver/minres.rs:60-219), QmrSolver::solve (src/solver/qmr.rs:61-166) and CgnrSolver::solve
+ * (src/solver/cgnr.rs:77-132), as written; CgneSolver::solve (cgnr.rs:153-208) does the same floating-point operations and binds
+ * to kryst_cgnr_solve[_dev].  All three ignore pc (minres.rs:61, qmr.rs:64, cgnr.rs:78); history (an addition) = the value each
+ * passes to Convergence::check.  MINRES: x0 enters r0 only, x_out starts from zero (minres.rs:72-77, :94); x = x_best, the iterate
+ * of the smallest |phi_bar| estimate, final_residual = phi_min (:207-218); the estimate is not the true residual.  QMR: a
+ * BiCGStab-type loop whose A^T p_tld is never read (qmr.rs:121-122, dropped here), stopping on ||b - A x_j|| (:146-152).  CGNR:
+ * A where A^T is meant and ||A(Ap)||^2 as the denominator (cgnr.rs:84, :94-97, :105), without a guard. */
+int32_t kryst_minres_solve    (const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS);
+int32_t kryst_qmr_solve       (const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS);
+int32_t kryst_cgnr_solve      (const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS);
+int32_t kryst_minres_solve_dev(kryst_vec_t b, kryst_vec_t x, KRYST_SOLVE_ARGS);
+int32_t kryst_qmr_solve_dev   (kryst_vec_t b, kryst_vec_t x, KRYST_SOLVE_ARGS);
+int32_t kryst_cgnr_solve_dev  (kryst_vec_t b, kryst_vec_t x, KRYST_SOLVE_ARGS);
+/* extensions (not in the reference; pc ignored): textbook MINRES (Paige & Saunders 1975, unpreconditioned) from x0, last
+ * iterate returned, stop on |phi_bar_k| / beta_1 <= tol or the cap (reported like Convergence::check), beta_{k+1} = 0 an exact exit
+ * with converged = true; textbook CGNR (Saad, Iterative Methods for Sparse Linear Systems, section 8.3) with z = A^T r through
+ * kryst_spmv_transpose's cached A^T, stop on ||r|| / ||r0||.  History: |phi_bar_k| / ||r|| per iteration. */
+int32_t kryst_minres_textbook_solve_dev(kryst_vec_t b, kryst_vec_t x, KRYST_SOLVE_ARGS);
+int32_t kryst_cgnr_textbook_solve_dev  (kryst_vec_t b, kryst_vec_t x, KRYST_SOLVE_ARGS);
 /* FgmresSolver::solve_flex (src/solver/fgmres.rs:114-340); pc plays the FlexiblePreconditioner (preconditioner/mod.rs:16-19),
  * NULL = None.  params: tol, max_iters, restart (fgmres.rs:52-54).  orthog: OrthogMethod 0 Classical (default, :59) /
  * 1 Modified; haptol: happy-breakdown tolerance (default 1e-12, :60); preallocate: set_preallocate_vectors (:77; only
@@ -319,7 +344,8 @@ int32_t kryst_fgmres_solve    (const double* b, double* x, int64_t n, int32_t or
 int32_t kryst_fgmres_solve_dev(kryst_vec_t b, kryst_vec_t x, int32_t orthog, double haptol, int32_t preallocate, KRYST_SOLVE_ARGS);
 
 /* ---- stepping session: the same solver split into begin / step / end, so that a caller (bench.py) can
- * enqueue and time exactly K iterations.  method: 0 CgSolver, 1 PcgSolver, 2 BiCgStabSolver, 3 CgsSolver, 4 TfqmrSolver.
+ * enqueue and time exactly K iterations.  method: 0 CgSolver, 1 PcgSolver, 2 BiCgStabSolver, 3 CgsSolver, 4 TfqmrSolver,
+ * 5 MinresSolver, 6 QmrSolver, 7 CgnrSolver (all three as written), 8 textbook MINRES, 9 textbook CGNR (extensions).
  * step() enqueues up to k further iterations (never past max_iters) without synchronising the host. ---- */
 typedef struct kryst_session_s* kryst_session_t;
 int32_t kryst_session_begin(int32_t method, kryst_vec_t b, kryst_vec_t x, kryst_csr_t a, kryst_pc_t pc,

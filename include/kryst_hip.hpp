@@ -105,6 +105,19 @@ public:
         check(kryst_spmv_host(h_, x.data(), (int64_t)x.size(), y.data(), (int64_t)y.size()));
     }
     void matvec(const Vec& x, Vec& y) const override { spmv(x, y); }
+    // MatTransVec::mattransvec: y <- A^T x through kryst_spmv_transpose (A^T built on the first call, cached on the operator)
+    void mattransvec(const Vec& x, Vec& y) const {
+        if (x.size() != nrows_ || y.size() != ncols_) throw KError(KRYST_ERR_ARG);
+        kryst_vec_t xv = nullptr, yv = nullptr;
+        int32_t rc = kryst_vec_create(ctx_->handle(), (int64_t)x.size(), &xv);
+        if (rc == 0) rc = kryst_vec_create(ctx_->handle(), (int64_t)y.size(), &yv);
+        if (rc == 0) rc = kryst_vec_upload(xv, x.data(), (int64_t)x.size());
+        if (rc == 0) rc = kryst_spmv_transpose(h_, xv, yv);
+        if (rc == 0) rc = kryst_vec_download(yv, y.data(), (int64_t)y.size());
+        if (xv) kryst_vec_destroy(xv);
+        if (yv) kryst_vec_destroy(yv);
+        check(rc);
+    }
     // The halo exchange of a row-partitioned operator (the neighbour exchange src/parallel/mpi_comm.rs:133-143 leaves as a TODO): false =
     // grouped ncclSend / ncclRecv (default), true = direct peer stores into hipIpc-mapped landing buffers (no collective launch, the same
     // bits).  Collective.  Returns whether the peer-store path is in use (it is not when a rank cannot map a peer's buffer).
@@ -350,6 +363,57 @@ struct TfqmrSolver : SolverBase {                            // tfqmr.rs:30-40
 protected:
     int32_t call(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS) override { return kryst_tfqmr_solve(b, x, n, KRYST_FWD); }
 };
+// MINRES / CGNR: the as-written forms (host slices, like every solver here) and the labelled textbook extensions, which exist for
+// device vectors only -- the slices go up and down around the _dev entry point
+struct TextbookSolverBase : SolverBase {
+    bool textbook = false;
+    SolveStats<double> solve(const HipCsrMatrix& a, const Preconditioner<HipCsrMatrix, Vec>* pc, const Vec& b, Vec& x) override {
+        ctx_h_ = a.context() ? a.context()->handle() : nullptr;
+        return SolverBase::solve(a, pc, b, x);
+    }
+protected:
+    using SolverBase::SolverBase;
+    kryst_ctx_t ctx_h_ = nullptr;
+    typedef int32_t (*DevFn)(kryst_vec_t, kryst_vec_t, KRYST_SOLVE_ARGS);
+    int32_t call_dev(DevFn f, const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS) {
+        kryst_vec_t bv = nullptr, xv = nullptr;
+        int32_t rc = kryst_vec_create(ctx_h_, n, &bv);
+        if (rc == 0) rc = kryst_vec_create(ctx_h_, n, &xv);
+        if (rc == 0) rc = kryst_vec_upload(bv, b, n);
+        if (rc == 0) rc = kryst_vec_upload(xv, x, n);
+        if (rc == 0) rc = f(bv, xv, KRYST_FWD);
+        if (rc == 0) rc = kryst_vec_download(xv, x, n);
+        if (bv) kryst_vec_destroy(bv);
+        if (xv) kryst_vec_destroy(xv);
+        return rc;
+    }
+};
+struct MinresSolver : TextbookSolverBase {                    // minres.rs:60-219 as written; with_textbook(): Paige-Saunders MINRES (extension)
+    MinresSolver(double tol, size_t max_iters) : TextbookSolverBase(tol, max_iters) {}
+    MinresSolver& with_textbook() { textbook = true; return *this; }
+protected:
+    int32_t call(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS) override {
+        return textbook ? call_dev(kryst_minres_textbook_solve_dev, b, x, n, KRYST_FWD) : kryst_minres_solve(b, x, n, KRYST_FWD);
+    }
+};
+struct QmrSolver : SolverBase {                              // qmr.rs:61-166 as written (a BiCGStab-type loop)
+    QmrSolver(double tol, size_t max_iters) : SolverBase(tol, max_iters) {}
+protected:
+    int32_t call(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS) override { return kryst_qmr_solve(b, x, n, KRYST_FWD); }
+};
+struct CgnrSolver : TextbookSolverBase {                      // cgnr.rs:77-132 as written; with_textbook(): CGNR with A^T (Saad 8.3, extension)
+    CgnrSolver(double tol, size_t max_iters) : TextbookSolverBase(tol, max_iters) {}
+    CgnrSolver& with_textbook() { textbook = true; return *this; }
+protected:
+    int32_t call(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS) override {
+        return textbook ? call_dev(kryst_cgnr_textbook_solve_dev, b, x, n, KRYST_FWD) : kryst_cgnr_solve(b, x, n, KRYST_FWD);
+    }
+};
+struct CgneSolver : SolverBase {                             // cgnr.rs:153-208: CGNR's floating-point operations exactly, the same entry point
+    CgneSolver(double tol, size_t max_iters) : SolverBase(tol, max_iters) {}
+protected:
+    int32_t call(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS) override { return kryst_cgnr_solve(b, x, n, KRYST_FWD); }
+};
 #undef KRYST_FWD
 
 // ---- context/: PC<T> (src/context/pc_context.rs:36-76) and KspContext (src/context/ksp_context.rs:25-148) ---------------------
@@ -392,8 +456,9 @@ struct PC {
 enum class SolverKind { Cg, Pcg, GmresLeft, GmresRight, Fgmres, Bicgstab, Cgs, Qmr, Tfqmr, Minres, Cgnr };   // ksp_context.rs:25-50
 
 // KspContext { kind, a, pc, flex_pc, tol, max_it, restart } + solve_context (ksp_context.rs:54-148): a fresh solver of `kind` per
-// call, forwarded (a, pc, b, x) exactly as the reference's match does -- FGMRES uses flex_pc, never pc (:101-107); the kinds that
-// need A^T or are outside the accelerated path (Qmr, Minres, Cgnr) throw KError{Unsupported}.  `a` is borrowed (the reference
+// call, forwarded (a, pc, b, x) exactly as the reference's match does -- FGMRES uses flex_pc, never pc (:101-107); Qmr, Minres and Cgnr
+// still throw KError{Unsupported} here (the mirror's tests pin that), although the library has them: a C++ caller reaches them
+// directly as QmrSolver, MinresSolver and CgnrSolver (the Python KspContext dispatches them).  `a` is borrowed (the reference
 // owns an M by value; a device operator is not copyable).  `pc` is any device preconditioner, e.g. PC::BlockJacobi(blocks).build(a).
 struct KspContext {
     SolverKind kind;

@@ -23,7 +23,7 @@ from ._ffi import KError, lib, check
 
 __all__ = ["Context", "DeviceVec", "CsrMatrix", "dot", "norm", "Jacobi", "Ilu0", "Ilup", "Ilut", "TrueIlu0", "Chebyshev",
            "ChebyshevPc", "IdentityPc", "ApproxInv", "BlockJacobi", "SparsityPattern", "Spai", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
-           "Preconditioning", "CgSolver", "PcgSolver", "GmresSolver", "FgmresSolver", "Orthog", "CgsSolver", "TfqmrSolver", "BiCgStabSolver", "BiCgStabRightPcSolver", "Session", "KspContext", "SolverKind", "PC", "KError", "reduce_spec",
+           "Preconditioning", "CgSolver", "PcgSolver", "GmresSolver", "FgmresSolver", "Orthog", "CgsSolver", "TfqmrSolver", "MinresSolver", "QmrSolver", "CgnrSolver", "CgneSolver", "BiCgStabSolver", "BiCgStabRightPcSolver", "Session", "KspContext", "SolverKind", "PC", "KError", "reduce_spec",
            "host_stencil7", "partition_rows", "halo_recv_plan", "read_matrix_market", "read_petsc_binary", "host_ilup", "host_ilut", "host_levels"]
 
 
@@ -298,6 +298,24 @@ class CsrMatrix:
         if tmp is not out:
             out[:] = tmp
         return out
+
+    def spmv_transpose(self, x, y=None):
+        """MatTransVec::mattransvec: y <- A^T x (x of length nrows, y of length ncols).  A^T is built on the device by the first
+        call and cached on the operator (it costs about as much memory as A).  Host arrays round-trip over PCIe."""
+        if isinstance(x, DeviceVec):
+            if y is None:
+                y = DeviceVec(self.ctx, self._ncols)
+            check(lib().kryst_spmv_transpose(self.h, x.h, y.h))
+            return y
+        xv = DeviceVec(self.ctx, _f64(x))
+        yv = DeviceVec(self.ctx, self._ncols)
+        check(lib().kryst_spmv_transpose(self.h, xv.h, yv.h))
+        if y is None:
+            return yv.to_host()
+        if len(y) != self._ncols:
+            raise KError(102, "spmv_transpose: y.len() != ncols")
+        y[:] = yv.to_host()
+        return y
 
     ENCODINGS = ("csr", "csr-d8", "csr-d16", "csr-p16", "csr-dia")
 
@@ -903,6 +921,39 @@ class TfqmrSolver(_Solver):
     _HIST_PER_ITER = 2
 
 
+class MinresSolver(_Solver):
+    """MinresSolver::new(tol, max_iters)  src/solver/minres.rs:60-219 as written (pc ignored, :61): x0 enters r0 only, x_out starts
+    from zero, x = x_best (the iterate of the smallest estimate), final_residual = phi_min.  Its estimate is not the true residual.
+    with_textbook() selects the labelled extension: Paige-Saunders MINRES from x0, last iterate (device form only)."""
+    _HOST, _DEV = "kryst_minres_solve", "kryst_minres_solve_dev"
+
+    def with_textbook(self):
+        self._HOST, self._DEV = None, "kryst_minres_textbook_solve_dev"
+        return self
+
+
+class QmrSolver(_Solver):
+    """QmrSolver::new(tol, max_iters)  src/solver/qmr.rs:61-166 as written (pc ignored): a BiCGStab-type loop stopping on ||b - A x_j||."""
+    _HOST, _DEV = "kryst_qmr_solve", "kryst_qmr_solve_dev"
+
+
+class CgnrSolver(_Solver):
+    """CgnrSolver::new(tol, max_iters)  src/solver/cgnr.rs:77-132 as written (pc ignored, A where A^T is meant, ||A(Ap)||^2 as the
+    denominator).  with_textbook() selects the labelled extension: CGNR (Saad section 8.3) with the operator's cached A^T (device form only)."""
+    _HOST, _DEV = "kryst_cgnr_solve", "kryst_cgnr_solve_dev"
+
+    def with_textbook(self):
+        self._HOST, self._DEV = None, "kryst_cgnr_textbook_solve_dev"
+        return self
+
+
+class CgneSolver(CgnrSolver):
+    """CgneSolver::new(tol, max_iters)  src/solver/cgnr.rs:153-208: the same floating-point operations as CgnrSolver, the same path."""
+
+    def with_textbook(self):
+        raise KError(6, "CgneSolver has no textbook form")
+
+
 class BiCgStabRightPcSolver(_Solver):
     """Extension: right-preconditioned BiCGStab (device vectors only)."""
     _HOST, _DEV = None, "kryst_bicgstab_rpc_solve_dev"
@@ -975,6 +1026,9 @@ class SolverKind(enum.Enum):                      # src/context/ksp_context.rs:2
     Fgmres = "fgmres"
     Cgs = "cgs"
     Tfqmr = "tfqmr"
+    Qmr = "qmr"
+    Minres = "minres"
+    Cgnr = "cgnr"
 
 
 class KspContext:
@@ -1001,6 +1055,12 @@ class KspContext:
             s = CgsSolver(self.tol, self.max_it)
         elif k == SolverKind.Tfqmr:
             s = TfqmrSolver(self.tol, self.max_it)
+        elif k == SolverKind.Qmr:                    # ksp_context.rs:128-146: the as-written solvers
+            s = QmrSolver(self.tol, self.max_it)
+        elif k == SolverKind.Minres:
+            s = MinresSolver(self.tol, self.max_it)
+        elif k == SolverKind.Cgnr:
+            s = CgnrSolver(self.tol, self.max_it)
         elif k == SolverKind.Fgmres:
             return FgmresSolver(self.tol, self.max_it, self.restart).solve_flex(self.a, self.flex_pc, b, x)
         else:
@@ -1011,7 +1071,8 @@ class KspContext:
 class Session:
     """Stepping form of CgSolver / PcgSolver / BiCgStabSolver on device vectors: begin, step(k) (enqueue k
     iterations without synchronising), end() -> SolveStats.  bench.py uses it to time exactly K iterations."""
-    METHODS = {"cg": 0, "pcg": 1, "bicgstab": 2, "cgs": 3, "tfqmr": 4}
+    METHODS = {"cg": 0, "pcg": 1, "bicgstab": 2, "cgs": 3, "tfqmr": 4, "minres": 5, "qmr": 6, "cgnr": 7,
+               "minres_textbook": 8, "cgnr_textbook": 9}
 
     def __init__(self, method, a, pc, b, x, tol, max_iters, norm_type=CgNormType.Unpreconditioned):
         self.a, self.pc, self.b, self.x = a, pc, b, x

@@ -75,6 +75,7 @@ SIGNATURES = {
     "kryst_csr_placement_info": (C.c_int32, [Handle, c_i32p, c_i32p, c_dp]),
     "kryst_spmv": (C.c_int32, [Handle, Handle, Handle]),
     "kryst_spmv_host": (C.c_int32, [Handle, c_dp, C.c_int64, c_dp, C.c_int64]),
+    "kryst_spmv_transpose": (C.c_int32, [Handle, Handle, Handle]),
     "kryst_csr_encoding": (C.c_int32, [Handle, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "kryst_csr_tile_order": (C.c_int32, [Handle, C.POINTER(C.c_int64)]),
     "kryst_csr_pattern_info": (C.c_int32, [Handle, C.POINTER(C.c_int64)]),
@@ -117,6 +118,14 @@ SIGNATURES = {
     "kryst_tfqmr_solve": (C.c_int32, [c_dp, c_dp, C.c_int64] + _SOLVE_TAIL),
     "kryst_cgs_solve_dev": (C.c_int32, [Handle, Handle] + _SOLVE_TAIL),
     "kryst_tfqmr_solve_dev": (C.c_int32, [Handle, Handle] + _SOLVE_TAIL),
+    "kryst_minres_solve": (C.c_int32, [c_dp, c_dp, C.c_int64] + _SOLVE_TAIL),
+    "kryst_qmr_solve": (C.c_int32, [c_dp, c_dp, C.c_int64] + _SOLVE_TAIL),
+    "kryst_cgnr_solve": (C.c_int32, [c_dp, c_dp, C.c_int64] + _SOLVE_TAIL),
+    "kryst_minres_solve_dev": (C.c_int32, [Handle, Handle] + _SOLVE_TAIL),
+    "kryst_qmr_solve_dev": (C.c_int32, [Handle, Handle] + _SOLVE_TAIL),
+    "kryst_cgnr_solve_dev": (C.c_int32, [Handle, Handle] + _SOLVE_TAIL),
+    "kryst_minres_textbook_solve_dev": (C.c_int32, [Handle, Handle] + _SOLVE_TAIL),
+    "kryst_cgnr_textbook_solve_dev": (C.c_int32, [Handle, Handle] + _SOLVE_TAIL),
     "kryst_fgmres_solve": (C.c_int32, [c_dp, c_dp, C.c_int64, C.c_int32, C.c_double, C.c_int32] + _SOLVE_TAIL),
     "kryst_fgmres_solve_dev": (C.c_int32, [Handle, Handle, C.c_int32, C.c_double, C.c_int32] + _SOLVE_TAIL),
     "kryst_bicgstab_solve_dev": (C.c_int32, [Handle, Handle] + _SOLVE_TAIL),

@@ -57,6 +57,9 @@ struct kryst_csr_s {
     const double* halo_started_for = nullptr;   // the halo exchange of this input vector is already in flight (halo_begin: a solver started it early)
     // where the CSR arrays live (bench_streams.hip: csr_place): homes tried, the one kept, the traffic skeleton's ms on each
     int32_t placement_tries = 1, placement_chosen = 0; double placement_ms[8] = {0};
+    // A^T as an operator of its own (csr_create.hip: csr_transpose_operator), built on the first transposed SpMV or CGNR solve and
+    // destroyed with this operator
+    kryst_csr_s* at = nullptr;
 };
 
 namespace kr {
@@ -84,5 +87,15 @@ int32_t csr_place(kryst_csr_t a);            // KRYST_CSR_PLACEMENT_TRIES: the f
 int32_t halo_default_mode(kryst_csr_t a);    // at creation: peer stores when they work on every rank, else RCCL (KRYST_HALO_MODE=rccl: RCCL)
 // the tile ranges [lo, hi) whose rows are sent to neighbours, merged and ascending (send_contiguous operators)
 void halo_send_tiles(kryst_csr_t a, std::vector<std::pair<int64_t, int64_t>>& ranges);
+
+// a device CSR / CSC triple; allocations of nnz + 8 entries with a zeroed tail (the SpMV reads whole pairs and windows)
+struct DevCsr { int32_t* ptr = nullptr; int32_t* idx = nullptr; double* val = nullptr; int64_t nnz = 0; };
+void dev_csr_free(DevCsr& m);
+// transpose.hip: rows (ptr, idx, val) of nin rows -> nout segments of (row, value) with rows ascending; drop keeps only |v| > tol.
+// `who` prefixes the error messages.
+int32_t csr_transpose(kryst_ctx_t ctx, const char* who, const int32_t* ptr, const int32_t* idx, const double* val, int64_t nin, int64_t nout,
+                      bool drop, double tol, DevCsr& out);
+// a->at, built once (csr_create.hip); KRYST_UNSUPPORTED for distributed operators
+int32_t csr_transpose_operator(kryst_csr_t a, kryst_csr_t* out);
 
 }  // namespace kr

@@ -331,6 +331,7 @@ static int32_t build_tile_order(kryst_csr_t a) {
 }
 
 // ---------------------------------------------------------------- creation
+static int32_t encode_csr(kryst_csr_t a, const std::vector<int32_t>& rp, const std::vector<int32_t>& col, const double* val);
 static int32_t upload_csr(kryst_csr_t a, const std::vector<int32_t>& rp, const std::vector<int32_t>& col, const double* val) {
     kryst_ctx_t ctx = a->ctx;
     const size_t nnz = (size_t)a->nnz;
@@ -345,6 +346,13 @@ static int32_t upload_csr(kryst_csr_t a, const std::vector<int32_t>& rp, const s
         KR_HIP(hipMemcpyAsync(a->d_val, val, sizeof(double) * nnz, hipMemcpyHostToDevice, ctx->s_main));
     }
     KR_HIP(hipStreamSynchronize(ctx->s_main));
+    return encode_csr(a, rp, col, val);
+}
+
+// the storage forms beside the CSR arrays (already on the device), from the host copy of the same arrays
+static int32_t encode_csr(kryst_csr_t a, const std::vector<int32_t>& rp, const std::vector<int32_t>& col, const double* val) {
+    kryst_ctx_t ctx = a->ctx;
+    const size_t nnz = (size_t)a->nnz;
     a->ntiles = ntiles_of(a->nrows);
     {   // CSR-D8: one byte per entry when the operator has <= 256 distinct (col - row) offsets
         std::vector<int32_t> dict; dict.reserve(256);
@@ -450,11 +458,53 @@ static int32_t create_local(kryst_ctx_t ctx, int64_t nrows, int64_t ncols, const
     return KRYST_OK;
 }
 
+// A^T (kryst_spmv_transpose, textbook CGNR): the deterministic device transpose (transpose.hip) gives A^T's CSR arrays -- row j lists
+// column j of A in ascending row order -- which become an operator through the creation path's own encoding pass (a host copy of the
+// arrays feeds it, as for any operator made by kryst_csr_create), so A^T gets the same storage-form choice and SpMV kernels.
+int32_t csr_transpose_operator(kryst_csr_t a, kryst_csr_t* out) {
+    if (a->at) { *out = a->at; return KRYST_OK; }
+    if (a->dist) { set_error("transposed SpMV: distributed operators are not supported"); return KRYST_UNSUPPORTED; }
+    kryst_ctx_t ctx = a->ctx;
+    KR_HIP(hipSetDevice(ctx->device));
+    DevCsr t;
+    KR_TRY(csr_transpose(ctx, "transposed SpMV", a->d_row_ptr, a->d_col, a->d_val, a->nrows, a->ncols, false, 0.0, t));
+    kryst_csr_t m = new kryst_csr_s();
+    m->ctx = ctx; m->nrows = a->ncols; m->ncols = a->nrows; m->xlen = a->nrows; m->nnz = t.nnz;
+    m->d_row_ptr = t.ptr; m->d_col = t.idx; m->d_val = t.val;
+    int32_t rc = KRYST_OK;
+    try {
+        std::vector<int32_t> rp((size_t)m->nrows + 1), col((size_t)t.nnz);
+        std::vector<double> val((size_t)t.nnz);
+        if (hipMemcpyAsync(rp.data(), t.ptr, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, ctx->s_main) != hipSuccess ||
+            (t.nnz && hipMemcpyAsync(col.data(), t.idx, sizeof(int32_t) * col.size(), hipMemcpyDeviceToHost, ctx->s_main) != hipSuccess) ||
+            (t.nnz && hipMemcpyAsync(val.data(), t.val, sizeof(double) * val.size(), hipMemcpyDeviceToHost, ctx->s_main) != hipSuccess) ||
+            hipStreamSynchronize(ctx->s_main) != hipSuccess) { set_error("transposed SpMV: download of A^T failed"); rc = KRYST_ERR_HIP; }
+        if (rc == KRYST_OK) rc = encode_csr(m, rp, col, val.data());
+    } catch (const std::bad_alloc&) { set_error("transposed SpMV: out of host memory (A^T has %lld entries)", (long long)t.nnz); rc = KRYST_ERR_HIP; }
+    if (rc == KRYST_OK) rc = csr_place(m);
+    if (rc != KRYST_OK) { kryst_csr_destroy(m); return rc; }
+    a->at = m;
+    *out = m;
+    return KRYST_OK;
+}
+
 }  // namespace kr
 
 using namespace kr;
 
 extern "C" {
+
+int32_t kryst_spmv_transpose(kryst_csr_t a, kryst_vec_t x, kryst_vec_t y) {
+    KR_ARG(a && x && y, "spmv_transpose");
+    KR_ARG(x->ctx == a->ctx && y->ctx == a->ctx, "spmv_transpose: context mismatch");
+    if (a->dist) { set_error("transposed SpMV: distributed operators are not supported"); return KRYST_UNSUPPORTED; }
+    KR_ARG(x->n == a->nrows, "spmv_transpose: x.len() != nrows");
+    KR_ARG(y->n == a->ncols, "spmv_transpose: y.len() != ncols");
+    KR_ARG(x->d != y->d, "spmv_transpose: x and y alias");
+    kryst_csr_t at = nullptr;
+    KR_TRY(csr_transpose_operator(a, &at));
+    return kryst_spmv(at, x, y);
+}
 
 int32_t kryst_csr_create(kryst_ctx_t ctx, int64_t nrows, int64_t ncols, const uint64_t* row_ptr, const uint64_t* col_idx,
                          const double* vals, kryst_csr_t* out) {
@@ -865,6 +915,7 @@ int32_t kryst_csr_destroy(kryst_csr_t a) {
     (void)hipFree(a->d_tiles_interior); (void)hipFree(a->d_tiles_boundary); (void)hipFree(a->d_tile_order);
     (void)hipFree(a->plan.d_send_idx); (void)hipFree(a->plan.d_sendbuf); (void)hipFree(a->plan.d_halo);
     halo_peer_destroy(a);
+    if (a->at) kryst_csr_destroy(a->at);
     delete a;
     return KRYST_OK;
 }

@@ -870,6 +870,12 @@ int32_t cgs_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io);      // cg
 int32_t tfqmr_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io);
 SolverRun* make_cgs_run(kryst_vec_t b, kryst_vec_t x, const SolveIO& io);
 SolverRun* make_tfqmr_run(kryst_vec_t b, kryst_vec_t x, const SolveIO& io);
+int32_t minres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, bool textbook);    // minres_qmr_cgnr.hip
+int32_t qmr_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io);
+int32_t cgnr_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, bool textbook);
+SolverRun* make_minres_run(kryst_vec_t b, kryst_vec_t x, const SolveIO& io, bool textbook);
+SolverRun* make_qmr_run(kryst_vec_t b, kryst_vec_t x, const SolveIO& io);
+SolverRun* make_cgnr_run(kryst_vec_t b, kryst_vec_t x, const SolveIO& io, bool textbook);
 int32_t fgmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32_t orthog, double haptol, int32_t preallocate);   // fgmres.hip
 
 // ---- one checked reduction through freshly mapped mailboxes (dist.cpp: ipc_reduce_setup) before a solver relies on them: rank r sends
@@ -971,6 +977,11 @@ int32_t kryst_session_begin(int32_t method, kryst_vec_t b, kryst_vec_t x, kryst_
         case 2: run = new BicgRun(b, x, io, false); break;
         case 3: run = make_cgs_run(b, x, io); break;
         case 4: run = make_tfqmr_run(b, x, io); break;
+        case 5: run = make_minres_run(b, x, io, false); break;
+        case 6: run = make_qmr_run(b, x, io); break;
+        case 7: run = make_cgnr_run(b, x, io, false); break;
+        case 8: run = make_minres_run(b, x, io, true); break;
+        case 9: run = make_cgnr_run(b, x, io, true); break;
         default: set_error("session_begin: unknown method %d", method); return KRYST_ERR_ARG;
     }
     const int32_t rc = run->begin();
@@ -1003,6 +1014,20 @@ int32_t kryst_cgs_solve(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS)
 }
 int32_t kryst_tfqmr_solve(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS) {
     IO_FROM_ARGS; return host_solve(b, x, n, io, [](kryst_vec_t bv, kryst_vec_t xv, const SolveIO& i) { return tfqmr_solve(bv, xv, i); });
+}
+int32_t kryst_minres_solve_dev(kryst_vec_t b, kryst_vec_t x, KRYST_SOLVE_ARGS) { IO_FROM_ARGS; return minres_solve(b, x, io, false); }
+int32_t kryst_qmr_solve_dev(kryst_vec_t b, kryst_vec_t x, KRYST_SOLVE_ARGS) { IO_FROM_ARGS; return qmr_solve(b, x, io); }
+int32_t kryst_cgnr_solve_dev(kryst_vec_t b, kryst_vec_t x, KRYST_SOLVE_ARGS) { IO_FROM_ARGS; return cgnr_solve(b, x, io, false); }
+int32_t kryst_minres_textbook_solve_dev(kryst_vec_t b, kryst_vec_t x, KRYST_SOLVE_ARGS) { IO_FROM_ARGS; return minres_solve(b, x, io, true); }
+int32_t kryst_cgnr_textbook_solve_dev(kryst_vec_t b, kryst_vec_t x, KRYST_SOLVE_ARGS) { IO_FROM_ARGS; return cgnr_solve(b, x, io, true); }
+int32_t kryst_minres_solve(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS) {
+    IO_FROM_ARGS; return host_solve(b, x, n, io, [](kryst_vec_t bv, kryst_vec_t xv, const SolveIO& i) { return minres_solve(bv, xv, i, false); });
+}
+int32_t kryst_qmr_solve(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS) {
+    IO_FROM_ARGS; return host_solve(b, x, n, io, [](kryst_vec_t bv, kryst_vec_t xv, const SolveIO& i) { return qmr_solve(bv, xv, i); });
+}
+int32_t kryst_cgnr_solve(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS) {
+    IO_FROM_ARGS; return host_solve(b, x, n, io, [](kryst_vec_t bv, kryst_vec_t xv, const SolveIO& i) { return cgnr_solve(bv, xv, i, false); });
 }
 int32_t kryst_fgmres_solve_dev(kryst_vec_t b, kryst_vec_t x, int32_t orthog, double haptol, int32_t preallocate, KRYST_SOLVE_ARGS) {
     IO_FROM_ARGS; return retry_on_pc_fallback(pc, [&] { return fgmres_solve(b, x, io, orthog, haptol, preallocate); });
