@@ -9,6 +9,7 @@ pub type Vecd = *mut c_void;
 pub type Pc = *mut c_void;
 pub type Session = *mut c_void;
 pub type HostFactors = *mut c_void;
+pub type HostAmg = *mut c_void;
 
 pub const KRYST_OK: i32 = 0;
 pub const KRYST_FACTOR_ERROR: i32 = 1;
@@ -26,6 +27,9 @@ pub const KRYST_ERR_BUSY: i32 = 104;
 pub const KRYST_ILU_KRYST_COMPAT: i32 = 0;
 pub const KRYST_ILU_ILUP0: i32 = 1;
 pub const KRYST_ILU_TRUE_ILU0: i32 = 2;
+pub const KRYST_AMG_AS_WRITTEN: i32 = 0;
+pub const KRYST_AMG_SMOOTHED: i32 = 1;
+pub const KRYST_AMG_DIRECT_MAX: i32 = 4096;
 
 /// kryst_params_t
 #[repr(C)]
@@ -130,6 +134,10 @@ extern "C" {
     pub fn kryst_pc_block_jacobi_export(pc: Pc, nnz: *mut i64, row_ptr: *mut i64, col: *mut i32, val: *mut f64) -> i32;
     pub fn kryst_pc_spai(a: Csr, pattern_kind: i32, pat_ptr: *const i64, pat_idx: *const i64, pat_n: i64, tol: f64, out: *mut Pc) -> i32;
     pub fn kryst_pc_spai_export(pc: Pc, nnz: *mut i64, row_ptr: *mut i64, col: *mut i32, val: *mut f64) -> i32;
+    pub fn kryst_pc_amg(a: Csr, max_levels: i32, threshold: f64, variant: i32, nu_pre: i32, nu_post: i32, out: *mut Pc) -> i32;
+    pub fn kryst_pc_amg_info(pc: Pc, nlevels: *mut i32, rows: *mut i64, nnz: *mut i64, count: i32) -> i32;
+    pub fn kryst_pc_amg_export(pc: Pc, level: i32, which: i32, nrows: *mut i64, ncols: *mut i64, nnz: *mut i64, row_ptr: *mut i64,
+                               col: *mut i32, val: *mut f64) -> i32;
     pub fn kryst_pc_apply(pc: Pc, r: Vecd, z: Vecd) -> i32;
     pub fn kryst_pc_destroy(pc: Pc) -> i32;
     pub fn kryst_bench_pc_apply(pc: Pc, r: Vecd, z: Vecd, reps: i32, avg_ms: *mut f64) -> i32;
@@ -171,6 +179,12 @@ extern "C" {
     pub fn kryst_host_factors_sizes(f: HostFactors, n: *mut i64, nnz_l: *mut i64, nnz_u: *mut i64) -> i32;
     pub fn kryst_host_factors_get(f: HostFactors, l_ptr: *mut i64, l_col: *mut i32, l_val: *mut f64, u_ptr: *mut i64, u_col: *mut i32, u_val: *mut f64, diag: *mut f64) -> i32;
     pub fn kryst_host_factors_destroy(f: HostFactors) -> i32;
+    pub fn kryst_host_amg(n: i64, row_ptr: *const i64, col: *const i32, val: *const f64, max_levels: i32, threshold: f64, level_budget: i64,
+                          out: *mut HostAmg) -> i32;
+    pub fn kryst_host_amg_levels(h: HostAmg, nlevels: *mut i32) -> i32;
+    pub fn kryst_host_amg_get(h: HostAmg, level: i32, which: i32, nrows: *mut i64, ncols: *mut i64, nnz: *mut i64, row_ptr: *mut i64,
+                              col: *mut i32, val: *mut f64) -> i32;
+    pub fn kryst_host_amg_destroy(h: HostAmg) -> i32;
     pub fn kryst_host_levels(n: i64, ptr: *const i64, col: *const i32, forward: i32, level: *mut i32, nlevels: *mut i32) -> i32;
     pub fn kryst_host_read_matrix_market(path: *const c_char, nrows: *mut i64, ncols: *mut i64, row_ptr: *mut i64, col_idx: *mut i64,
                                          vals: *mut f64) -> i64;

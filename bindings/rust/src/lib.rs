@@ -236,6 +236,11 @@ fn pc_apply_host(ctx: &HipContext, pc: ffi::Pc, r: &Vec<f64>, z: &mut Vec<f64>) 
         check(ffi::kryst_vec_create(ctx.raw(), n, &mut dr))?;
         let mut rc = ffi::kryst_vec_create(ctx.raw(), n, &mut dz);
         if rc == 0 { rc = ffi::kryst_vec_upload(dr, r.as_ptr(), n); }
+        // AMG as written starts from the incoming z (amg.rs:211): hand it z; every other kind overwrites z whatever it holds
+        let mut nl: i32 = 0;
+        if rc == 0 && ffi::kryst_pc_amg_info(pc, &mut nl, std::ptr::null_mut(), std::ptr::null_mut(), 0) == 0 {
+            rc = ffi::kryst_vec_upload(dz, z.as_ptr(), n);
+        }
         if rc == 0 { rc = ffi::kryst_pc_apply(pc, dr, dz); }
         if rc == 0 { rc = ffi::kryst_vec_download(dz, z.as_mut_ptr(), n); }
         ffi::kryst_vec_destroy(dr);
@@ -360,6 +365,22 @@ device_pc! {
 }
 impl HipSpai {
     pub fn new(pattern: SparsityPattern, tol: f64, max_iter: usize) -> Self { Self::empty(pattern, tol, max_iter) }
+}
+
+device_pc! {
+    /// `AMG::new(a, max_levels, threshold)` (src/preconditioner/amg.rs:73-118) as written, set up on the host and applied on the device
+    /// (`apply_recursive`, :200-250: one undamped Jacobi sweep before and after the coarse correction, the finest level from the incoming
+    /// z, CG on the coarsest level).  Errors (include/kryst_hip.h, kryst_pc_amg): `FactorError` when a coarse level exceeds the fill
+    /// budget, `Unsupported` when the coarsest level has more than 4096 rows.  Unverified source like the rest of this crate (never compiled).
+    HipAmg { max_levels: usize = 10, threshold: f64 = 0.1, textbook: bool = false, nu_pre: usize = 1, nu_post: usize = 1 } setup(s, a, out) {
+        let variant = if s.textbook { ffi::KRYST_AMG_SMOOTHED } else { ffi::KRYST_AMG_AS_WRITTEN };
+        ffi::kryst_pc_amg(a.h, s.max_levels.min(i32::MAX as usize) as i32, s.threshold, variant, s.nu_pre as i32, s.nu_post as i32, &mut out)
+    }
+}
+impl HipAmg {
+    pub fn new(max_levels: usize, threshold: f64) -> Self { Self::empty(max_levels, threshold, false, 1, 1) }
+    /// labelled extension: textbook smoothed aggregation set up on the device (strength theta, 2 + 2 damped Jacobi sweeps, z from zero)
+    pub fn with_textbook(max_levels: usize, theta: f64) -> Self { Self::empty(max_levels, theta, true, 2, 2) }
 }
 
 // ------------------------------------------------------------------------------------------------------------------ solvers

@@ -252,6 +252,27 @@ int32_t kryst_pc_spai(kryst_csr_t a, int32_t pattern_kind, const int64_t* pat_pt
                       kryst_pc_t* out);                                                 /* ApproxInv::setup approxinv.rs:123-264 */
 /* inv_rows (approxinv.rs:66) of a SPAI preconditioner as CSR: row_ptr == NULL: *nnz only; else row_ptr (n + 1), col and val (*nnz each) */
 int32_t kryst_pc_spai_export(kryst_pc_t pc, int64_t* nnz, int64_t* row_ptr, int32_t* col, double* val);
+/* AMG (src/preconditioner/amg.rs) with its V-cycle on the device (kryst_amd/csrc/amg.hip).  variant
+ * KRYST_AMG_AS_WRITTEN: AMG::new(a, max_levels, threshold) (amg.rs:73-118) with every quirk, set up on the host (kryst_host_amg) and
+ * uploaded; the apply is apply_recursive (:200-250): nu_pre / nu_post undamped Jacobi sweeps (the reference fixes both at 1, :115-116)
+ * around the coarse correction, the finest level starting from the INCOMING z, coarse levels from zero, and on the coarsest level
+ * solve_direct (:254-312): CG from zero for up to n iterations, stopped on the device when sqrt(r.r) < 1e-10.  The coarsest level
+ * may hold at most KRYST_AMG_DIRECT_MAX rows (else KRYST_UNSUPPORTED: its CG runs in one workgroup).  KRYST_AMG_SMOOTHED: the labelled
+ * extension, textbook smoothed aggregation set up on the device (threshold = theta of |a_ij| > theta sqrt(|a_ii a_jj|); distance-2 MIS
+ * aggregates; P = (I - 4/(3 rho) D^-1 A) P0; R = P^T; A_c = R (A P); stop at <= 64 rows, max_levels >= 1 levels or n_c > 0.8 n; block
+ * Jacobi of 64 rows on the coarsest level); its apply starts from z = 0 with nu_pre / nu_post damped Jacobi sweeps, and a zero diagonal
+ * is KRYST_ZERO_PIVOT.  Export which 3 then gives omega D^-1, which 4 the aggregates (col).  Errors: KRYST_ERR_ARG (non-square or distributed operator,
+ * rows not strictly ascending, max_levels / nu_pre / nu_post < 0), KRYST_FACTOR_ERROR (a level over the fill budget of kryst_host_amg).
+ * a is borrowed (must outlive the preconditioner); the coarse levels are owned. */
+enum { KRYST_AMG_AS_WRITTEN = 0, KRYST_AMG_SMOOTHED = 1, KRYST_AMG_DIRECT_MAX = 4096 };
+int32_t kryst_pc_amg(kryst_csr_t a, int32_t max_levels, double threshold, int32_t variant, int32_t nu_pre, int32_t nu_post, kryst_pc_t* out);
+/* *nlevels, and per level (count >= nlevels entries; either array may be NULL) the rows and the stored entries of A_l */
+int32_t kryst_pc_amg_info(kryst_pc_t pc, int32_t* nlevels, int64_t* rows, int64_t* nnz, int32_t count);
+/* A_l (which 0), P_l (1, n_l x n_{l+1}), R_l (2, n_{l+1} x n_l), D_l^-1 (3: nrows entries in val) or the aggregates (4, smoothed aggregation:
+ * nrows entries in col) of the device hierarchy, downloaded.
+ * P / R of the last level are empty (0 x 0).  row_ptr == NULL: the sizes only; else row_ptr (nrows + 1), col and val (*nnz each). */
+int32_t kryst_pc_amg_export(kryst_pc_t pc, int32_t level, int32_t which, int64_t* nrows, int64_t* ncols, int64_t* nnz, int64_t* row_ptr,
+                            int32_t* col, double* val);
 int32_t kryst_pc_apply(kryst_pc_t pc, kryst_vec_t r, kryst_vec_t z);                /* Preconditioner::apply */
 int32_t kryst_pc_destroy(kryst_pc_t pc);
 /* measurement hooks (bench.py): average ms of `reps` back-to-back applies between two HIP events on the compute stream; and what
@@ -393,6 +414,19 @@ int32_t kryst_host_factors_destroy(kryst_host_factors_t f);
  * level[i] = 1 + the highest level among the rows that row i of a strictly-lower (forward != 0: rows ascending) or strictly-upper (rows
  * descending) factor depends on, 0 when it depends on none.  *nlevels (may be NULL): the number of levels. */
 int32_t kryst_host_levels(int64_t n, const int64_t* ptr, const int32_t* col, int32_t forward, int32_t* level, int32_t* nlevels);
+
+/* AMG::new(a, max_levels, threshold) (src/preconditioner/amg.rs:73-118) as written, on host rows (strictly ascending columns, n x n): the
+ * code kryst_pc_amg runs before the upload (kryst_amd/csrc/amg_setup.cpp).  level_budget: the most entries P_l, R*A and A_{l+1} of one level
+ * may hold (<= 0: max(8 nnz(A), 65536)); KRYST_FACTOR_ERROR when a level would exceed it (the reference's coarse levels fill in).  Level l
+ * holds A_l, D_l^-1 and, except on the last level, P_l, R_l = P0_l^T and the aggregate of every row (which 4: in col, nrows entries). */
+typedef struct kryst_host_amg_s* kryst_host_amg_t;
+int32_t kryst_host_amg(int64_t n, const int64_t* row_ptr, const int32_t* col, const double* val, int32_t max_levels, double threshold,
+                       int64_t level_budget, kryst_host_amg_t* out);
+int32_t kryst_host_amg_levels(kryst_host_amg_t h, int32_t* nlevels);
+/* which: 0 A_l, 1 P_l, 2 R_l, 3 D_l^-1 (val), 4 aggregates (col); any pointer may be NULL */
+int32_t kryst_host_amg_get(kryst_host_amg_t h, int32_t level, int32_t which, int64_t* nrows, int64_t* ncols, int64_t* nnz, int64_t* row_ptr,
+                           int32_t* col, double* val);
+int32_t kryst_host_amg_destroy(kryst_host_amg_t h);
 
 /* Matrix Market coordinate file -> CSR (0-based, rows sorted, symmetric / skew-symmetric storage expanded, duplicates summed;
  * real, integer and pattern fields).  Returns nnz, or -1 (kryst_hip_last_error() says why).  Call with NULL arrays to size,

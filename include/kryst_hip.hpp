@@ -212,6 +212,18 @@ struct BlockJacobi : DevicePc {
         reset(h, a.context()->handle());
     }
 };
+// AMG::new(a, max_levels, threshold) (amg.rs:73-118) as written, set up on the host and applied on the device (kryst_pc_amg): one undamped
+// Jacobi sweep before and after the coarse correction, the finest level from the incoming z, CG on the coarsest level.  PC{AMGKind} keeps
+// throwing KError{Unsupported} (the mirror's tests pin that); construct Amg directly.
+struct Amg : DevicePc {
+    Amg(size_t max_levels = 10, double threshold = 0.1) : max_levels(max_levels), threshold(threshold) {}
+    size_t max_levels; double threshold;
+    void setup(const HipCsrMatrix& a) override {
+        kryst_pc_t h = nullptr;
+        check(kryst_pc_amg(a.handle(), (int32_t)std::min<size_t>(max_levels, INT32_MAX), threshold, KRYST_AMG_AS_WRITTEN, 1, 1, &h));
+        reset(h, a.context()->handle());
+    }
+};
 // SparsityPattern (preconditioner/mod.rs) for the SPAI set-up: Manual(pat) (pat[j] = the rows of column j of M, n = pat.size()), Auto (as
 // written: the set-up throws KError{Unsupported}, approxinv.rs:127-133), Operator (extension: the stored columns of row j of A).
 struct SparsityPattern {

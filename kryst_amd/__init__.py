@@ -22,9 +22,9 @@ from . import _ffi
 from ._ffi import KError, lib, check
 
 __all__ = ["Context", "DeviceVec", "CsrMatrix", "dot", "norm", "Jacobi", "Ilu0", "Ilup", "Ilut", "TrueIlu0", "Chebyshev",
-           "ChebyshevPc", "IdentityPc", "ApproxInv", "BlockJacobi", "SparsityPattern", "Spai", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
+           "ChebyshevPc", "IdentityPc", "ApproxInv", "BlockJacobi", "SparsityPattern", "Spai", "Amg", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
            "Preconditioning", "CgSolver", "PcgSolver", "GmresSolver", "FgmresSolver", "Orthog", "CgsSolver", "TfqmrSolver", "MinresSolver", "QmrSolver", "CgnrSolver", "CgneSolver", "BiCgStabSolver", "BiCgStabRightPcSolver", "Session", "KspContext", "SolverKind", "PC", "KError", "reduce_spec",
-           "host_stencil7", "partition_rows", "halo_recv_plan", "read_matrix_market", "read_petsc_binary", "host_ilup", "host_ilut", "host_levels"]
+           "host_stencil7", "partition_rows", "halo_recv_plan", "read_matrix_market", "read_petsc_binary", "host_ilup", "host_ilut", "host_amg", "host_levels"]
 
 
 def _dp(a):
@@ -710,6 +710,76 @@ class Spai(_Pc):
         return rp, ci, va
 
 
+class Amg(_Pc):
+    """AMG::new(a, max_levels, threshold) (src/preconditioner/amg.rs:73-118) as written, with its V-cycle on the device (kryst_pc_amg).
+    The set-up runs on the host, quirks included: the adaptive threshold, double-pairwise aggregation, P = rows of (P0 - 0.5 A[:, :nc])
+    scaled to unit norm, R = P0^T, A_c = (R A) P.  The apply is apply_recursive (:200-250): one undamped Jacobi sweep before and after
+    the coarse correction, the finest level starting from the incoming z (zeros when `apply` makes z), and CG from zero on the coarsest
+    level (at most 4096 rows).  The coarse levels fill in: a level over the fill budget raises KError(FactorError).  `info()` and
+    `export()` show the hierarchy."""
+
+    def __init__(self, max_levels=10, threshold=0.1):
+        super().__init__()
+        self.max_levels, self.threshold = int(max_levels), float(threshold)
+        self.variant, self.nu_pre, self.nu_post = 0, 1, 1
+
+    def with_textbook(self, theta=0.0):
+        """LABELLED EXTENSION (not in the reference): textbook smoothed aggregation, set up on the device (kryst_pc_amg variant 1).
+        Strength |a_ij| > theta sqrt(|a_ii a_jj|); aggregates by distance-2 MIS with hashed priorities; P = (I - 4/(3 rho) D^-1 A) P0 with
+        rho the Gershgorin bound of D^-1 A; R = P^T; A_c = R (A P); coarsening stops at <= 64 rows, max_levels levels or n_c > 0.8 n; block
+        Jacobi of 64 rows on the coarsest level; damped Jacobi (omega = 4/(3 rho)), nu_pre = nu_post = 2, z from zero: M is symmetric."""
+        self.variant, self.threshold, self.nu_pre, self.nu_post = 1, float(theta), 2, 2
+        return self
+
+    def with_sweeps(self, nu_pre, nu_post):
+        self.nu_pre, self.nu_post = int(nu_pre), int(nu_post)
+        return self
+
+    def apply(self, r, z=None):
+        """As written the finest level starts from the incoming z (amg.rs:211): a host z is uploaded (zeros when z is None)."""
+        if z is not None and not isinstance(r, DeviceVec) and self.h is not None:
+            rv, zv = DeviceVec(self.ctx, r), DeviceVec(self.ctx, _f64(z))
+            check(lib().kryst_pc_apply(self.h, rv.h, zv.h))
+            z[:] = zv.to_host()
+            return z
+        return super().apply(r, z)
+
+    def setup(self, a):
+        h = _ffi.Handle()
+        check(lib().kryst_pc_amg(a.h, self.max_levels, self.threshold, self.variant, self.nu_pre, self.nu_post, C.byref(h)))
+        self._set(a.ctx, h)
+        self._a = a
+        return self
+
+    def info(self):
+        """-> {"levels", "rows", "nnz", "operator_complexity"}: rows and stored entries of A_l per level, sum(nnz) / nnz(A_0)."""
+        nl = C.c_int32()
+        check(lib().kryst_pc_amg_info(self.h, C.byref(nl), None, None, 0))
+        rows = np.zeros(nl.value, dtype=np.int64); nnz = np.zeros(nl.value, dtype=np.int64)
+        check(lib().kryst_pc_amg_info(self.h, C.byref(nl), rows.ctypes.data_as(_ffi.c_i64p), nnz.ctypes.data_as(_ffi.c_i64p), nl.value))
+        return {"levels": nl.value, "rows": rows.tolist(), "nnz": nnz.tolist(),
+                "operator_complexity": float(nnz.sum()) / float(max(nnz[0], 1))}
+
+    def export(self, level, which):
+        """which "A", "P", "R" -> (nrows, ncols, row_ptr int64, col int32, val float64) of the device hierarchy; "Dinv" -> D_l^-1 (smoothed
+        aggregation: omega D_l^-1, what the sweep multiplies by); "agg" -> the aggregate of every row (smoothed aggregation, not the last level)."""
+        w = {"A": 0, "P": 1, "R": 2, "Dinv": 3, "agg": 4}[which]
+        nr, nc, nz = C.c_int64(), C.c_int64(), C.c_int64()
+        check(lib().kryst_pc_amg_export(self.h, level, w, C.byref(nr), C.byref(nc), C.byref(nz), None, None, None))
+        if w == 4:
+            g = np.zeros(max(nr.value, 1), dtype=np.int32)
+            check(lib().kryst_pc_amg_export(self.h, level, w, None, None, None, None, g.ctypes.data_as(_ffi.c_i32p), None))
+            return g[:nr.value]
+        if w == 3:
+            v = np.zeros(max(nr.value, 1))
+            check(lib().kryst_pc_amg_export(self.h, level, w, None, None, None, None, None, _dp(v)))
+            return v[:nr.value]
+        rp = np.zeros(nr.value + 1, dtype=np.int64)
+        ci = np.zeros(max(nz.value, 1), dtype=np.int32); va = np.zeros(max(nz.value, 1))
+        check(lib().kryst_pc_amg_export(self.h, level, w, None, None, None, rp.ctypes.data_as(_ffi.c_i64p), ci.ctypes.data_as(_ffi.c_i32p), _dp(va)))
+        return nr.value, nc.value, rp, ci[:nz.value], va[:nz.value]
+
+
 def apply_chebyshev(a, r, z, alpha, beta, m):
     """apply_chebyshev(a, r, z, alpha, beta, m)  src/preconditioner/chebyshev.rs:83-140."""
     if isinstance(r, DeviceVec):
@@ -961,8 +1031,10 @@ class BiCgStabRightPcSolver(_Solver):
 
 class PC:
     """PC<T> (src/context/pc_context.rs:36-76): the reference's configuration enum for preconditioners, plus the constructor it
-    lacks -- `PC.Ilut(fill=10, droptol=1e-3).build(a)` returns the set-up device preconditioner.  Kinds outside the hot path
-    (Ssor, Multicolor, AMG, AdditiveSchwarz) raise KError(Unsupported)."""
+    lacks -- `PC.Ilut(fill=10, droptol=1e-3).build(a)` returns the set-up device preconditioner.  PC::AMG carries no parameters in
+    the reference; `PC.AMG()` builds Amg(max_levels=10, threshold=0.1), the as-written hierarchy (a bare `PC("AMG")` without them
+    still raises KError(Unsupported), as it did before AMG existed).  Kinds outside the hot path (Ssor, Multicolor, AdditiveSchwarz)
+    raise KError(Unsupported)."""
 
     def __init__(self, kind, **params):
         self.kind, self.params = kind, params
@@ -998,6 +1070,10 @@ class PC:
     def ApproxInv(pattern, tol, max_iter=0):        # pc_context.rs:63 ApproxInv { pattern, tol, max_iter }
         return PC("ApproxInv", pattern=pattern, tol=tol, max_iter=max_iter)
 
+    @staticmethod
+    def AMG(max_levels=10, threshold=0.1):            # pc_context.rs:72 AMG (no parameters there: these are the defaults)
+        return PC("AMG", max_levels=max_levels, threshold=threshold)
+
     def build(self, a):
         k, q = self.kind, self.params
         if k == "Jacobi":
@@ -1014,6 +1090,8 @@ class PC:
             return BlockJacobi(q["blocks"]).setup(a)
         if k == "ApproxInv":
             return Spai(q["pattern"], q["tol"], q["max_iter"]).setup(a)
+        if k == "AMG" and "max_levels" in q:          # PC.AMG(...); the bare PC("AMG") keeps raising Unsupported, as before
+            return Amg(q["max_levels"], q["threshold"]).setup(a)
         raise KError(6, f"preconditioner kind {k} is outside the accelerated path")
 
 
@@ -1184,6 +1262,44 @@ def host_ilut(row_ptr, col_idx, values, fill, droptol, threads=0):
     h = _ffi.Handle()
     check(lib().kryst_host_ilut(len(rp) - 1, rp.ctypes.data_as(_ffi.c_i64p), ci.ctypes.data_as(_ffi.c_i32p), _dp(va), fill, float(droptol), threads, C.byref(h)))
     return _host_factors(h)
+
+
+def host_amg(row_ptr, col_idx, values, max_levels, threshold, level_budget=0):
+    """AMG::new(a, max_levels, threshold) (amg.rs:73-118) as written on host arrays, no GPU (kryst_host_amg): the set-up kryst_pc_amg
+    uploads.  -> list of levels, each a dict with "A", "P", "R" as (nrows, ncols, row_ptr, col, val) ("P" / "R" None on the last level),
+    "dinv" and "agg" (None on the last level).  KError(FactorError) when a level exceeds level_budget entries (<= 0: the default)."""
+    rp, ci, va = _host_rows(row_ptr, col_idx, values)
+    h = _ffi.Handle()
+    check(lib().kryst_host_amg(len(rp) - 1, rp.ctypes.data_as(_ffi.c_i64p), ci.ctypes.data_as(_ffi.c_i32p), _dp(va), int(max_levels),
+                               float(threshold), int(level_budget), C.byref(h)))
+    try:
+        nl = C.c_int32()
+        check(lib().kryst_host_amg_levels(h, C.byref(nl)))
+        out = []
+        for lv in range(nl.value):
+            d = {}
+            for w, key in ((0, "A"), (1, "P"), (2, "R")):
+                nr, nc, nz = C.c_int64(), C.c_int64(), C.c_int64()
+                check(lib().kryst_host_amg_get(h, lv, w, C.byref(nr), C.byref(nc), C.byref(nz), None, None, None))
+                if w and lv == nl.value - 1:
+                    d[key] = None
+                    continue
+                p = np.zeros(nr.value + 1, dtype=np.int64); c = np.zeros(max(nz.value, 1), dtype=np.int32); v = np.zeros(max(nz.value, 1))
+                check(lib().kryst_host_amg_get(h, lv, w, None, None, None, p.ctypes.data_as(_ffi.c_i64p), c.ctypes.data_as(_ffi.c_i32p), _dp(v)))
+                d[key] = (nr.value, nc.value, p, c[:nz.value], v[:nz.value])
+            nz = C.c_int64()
+            check(lib().kryst_host_amg_get(h, lv, 3, None, None, C.byref(nz), None, None, None))
+            dv = np.zeros(max(nz.value, 1))
+            check(lib().kryst_host_amg_get(h, lv, 3, None, None, None, None, None, _dp(dv)))
+            d["dinv"] = dv[:nz.value]
+            check(lib().kryst_host_amg_get(h, lv, 4, None, None, C.byref(nz), None, None, None))
+            ag = np.zeros(max(nz.value, 1), dtype=np.int32)
+            check(lib().kryst_host_amg_get(h, lv, 4, None, None, None, None, ag.ctypes.data_as(_ffi.c_i32p), None))
+            d["agg"] = ag[:nz.value] if nz.value else None
+            out.append(d)
+        return out
+    finally:
+        lib().kryst_host_amg_destroy(h)
 
 
 def host_levels(ptr, col, forward=True):

@@ -102,6 +102,9 @@ SIGNATURES = {
     "kryst_pc_block_jacobi_export": (C.c_int32, [Handle, c_i64p, c_i64p, c_i32p, c_dp]),
     "kryst_pc_spai": (C.c_int32, [Handle, C.c_int32, c_i64p, c_i64p, C.c_int64, C.c_double, C.POINTER(Handle)]),
     "kryst_pc_spai_export": (C.c_int32, [Handle, c_i64p, c_i64p, c_i32p, c_dp]),
+    "kryst_pc_amg": (C.c_int32, [Handle, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Handle)]),
+    "kryst_pc_amg_info": (C.c_int32, [Handle, c_i32p, c_i64p, c_i64p, C.c_int32]),
+    "kryst_pc_amg_export": (C.c_int32, [Handle, C.c_int32, C.c_int32, c_i64p, c_i64p, c_i64p, c_i64p, c_i32p, c_dp]),
     "kryst_pc_apply": (C.c_int32, [Handle, Handle, Handle]),
     "kryst_pc_destroy": (C.c_int32, [Handle]),
     "kryst_bench_pc_apply": (C.c_int32, [Handle, Handle, Handle, C.c_int32, c_dp]),
@@ -139,6 +142,10 @@ SIGNATURES = {
     "kryst_host_read_matrix_market": (C.c_int64, [C.c_char_p, c_i64p, c_i64p, c_i64p, c_i64p, c_dp]),
     "kryst_host_halo_recv_plan": (C.c_int64, [C.c_int32, C.c_int32, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p]),
     "kryst_host_ilup": (C.c_int32, [C.c_int64, c_i64p, c_i32p, c_dp, C.c_int32, C.c_int32, C.c_int64, C.POINTER(Handle)]),
+    "kryst_host_amg": (C.c_int32, [C.c_int64, c_i64p, c_i32p, c_dp, C.c_int32, C.c_double, C.c_int64, C.POINTER(Handle)]),
+    "kryst_host_amg_levels": (C.c_int32, [Handle, c_i32p]),
+    "kryst_host_amg_get": (C.c_int32, [Handle, C.c_int32, C.c_int32, c_i64p, c_i64p, c_i64p, c_i64p, c_i32p, c_dp]),
+    "kryst_host_amg_destroy": (C.c_int32, [Handle]),
     "kryst_host_ilut": (C.c_int32, [C.c_int64, c_i64p, c_i32p, c_dp, C.c_int32, C.c_double, C.c_int32, C.POINTER(Handle)]),
     "kryst_host_factors_sizes": (C.c_int32, [Handle, c_i64p, c_i64p, c_i64p]),
     "kryst_host_factors_get": (C.c_int32, [Handle, c_i64p, c_i32p, c_dp, c_i64p, c_i32p, c_dp, c_dp]),

@@ -320,7 +320,7 @@ int32_t fgmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32_t 
         for (int j = 0; j < m; ++j) {                                                             // :207
             hipLaunchKernelGGL(fg_gate_kernel, dim3(1), dim3(1), 0, ctx->s_main, st, fs, d_gate);
             KR_HIP(hipGetLastError());
-            if (pc) { rc = pc_apply_dev(pc, V[j], Z[j], d_gate); if (rc) return rc; }             // :209-212
+            if (pc) { rc = pc_apply_dev_fresh(pc, V[j], Z[j], d_gate, V[j]); if (rc) return rc; }             // :209-212
             KR_TRY(launch_spmv(a, Z[j], w, 0, nullptr, d_gate));                                  // :214-215
             // all h_col[i] = (w, v_i) from the unmodified w (:220-222 / :231-233)
             for (int i0 = 0; i0 <= j; i0 += 8) {

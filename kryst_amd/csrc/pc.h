@@ -2,7 +2,9 @@
 #pragma once
 #include "csr.h"
 
-enum { KR_PC_IDENTITY = 1, KR_PC_JACOBI = 2, KR_PC_ILU = 3, KR_PC_CHEB_STUB = 6, KR_PC_CHEB = 7, KR_PC_SPAI = 9, KR_PC_BLOCK_JACOBI = 10 };
+enum { KR_PC_IDENTITY = 1, KR_PC_JACOBI = 2, KR_PC_ILU = 3, KR_PC_CHEB_STUB = 6, KR_PC_CHEB = 7, KR_PC_SPAI = 9, KR_PC_BLOCK_JACOBI = 10, KR_PC_AMG = 11 };
+
+namespace kr { struct AmgDev; }
 
 struct kryst_pc_s {
     kryst_ctx_t ctx = nullptr;
@@ -32,6 +34,7 @@ struct kryst_pc_s {
     int32_t* d_bj_idx = nullptr;      // index-set form: each block's indices, sorted ascending
     int32_t* d_bj_owner = nullptr;    // index-set form with overlapping blocks or uncovered rows: the last block containing a row, or -1
     std::vector<int64_t> bj_ptr_h; std::vector<int32_t> bj_idx_h;
+    kr::AmgDev* amg = nullptr;        // AMG (amg.hip): the levels, their operators and work vectors
 };
 
 namespace kr {
@@ -44,6 +47,13 @@ int32_t pc_health(kryst_pc_t pc);
 bool pc_fell_back(kryst_pc_t pc);
 int32_t bj_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done);   // block_jacobi.hip
 void bj_free(kryst_pc_t pc);
+int32_t amg_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done);   // amg.hip
+// whether the apply reads z on entry (AMG as written starts its finest level from the incoming z, amg.rs:211)
+bool pc_reads_z(kryst_pc_t pc);
+// pc_apply_dev for solvers whose reference apply gets a FRESH z: z = 0 (init == nullptr; gmres.rs:244, 250, 256, 283, 311, 339) or
+// z = init (fgmres.rs:208-210: z_basis[j] = v_basis[j].clone()) first, when the preconditioner reads z; both gated by `done`
+int32_t pc_apply_dev_fresh(kryst_pc_t pc, const double* r, double* z, const int* done, const double* init);
+void amg_free(kryst_pc_t pc);
 int32_t chebyshev_dev(kryst_csr_t a, const double* r, double* z, double alpha, double beta, int64_t m,
                       double* v0, double* v1, double* v2, const int* done);
 }

@@ -845,12 +845,12 @@ struct BicgRun : SolverRun {
         const DevState* st = ws.st;
         if (keep_in_cache(n)) KR_TRY(launch_ew(ctx, BicgPOp<true>{st, r, v, pp}, n, done));
         else KR_TRY(launch_ew(ctx, BicgPOp<false>{st, r, v, pp}, n, done));                                   // :126-142
-        if (pc) { KR_TRY(pc_apply_dev(pc, pp, ph, done)); KR_TRY(launch_spmv(a, ph, v, 1, rhat, done)); }
+        if (pc) { KR_TRY(pc_apply_dev_fresh(pc, pp, ph, done, nullptr)); KR_TRY(launch_spmv(a, ph, v, 1, rhat, done)); }
         else KR_TRY(launch_spmv(a, pp, v, 1, rhat, done));                                        // :144-146 + (rhat,v)
         KR_TRY((reduce_then<1>(ctx, nt, ws.red, BicgAlphaLogic{lc})));
         KR_TRY(launch_ew(ctx, BicgSOp{st, r, v, s}, n, done));                                    // :166-188
         KR_TRY((reduce_then<1>(ctx, nt, ws.red, BicgSLogic{lc})));
-        if (pc) { KR_TRY(pc_apply_dev(pc, s, sh, done)); KR_TRY(launch_spmv(a, sh, t, 2, s, done)); }
+        if (pc) { KR_TRY(pc_apply_dev_fresh(pc, s, sh, done, nullptr)); KR_TRY(launch_spmv(a, sh, t, 2, s, done)); }
         else KR_TRY(launch_spmv(a, s, t, 2, s, done));                                            // :208-209 + (t,s),(t,t)
         KR_TRY((reduce_then<2>(ctx, nt, ws.red, BicgOmegaLogic{lc})));
         if (keep_in_cache(n)) KR_TRY(launch_ew_gated(ctx, BicgXROp<true>{st, pc ? ph : pp, pc ? sh : s, s, t, rhat, xw, r}, n, GateEarly{st}));
