@@ -1,13 +1,16 @@
 """Textbook smoothed aggregation (labelled extension; kryst_pc_amg variant 1, set up on the device in kryst_amd/csrc/amg.hip) against
-the numpy restatement (tests/amg_ref.py: sa_aggregates, sa_level)."""
+the numpy restatements (tests/amg_ref.py): the dense sa_level, and the ordered sa_level_ordered / sa_hierarchy / sa_apply, which follow
+the kernels operation by operation and give the device's bits on every level, in the V-cycle and in PCG."""
 import time
 
 import numpy as np
 import pytest
+import scipy.sparse as sp
 
 import kryst_amd as K
 from oracle import oracle as O
 import amg_ref as R
+import sa_cases as S
 
 pytestmark = pytest.mark.gpu
 
@@ -21,8 +24,23 @@ def to_dev(ctx, a):
     return K.CsrMatrix.from_csr(a.nrows, a.ncols, a.row_ptr, a.col_idx, a.vals, ctx=ctx)
 
 
-def sa(ctx, a, max_levels=10, theta=0.0):
-    return K.Amg(max_levels).with_textbook(theta).setup(to_dev(ctx, a) if isinstance(a, O.Csr) else a)
+def sa(ctx, a, max_levels=10, theta=0.0, sweeps=None):
+    amg = K.Amg(max_levels).with_textbook(theta)
+    if sweeps is not None:
+        amg.with_sweeps(*sweeps)
+    return amg.setup(to_dev(ctx, a) if isinstance(a, O.Csr) else a)
+
+
+def same_bits(x, y):
+    x = np.asarray(x, dtype=np.float64); y = np.asarray(y, dtype=np.float64)
+    return x.shape == y.shape and np.array_equal(x.view(np.int64), y.view(np.int64))
+
+
+def same_csr(g, want):
+    """an exported (nrows, ncols, row_ptr, col, val) against an oracle.Csr: the pattern exactly, the values bit for bit"""
+    nr, nc, rp, ci, va = g
+    return ((nr, nc) == (want.nrows, want.ncols) and np.array_equal(rp, want.row_ptr) and np.array_equal(ci, want.col_idx)
+            and same_bits(va, want.vals))
 
 
 def dense(t):
@@ -63,6 +81,9 @@ def test_first_level_matches_the_restatement(ctx, kind, N):
     assert relmax(gac, Ac) <= 1e-13
     assert relmax(gac, gp.T @ (a.to_dense() @ gp)) <= 1e-13           # A_c = P^T A P from the exported P and A
     assert relmax(pc.export(0, "Dinv"), wd) <= 1e-15
+    o = R.sa_level_ordered(a)                                         # ... and bit for bit against the ordered restatement
+    assert same_bits(pc.export(0, "Dinv"), o["wdinv"])
+    assert same_csr(pc.export(0, "P"), o["P"]) and same_csr(pc.export(0, "R"), o["R"]) and same_csr(pc.export(1, "A"), o["Ac"])
     info = pc.info()
     assert info["rows"][1] == agg.max() + 1 and info["rows"][-1] <= 64 or info["levels"] == 10
 
@@ -130,3 +151,193 @@ def test_full_size_setup(ctx):
     info = pc.info()
     print(f"SA set-up 256^3: {time.perf_counter() - t0:.3f} s, levels {info['rows']}, complexity {info['operator_complexity']:.3f}")
     assert info["levels"] >= 3 and info["operator_complexity"] <= 1.8
+
+
+# ----------------------------------------------------------------------------- every level, the V-cycle and PCG against the ordered restatement
+U = 2.0 ** -53
+
+# name -> (matrix, theta, max_levels)
+SA_CASES = {f"{kind}{N}": (lambda kind=kind, N=N: O.stencil7(N, kind), 0.0, 10)
+            for kind in ("poisson", "aniso", "varcoef", "convdiff") for N in (12, 24, 32)}
+SA_CASES.update({
+    "op27_12": (lambda: S.op27(12, 3), 0.0, 10),                             # 27-entry rows from level 0 on
+    "graph4000_hub": (lambda: S.graph_laplacian(4000, 5), 0.0, 10),          # a 1010-entry row; P columns of 2566 and 376 entries
+    "dirichlet12": (lambda: S.dirichlet_poisson(12), 0.0, 10),               # isolated rows, stored zeros; level 1 stalls (827 rows)
+    "aniso24_theta005": (lambda: O.stencil7(24, "aniso"), 0.05, 10),         # z-couplings weak: semi-coarsening
+    "poisson12_theta02": (lambda: O.stencil7(12), 0.2, 10),                  # nothing strong: stalls at once, one level
+    "diagonal500": (lambda: S.diagonal(500), 0.0, 10),                        # stalls at once: block Jacobi 64 x 7 + 52
+    "poisson24_cut1": (lambda: O.stencil7(24), 0.0, 1),                      # the coarsest level has more than 64 rows
+    "poisson4_single": (lambda: O.stencil7(4), 0.0, 10),                      # 64 rows: one level, block Jacobi = the exact inverse
+})
+SYMMETRIC = [k for k in SA_CASES if not k.startswith(("convdiff", "op27"))]   # M is symmetric only when A is
+SWEEPS = [None, (0, 0), (1, 0), (0, 3), (3, 3)]                              # None: the default (2, 2)
+
+_case_cache = {}
+
+
+def sa_case(name):
+    if name not in _case_cache:
+        mk, theta, ml = SA_CASES[name]
+        _case_cache[name] = (mk(), theta, ml)
+    return _case_cache[name]
+
+
+def csr_of(t):
+    nr, nc, rp, ci, va = t
+    return O.Csr(nr, nc, rp, ci.astype(np.int64), va, check=False)
+
+
+def exported_levels(pc):
+    """the device hierarchy as amg_ref levels: A, P, R (None on the last level), dinv (omega D^-1), agg"""
+    L = pc.info()["levels"]
+    out = []
+    for l in range(L):
+        last = l == L - 1
+        out.append(dict(A=csr_of(pc.export(l, "A")), P=None if last else csr_of(pc.export(l, "P")),
+                        R=None if last else csr_of(pc.export(l, "R")), dinv=pc.export(l, "Dinv"), agg=pc.export(l, "agg")))
+    return out
+
+
+@pytest.mark.parametrize("name", list(SA_CASES))
+def test_hierarchy_level_by_level_bits(ctx, name):
+    """every level l: the ordered restatement run on the device's exported A_l gives the device's aggregates, omega D^-1, P, R = P^T and
+    A_{l+1} bit for bit, and the same decision to coarsen, stop (n <= 64, max_levels) or drop a stalled level (n_c > 0.8 n)"""
+    a, theta, ml = sa_case(name)
+    pc = sa(ctx, a, ml, theta)
+    info = pc.info()
+    lv = exported_levels(pc)
+    assert info["levels"] == len(lv) and info["rows"] == [L["A"].nrows for L in lv]
+    assert same_csr(pc.export(0, "A"), a)
+    for l, L in enumerate(lv):
+        n = L["A"].nrows
+        cut = l >= ml or n <= 64
+        o = None if cut else R.sa_level_ordered(L["A"], theta)
+        stalled = o is not None and float(o["nc"]) > 0.8 * float(n)
+        if l + 1 == len(lv):                                          # the coarsest level: stopped, cut or stalled, as restated
+            assert cut or stalled, (name, l, n)
+            assert pc.export(l, "P")[0] == 0 and pc.export(l, "R")[0] == 0 and len(L["agg"]) == 0
+            assert same_bits(L["dinv"], np.zeros(n))
+            continue
+        assert not cut and not stalled, (name, l, n)
+        assert np.array_equal(L["agg"], o["agg"])
+        assert same_bits(L["dinv"], o["wdinv"])
+        assert same_csr(pc.export(l, "P"), o["P"])
+        assert same_csr(pc.export(l, "R"), o["R"])
+        assert same_csr(pc.export(l + 1, "A"), o["Ac"])
+        pt = O.Csr(L["P"].ncols, L["P"].nrows, *R.transpose_sorted(L["P"].row_ptr, L["P"].col_idx, L["P"].vals, L["P"].ncols), check=False)
+        assert same_csr(pc.export(l, "R"), pt)                        # the device's R is the device's P transposed, bitwise
+    expect = {"poisson12_theta02": [1728], "diagonal500": [500], "poisson4_single": [64]}
+    if name in expect:
+        assert info["rows"] == expect[name]
+    if name == "poisson24_cut1":
+        assert info["levels"] == 2 and info["rows"][1] > 64
+    if name == "dirichlet12":
+        assert info["levels"] == 2 and info["rows"][1] > 64           # the level after 827 rows stalls
+    if name.endswith("32") or name == "aniso24_theta005":
+        assert info["levels"] >= 3
+
+
+def test_generator_operator_gives_the_same_hierarchy(ctx):
+    """K.CsrMatrix.stencil7 (made on the device) and from_csr of oracle.stencil7 give the same hierarchy bits"""
+    for N in (12, 24):
+        p1 = sa(ctx, K.CsrMatrix.stencil7(N, ctx=ctx))
+        p2 = sa(ctx, O.stencil7(N))
+        assert p1.info() == p2.info()
+        for l in range(p1.info()["levels"]):
+            for w in ("A", "P", "R"):
+                e1, e2 = p1.export(l, w), p2.export(l, w)
+                assert e1[:2] == e2[:2] and np.array_equal(e1[2], e2[2]) and np.array_equal(e1[3], e2[3]) and same_bits(e1[4], e2[4])
+            assert same_bits(p1.export(l, "Dinv"), p2.export(l, "Dinv")) and np.array_equal(p1.export(l, "agg"), p2.export(l, "agg"))
+        r = np.random.default_rng(N).standard_normal(N ** 3)
+        assert same_bits(p1.apply(r), p2.apply(r))
+
+
+def abs_csr(c):
+    return sp.csr_matrix((np.abs(c.vals), c.col_idx, c.row_ptr), shape=(c.nrows, c.ncols))
+
+
+@pytest.mark.parametrize("name", list(SA_CASES))
+def test_vcycle_bits_and_longdouble(ctx, name):
+    """pc.apply(r) with garbage in the incoming z equals the restated V-cycle on the exported hierarchy bit for bit, for the default
+    sweeps and with_sweeps (0, 0), (1, 0), (0, 3), (3, 3); and agrees with the same recursion in np.longdouble within 64 u times the
+    absolute-value recursion (|A|, |P|, |R|, |omega D^-1|, |M_c|, |r|; subtractions as additions): 64 covers the longest chain of
+    roundings, a 64-term row of the coarsest block-Jacobi inverse"""
+    a, theta, ml = sa_case(name)
+    d = to_dev(ctx, a)
+    rng = np.random.default_rng(7)
+    r = rng.standard_normal(a.nrows)
+    for sw in SWEEPS:
+        pc = sa(ctx, d, ml, theta, sw)
+        lv = exported_levels(pc)
+        coarse, m = R.sa_coarse_block_jacobi(lv[-1]["A"])
+        nu = (2, 2) if sw is None else sw
+        want = R.sa_apply(lv, *nu, coarse=coarse)(r)
+        z = 1e3 * rng.standard_normal(a.nrows)                        # SA ignores the incoming z
+        got = pc.apply(r, z)
+        assert same_bits(got, want), (name, sw)
+        zl = R.vcycle_longdouble(lv, r, *nu, m)
+        za = R.vcycle_longdouble(lv, r, *nu, m, absval=True)
+        assert np.all(np.abs(got.astype(np.longdouble) - zl) <= 64 * U * za), (name, sw)
+
+
+@pytest.mark.parametrize("name", ["poisson8", "varcoef8", "op27_12", "aniso7"])
+def test_two_level_galerkin_orthogonality(ctx, name):
+    """with_sweeps(0, 0) on a two-level hierarchy whose coarsest level (<= 64 rows) block Jacobi inverts exactly: z = P A_c^-1 P^T r,
+    so P^T (r - A z) = 0 up to rounding: within 16 u P^T (|r| + |A| |z|) entrywise"""
+    a = {"poisson8": O.stencil7(8), "varcoef8": O.stencil7(8, "varcoef"), "op27_12": S.op27(12, 3), "aniso7": O.stencil7(7, "aniso")}[name]
+    pc = sa(ctx, a, 10, 0.0, (0, 0))
+    info = pc.info()
+    assert info["levels"] == 2 and info["rows"][1] <= 64, info
+    r = np.random.default_rng(3).standard_normal(a.nrows)
+    z = pc.apply(r)
+    P = csr_of(pc.export(0, "P"))
+    Ps = sp.csr_matrix((P.vals, P.col_idx, P.row_ptr), shape=(P.nrows, P.ncols))
+    g = Ps.T @ (r - a.spmv(z))
+    bound = 16 * U * (abs_csr(P).T @ (np.abs(r) + abs_csr(a) @ np.abs(z)))
+    assert np.all(np.abs(g) <= bound)
+    assert np.linalg.norm(Ps.T @ r) > 0 and np.max(np.abs(Ps.T @ r) / bound) > 1e6        # the bound is far below P^T r itself
+
+
+@pytest.mark.parametrize("name", SYMMETRIC)
+def test_vcycle_is_symmetric_positive_definite(ctx, name):
+    """equal sweeps before and after, z from zero, R = P^T, a symmetric coarsest inverse: M is symmetric and positive definite on a
+    symmetric A.  |u^T M v - v^T M u| within 64 u (|u|^T |M| |v| + |v|^T |M| |u|), |M| the absolute-value V-cycle"""
+    a, theta, ml = sa_case(name)
+    d = to_dev(ctx, a)
+    rng = np.random.default_rng(11)
+    for nu in ((1, 1), (2, 2), (3, 3)):
+        pc = sa(ctx, d, ml, theta, nu)
+        lv = exported_levels(pc)
+        _, m = R.sa_coarse_block_jacobi(lv[-1]["A"])
+        u, v = rng.standard_normal(a.nrows), rng.standard_normal(a.nrows)
+        mu, mv = pc.apply(u), pc.apply(v)
+        au = R.vcycle_longdouble(lv, np.abs(u), *nu, m, absval=True)
+        av = R.vcycle_longdouble(lv, np.abs(v), *nu, m, absval=True)
+        bound = 64 * U * float(np.abs(v) @ au + np.abs(u) @ av)
+        assert abs(float(u @ mv) - float(v @ mu)) <= bound, (name, nu)
+        assert u @ mu > 0 and v @ mv > 0
+
+
+@pytest.mark.parametrize("name", ["poisson24", "varcoef32", "aniso24_theta005", "graph4000_hub", "dirichlet12", "poisson12_theta02"])
+def test_pcg_follows_the_restatement(ctx, name):
+    """PCG + SA through K.PcgSolver against amg_ref.pcg driven by the restated SA apply on the exported hierarchy, with the inner
+    products in K.reduce_spec()'s order: the iteration count, x and the residual history bit for bit"""
+    a, theta, ml = sa_case(name)
+    T, V, F = K.reduce_spec()
+    rs = O.Reduce.tiled(T, V, F)
+    d = to_dev(ctx, a)
+    pc = sa(ctx, d, ml, theta)
+    lv = exported_levels(pc)
+    apply = R.sa_apply(lv)
+    b = np.ones(a.nrows)
+    xr, it, code, hist = R.pcg(a, None, b, 1e-8, 200, rs, apply=lambda r, z: apply(r))
+    s = K.PcgSolver(1e-8, 200)
+    x = np.zeros(a.nrows)
+    if code:
+        with pytest.raises(K.KError) as e:
+            s.solve(d, pc, b, x)
+        assert e.value.code == code and e.value.stats.iterations == it
+        return
+    st = s.solve(d, pc, b, x)
+    assert st.iterations == it and code == 0
+    assert same_bits(np.asarray(s.residual_history), np.asarray(hist)) and same_bits(x, xr)

@@ -83,6 +83,46 @@ def test_spmv_transpose_bits(ctx):
             assert np.array_equal(d.spmv_transpose(x), R.transpose(a).spmv(x))
 
 
+def _transpose_bits(ctx, a, g):
+    x = g.standard_normal(a.nrows)
+    want = R.transpose(a).spmv(x)
+    for make in ("u64", "i32"):
+        if make == "u64":
+            d = to_dev(ctx, a)
+        else:
+            d = K.CsrMatrix.from_csr_i32(a.nrows, a.ncols, a.row_ptr, a.col_idx.astype(np.int32), a.vals, ctx=ctx)
+        y = d.spmv_transpose(ctx.vec(x)).to_host()
+        assert y.shape == want.shape and np.array_equal(y.view(np.int64), want.view(np.int64)), make
+
+
+def test_spmv_transpose_long_columns(ctx):
+    """columns of 33, 100 and 5 000 entries: csr_transpose sorts segments longer than 32 by heapsort (one thread per segment), whatever
+    order the atomic fill left them in"""
+    g = np.random.default_rng(21)
+    m = 6000
+    lens = [33, 100, 5000, 32, 1, 0, 257]
+    rows = np.concatenate([g.choice(m, k, replace=False) for k in lens])
+    cols = np.concatenate([np.full(k, c) for c, k in enumerate(lens)])
+    order = np.lexsort((cols, rows))
+    rows, cols = rows[order], cols[order]
+    rp = np.zeros(m + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=m), out=rp[1:])
+    a = O.Csr(m, len(lens), rp, cols, g.standard_normal(len(cols)))
+    _transpose_bits(ctx, a, g)
+
+
+def test_spmv_transpose_more_than_1024_scan_blocks(ctx):
+    """3 x 2 200 000 with empty columns at both ends: 1 075 scan blocks of 2 048 columns, so tr_scan_top_kernel's threads take more
+    than one block sum each"""
+    g = np.random.default_rng(22)
+    nc, lo, hi = 2_200_000, 100, 2_200_000 - 100
+    r0 = np.arange(lo, hi, 2); r1 = np.arange(lo, hi, 3); r2 = np.sort(g.choice(np.arange(lo, hi), 400_000, replace=False))
+    ci = np.concatenate([r0, r1, r2])
+    rp = np.array([0, len(r0), len(r0) + len(r1), len(ci)], dtype=np.int64)
+    a = O.Csr(3, nc, rp, ci, g.standard_normal(len(ci)))
+    _transpose_bits(ctx, a, g)
+
+
 def test_spmv_transpose_errors(ctx):
     a = O.Csr(3, 5, [0, 2, 3, 4], [0, 4, 1, 2], [1.0, 2.0, 3.0, 4.0])
     d = to_dev(ctx, a)

@@ -10,6 +10,7 @@ import kryst_amd as K
 from oracle import oracle as O
 import bjacobi_ref as BR
 import spai_ref as R
+from sa_cases import op27
 
 pytestmark = pytest.mark.gpu
 
@@ -49,27 +50,6 @@ def check_values(pc, a, pptr, pidx, tol):
         scale[j] = np.max(np.abs(mj)) if len(mj) else 0.0
     assert np.all(np.abs(m.vals - va) <= 1e-11 * scale[ci])
     return m
-
-
-def op27(N, seed):
-    """A nonsymmetric 27-point box operator on an N^3 grid: off-diagonals -U(0.5, 1.5), diagonal 27 + U(0, 1)."""
-    rng = np.random.default_rng(seed)
-    n = N ** 3
-    r = np.arange(n)
-    i, j, k = r % N, (r // N) % N, r // (N * N)
-    cols, vals = [], []
-    for dk in (-1, 0, 1):
-        for dj in (-1, 0, 1):
-            for di in (-1, 0, 1):
-                ok = (i + di >= 0) & (i + di < N) & (j + dj >= 0) & (j + dj < N) & (k + dk >= 0) & (k + dk < N)
-                c = np.where(ok, r + di + N * (dj + N * dk), -1)
-                v = 27.0 + rng.random(n) if (di, dj, dk) == (0, 0, 0) else -(0.5 + rng.random(n))
-                cols.append(c); vals.append(v)
-    C = np.stack(cols, 1); V = np.stack(vals, 1)
-    keep = C >= 0
-    rp = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(keep.sum(1), out=rp[1:])
-    return O.Csr(n, n, rp, C[keep], V[keep])
 
 
 def random_sparse(n, seed, density=0.02):
