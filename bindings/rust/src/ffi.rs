@@ -166,6 +166,17 @@ extern "C" {
                                   params: *const Params, stats: *mut Stats, hist: *mut f64, hist_cap: i64, hist_len: *mut i64,
                                   monitor: MonitorFn, user: *mut c_void) -> i32;
 
+    // PcaGmresSolver::solve (src/solver/pca_gmres.rs:99-312) as written; the s-step extension (device vectors only)
+    pub fn kryst_pca_gmres_solve(b: *const f64, x: *mut f64, n: i64, block_size: i32, pipeline_depth: i32, tau: f64, a: Csr, pc: Pc,
+                                 params: *const Params, stats: *mut Stats, hist: *mut f64, hist_cap: i64, hist_len: *mut i64,
+                                 monitor: MonitorFn, user: *mut c_void) -> i32;
+    pub fn kryst_pca_gmres_solve_dev(b: Vecd, x: Vecd, block_size: i32, pipeline_depth: i32, tau: f64, a: Csr, pc: Pc,
+                                     params: *const Params, stats: *mut Stats, hist: *mut f64, hist_cap: i64, hist_len: *mut i64,
+                                     monitor: MonitorFn, user: *mut c_void) -> i32;
+    pub fn kryst_pca_gmres_textbook_solve_dev(b: Vecd, x: Vecd, block_size: i32, pipeline_depth: i32, tau: f64, a: Csr, pc: Pc,
+                                              params: *const Params, stats: *mut Stats, hist: *mut f64, hist_cap: i64, hist_len: *mut i64,
+                                              monitor: MonitorFn, user: *mut c_void) -> i32;
+
     pub fn kryst_session_begin(method: i32, b: Vecd, x: Vecd, a: Csr, pc: Pc, params: *const Params, out: *mut Session) -> i32;
     pub fn kryst_session_step(s: Session, k: i64) -> i32;
     pub fn kryst_session_end(s: Session, stats: *mut Stats, hist: *mut f64, hist_cap: i64, hist_len: *mut i64) -> i32;

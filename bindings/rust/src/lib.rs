@@ -29,6 +29,7 @@ use kryst::core::traits::{Indexing, MatShape, MatVec};
 use kryst::error::KError;
 use kryst::preconditioner::Preconditioner;
 use kryst::solver::gmres::Preconditioning;
+use kryst::solver::pca_gmres::Preconditioning as PcaPreconditioning;
 use kryst::solver::LinearSolver;
 use kryst::utils::convergence::{Convergence, SolveStats};
 
@@ -622,6 +623,75 @@ impl HipMinresSolver {
 }
 impl HipCgnrSolver {
     pub fn with_textbook(mut self) -> Self { self.textbook = true; self }
+}
+
+/// `PcaGmresSolver<f64>` (src/solver/pca_gmres.rs:37-76, solve :99-312) as written: x starts from zero, no orthogonalisation, Right =
+/// M^-1 A with the update in V, the stopping block's column left out of the update.  block_size >= 2 with restart >= 2, block_size = 0
+/// and restart = 0 return `KError` (the reference panics or never returns).  `pipeline_depth` and `tau` are never read.
+/// `with_textbook()`: LABELLED EXTENSION, s-step GMRES(restart) from x0, right preconditioned, block_size = s in 1..16.
+pub struct HipPcaGmresSolver {
+    pub restart: usize,
+    pub pipeline_depth: usize,
+    pub block_size: usize,
+    pub tau: Option<f64>,
+    pub conv: Convergence<f64>,
+    pub preconditioning: PcaPreconditioning,
+    pub residual_history: Vec<f64>,
+    /// LABELLED EXTENSION when set (device vectors only)
+    pub textbook: bool,
+}
+impl HipPcaGmresSolver {
+    pub fn new(restart: usize, pipeline_depth: usize, block_size: usize, tol: f64, max_iters: usize) -> Self {
+        Self { restart, pipeline_depth, block_size, tau: None, conv: Convergence { tol, max_iters },
+               preconditioning: PcaPreconditioning::Left, residual_history: Vec::new(), textbook: false }
+    }
+    pub fn with_preconditioning(mut self, mode: PcaPreconditioning) -> Self { self.preconditioning = mode; self }
+    pub fn with_tau(mut self, tau: f64) -> Self { self.tau = Some(tau); self }
+    pub fn with_textbook(mut self) -> Self { self.textbook = true; self }
+}
+impl LinearSolver<HipCsrMatrix, Vec<f64>> for HipPcaGmresSolver {
+    type Error = KError;
+    type Scalar = f64;
+    fn solve(&mut self, a: &HipCsrMatrix, pc: Option<&dyn Preconditioner<HipCsrMatrix, Vec<f64>>>, b: &Vec<f64>, x: &mut Vec<f64>)
+        -> Result<SolveStats<f64>, KError> {
+        assert_eq!(b.len(), x.len());
+        let pch = match pc {
+            Some(p) => probe_device_pc(p).ok_or(KError::Unsupported("kryst-hip: the preconditioner is not a device preconditioner of this crate"))?,
+            None => std::ptr::null_mut(),
+        };
+        let mut params = base_params(&self.conv);
+        params.restart = self.restart as i32;
+        params.precond_side = self.preconditioning as i32;
+        let (bs, pd, tau) = (self.block_size as i32, self.pipeline_depth as i32, self.tau.unwrap_or(0.0));
+        let n = b.len() as i64;
+        let cap = (params.max_iters.max(0) as usize).saturating_add(self.restart.max(1) + 8).min((1usize << 22) + 8);
+        let mut hist = vec![0.0f64; cap];
+        let mut len: i64 = 0;
+        let mut st = ffi::Stats::default();
+        let rc = unsafe {
+            if !self.textbook {
+                ffi::kryst_pca_gmres_solve(b.as_ptr(), x.as_mut_ptr(), n, bs, pd, tau, a.h, pch, &params, &mut st, hist.as_mut_ptr(),
+                                           cap as i64, &mut len, None, std::ptr::null_mut())
+            } else {
+                let (mut db, mut dx): (ffi::Vecd, ffi::Vecd) = (std::ptr::null_mut(), std::ptr::null_mut());
+                let mut rc = ffi::kryst_vec_create(a.ctx.raw(), n, &mut db);
+                if rc == 0 { rc = ffi::kryst_vec_create(a.ctx.raw(), n, &mut dx); }
+                if rc == 0 { rc = ffi::kryst_vec_upload(db, b.as_ptr(), n); }
+                if rc == 0 { rc = ffi::kryst_vec_upload(dx, x.as_ptr(), n); }
+                if rc == 0 {
+                    rc = ffi::kryst_pca_gmres_textbook_solve_dev(db, dx, bs, pd, tau, a.h, pch, &params, &mut st, hist.as_mut_ptr(),
+                                                                cap as i64, &mut len, None, std::ptr::null_mut());
+                }
+                if rc == 0 { rc = ffi::kryst_vec_download(dx, x.as_mut_ptr(), n); }
+                if !db.is_null() { ffi::kryst_vec_destroy(db); }
+                if !dx.is_null() { ffi::kryst_vec_destroy(dx); }
+                rc
+            }
+        };
+        self.residual_history.extend_from_slice(&hist[..(len.max(0) as usize).min(cap)]);
+        check(rc)?;
+        Ok(SolveStats { iterations: st.iterations as usize, final_residual: st.final_residual, converged: st.converged != 0 })
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------ KspContext

@@ -364,6 +364,22 @@ int32_t kryst_cgnr_textbook_solve_dev  (kryst_vec_t b, kryst_vec_t x, KRYST_SOLV
 int32_t kryst_fgmres_solve    (const double* b, double* x, int64_t n, int32_t orthog, double haptol, int32_t preallocate, KRYST_SOLVE_ARGS);
 int32_t kryst_fgmres_solve_dev(kryst_vec_t b, kryst_vec_t x, int32_t orthog, double haptol, int32_t preallocate, KRYST_SOLVE_ARGS);
 
+/* PcaGmresSolver::solve (src/solver/pca_gmres.rs:99-312) as written with the default features: x starts from zero whatever the caller
+ * passes (:107) and receives the result (:310); no orthogonalisation (the subtraction is under cfg(feature = "mpi"), :181-204);
+ * Right (params->precond_side 2) applies pc after A (:152,164), Left (1, the default, :61) and None (0) never call it; the stopping
+ * block's column stays out of the update (:277); converged = ||b - A x|| <= tol ||r0|| (:304).  restart and side come from params;
+ * pipeline_depth and tau are accepted and never read (:40-45).  Deviations where the reference panics or never returns:
+ * block_size >= 2 with restart >= 2 and max_iters >= 1 (:145,151,163), block_size = 0 (:273) or restart = 0 (:120) return
+ * KRYST_ERR_ARG with x untouched.  History = |g[j+t]| handed to Convergence::check (:266-268), one per block.  Distributed
+ * operators: KRYST_UNSUPPORTED. */
+int32_t kryst_pca_gmres_solve    (const double* b, double* x, int64_t n, int32_t block_size, int32_t pipeline_depth, double tau, KRYST_SOLVE_ARGS);
+int32_t kryst_pca_gmres_solve_dev(kryst_vec_t b, kryst_vec_t x, int32_t block_size, int32_t pipeline_depth, double tau, KRYST_SOLVE_ARGS);
+/* extension (not in the reference; pca_gmres.rs:10 names it): s-step GMRES(restart) from x0, right preconditioned, block_size = s in
+ * 1..16 -- scaled monomial blocks, BCGS2 against the basis, CholQR2 within the block, columns whose first pivot keeps less than 1e-6 of
+ * their length dropped (column 0: happy breakdown).  Left with a pc: KRYST_UNSUPPORTED.  History: |g_{c+1}| per column; the stop is
+ * exact to the column; converged = ||b - A x|| <= tol ||r0|| at a cycle end. */
+int32_t kryst_pca_gmres_textbook_solve_dev(kryst_vec_t b, kryst_vec_t x, int32_t block_size, int32_t pipeline_depth, double tau, KRYST_SOLVE_ARGS);
+
 /* ---- stepping session: the same solver split into begin / step / end, so that a caller (bench.py) can
  * enqueue and time exactly K iterations.  method: 0 CgSolver, 1 PcgSolver, 2 BiCgStabSolver, 3 CgsSolver, 4 TfqmrSolver,
  * 5 MinresSolver, 6 QmrSolver, 7 CgnrSolver (all three as written), 8 textbook MINRES, 9 textbook CGNR (extensions).

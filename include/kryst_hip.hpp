@@ -408,6 +408,31 @@ protected:
         return textbook ? call_dev(kryst_minres_textbook_solve_dev, b, x, n, KRYST_FWD) : kryst_minres_solve(b, x, n, KRYST_FWD);
     }
 };
+struct PcaGmresSolver : TextbookSolverBase {                  // pca_gmres.rs:37-76, solve :99-312 as written; with_textbook(): s-step GMRES (extension)
+    size_t restart, pipeline_depth, block_size; bool has_tau = false; double tau = 0.0;
+    Preconditioning preconditioning = Preconditioning::Left;  // pca_gmres.rs:61
+    PcaGmresSolver(size_t restart, size_t pipeline_depth, size_t block_size, double tol, size_t max_iters)
+        : TextbookSolverBase(tol, max_iters), restart(restart), pipeline_depth(pipeline_depth), block_size(block_size) {
+        restart_ = (int)restart; side_ = (int)preconditioning;
+    }
+    PcaGmresSolver& with_preconditioning(Preconditioning m) { preconditioning = m; side_ = (int)m; return *this; }
+    PcaGmresSolver& with_tau(double t) { has_tau = true; tau = t; return *this; }
+    PcaGmresSolver& with_textbook() { textbook = true; return *this; }
+protected:
+    int32_t call(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS) override {
+        if (!textbook) return kryst_pca_gmres_solve(b, x, n, (int32_t)block_size, (int32_t)pipeline_depth, tau, KRYST_FWD);
+        kryst_vec_t bv = nullptr, xv = nullptr;                 // the extension exists for device vectors only
+        int32_t rc = kryst_vec_create(ctx_h_, n, &bv);
+        if (rc == 0) rc = kryst_vec_create(ctx_h_, n, &xv);
+        if (rc == 0) rc = kryst_vec_upload(bv, b, n);
+        if (rc == 0) rc = kryst_vec_upload(xv, x, n);
+        if (rc == 0) rc = kryst_pca_gmres_textbook_solve_dev(bv, xv, (int32_t)block_size, (int32_t)pipeline_depth, tau, KRYST_FWD);
+        if (rc == 0) rc = kryst_vec_download(xv, x, n);
+        if (bv) kryst_vec_destroy(bv);
+        if (xv) kryst_vec_destroy(xv);
+        return rc;
+    }
+};
 struct QmrSolver : SolverBase {                              // qmr.rs:61-166 as written (a BiCGStab-type loop)
     QmrSolver(double tol, size_t max_iters) : SolverBase(tol, max_iters) {}
 protected:

@@ -23,7 +23,7 @@ from ._ffi import KError, lib, check
 
 __all__ = ["Context", "DeviceVec", "CsrMatrix", "dot", "norm", "Jacobi", "Ilu0", "Ilup", "Ilut", "TrueIlu0", "Chebyshev",
            "ChebyshevPc", "IdentityPc", "ApproxInv", "BlockJacobi", "SparsityPattern", "Spai", "Amg", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
-           "Preconditioning", "CgSolver", "PcgSolver", "GmresSolver", "FgmresSolver", "Orthog", "CgsSolver", "TfqmrSolver", "MinresSolver", "QmrSolver", "CgnrSolver", "CgneSolver", "BiCgStabSolver", "BiCgStabRightPcSolver", "Session", "KspContext", "SolverKind", "PC", "KError", "reduce_spec",
+           "Preconditioning", "CgSolver", "PcgSolver", "GmresSolver", "FgmresSolver", "PcaGmresSolver", "Orthog", "CgsSolver", "TfqmrSolver", "MinresSolver", "QmrSolver", "CgnrSolver", "CgneSolver", "BiCgStabSolver", "BiCgStabRightPcSolver", "Session", "KspContext", "SolverKind", "PC", "KError", "reduce_spec",
            "host_stencil7", "partition_rows", "halo_recv_plan", "read_matrix_market", "read_petsc_binary", "host_ilup", "host_ilut", "host_amg", "host_levels"]
 
 
@@ -972,6 +972,39 @@ class FgmresSolver(_Solver):
 
     def solve_flex(self, a, pc, b, x):
         return self.solve(a, pc, b, x)
+
+
+class PcaGmresSolver(_Solver):
+    """PcaGmresSolver::new(restart, pipeline_depth, block_size, tol, max_iters)  src/solver/pca_gmres.rs:54-76,99-312 as written:
+    x starts from zero, no orthogonalisation (the power basis of the default features), Right = M^-1 A with the update in V, the
+    stopping block's column left out of the update, converged from the true residual.  Only blocks of one vector run: block_size >= 2
+    with restart >= 2 (where the reference panics), block_size = 0 or restart = 0 raise KError(ERR_ARG).  pipeline_depth and tau are
+    accepted and never read.  with_textbook() selects the labelled extension: s-step GMRES(restart) from x0, right preconditioned,
+    block_size = s in 1..16 (BCGS2 + CholQR2; device form only)."""
+    _HOST, _DEV = "kryst_pca_gmres_solve", "kryst_pca_gmres_solve_dev"
+
+    def __init__(self, restart, pipeline_depth, block_size, tol, max_iters):
+        super().__init__(tol, max_iters)
+        self.restart = restart
+        self.pipeline_depth = pipeline_depth
+        self.block_size = block_size
+        self.tau = None
+        self.preconditioning = Preconditioning.Left          # pca_gmres.rs:61
+
+    def _extra(self):
+        return (int(self.block_size), int(self.pipeline_depth), float(self.tau) if self.tau is not None else 0.0)
+
+    def with_preconditioning(self, mode):
+        self.preconditioning = mode
+        return self
+
+    def with_tau(self, tau):
+        self.tau = tau
+        return self
+
+    def with_textbook(self):
+        self._HOST, self._DEV = None, "kryst_pca_gmres_textbook_solve_dev"
+        return self
 
 
 class BiCgStabSolver(_Solver):
