@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- CG iterations/sec + SpMV GB/s against the HBM roofline on synthetic 3-D 7-point Poisson CSR.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         N > 1 started PLAINLY (no WORLD_SIZE in the environment): this process launches N rank processes of itself, one per GPU (self_launch below);
         under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_* set) it is one rank.
 
@@ -19,7 +19,12 @@ Workload: ONE fixed 512^3 system for every N (BASELINE.json's metric is quoted o
 on 512^3, which fits a single 288 GB GPU).  N > 1: row-partitioned in k-slabs over the ranks, halo planes and inner products over xGMI (hipIpc peer
 stores / mailboxes where a checked test transfer succeeds on every rank, else RCCL; the line says which).
 
-What the line holds (every `frac` is bytes the named kernel really moves / its HIP-event time / 8 TB/s, so it is <= 1):
+A plain run measures the headline and nothing else: set-up, W warm-up iterations, the timed batches, the dump when asked for, and a line of
+the headline fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...), config and timing (N > 1: with `scalar_reduce`, since the
+headline is the fastest bit-identical transport form).  --full adds everything below the first entry: the plain-CSR run, kernel and phase timings, GMRES(30), the PMC traffic passes, the other
+sizes and configurations and the CPU baseline; --no-256, --no-configs, --no-cpu-baseline, --phase-iters and --gmres-steps trim that.
+
+What the --full line holds (every `frac` is bytes the named kernel really moves / its HIP-event time / 8 TB/s, so it is <= 1):
   value             CG iterations/s with the operator in its default (most compact lossless) storage form
   value_sec8d       the same K iterations with KRYST_SPMV_COMPRESS=0 (= value_plain_csr): the 12-bytes-per-entry CSR arrays of SURVEY 8(d) are streamed,
                     which is what every matrix that is not a constant-coefficient stencil gets -- the figure comparable to north_star
@@ -620,10 +625,11 @@ def timed_gmres(K, ctx, group, a, pc, b, warmup, steps, batches=3, keep=None):
     return sorted(dts)[len(dts) // 2], st, dts
 
 
-def measure(K, ctx, group, grid, solver, warmup, steps, phase_iters, batches=3, gmres_steps=0, provisional=None, keep=None):
+def measure(K, ctx, group, grid, solver, warmup, steps, phase_iters, batches=3, gmres_steps=0, provisional=None, keep=None, full=True):
     """Everything measured on one grid size -> dict (the operator is built once; the plain-CSR figures re-run the same
     iterations with KRYST_SPMV_COMPRESS=0, which the library reads per session step).  `keep` (a dict) receives the outputs of the
-    headline's timed iterations (stepped / timed_gmres)."""
+    headline's timed iterations (stepped / timed_gmres).  full=False: the headline's iterations only (N > 1: with the transport forms the
+    headline chooses from), no side measurement."""
     def barrier():
         ctx.synchronize()
         group.barrier()
@@ -729,6 +735,9 @@ def measure(K, ctx, group, grid, solver, warmup, steps, phase_iters, batches=3, 
         if best == "at_spmv":                                  # (the plain-CSR and phase runs below use the headline's setting)
             settings.enter_context(env_override(group, KRYST_HALO_EARLY="0"))
     enc = a.encoding()
+    if not full:
+        settings.close()
+        return {"dt": dt, "dts": dts, "stats": stats, "enc": enc, "reduce_info": reduce_info}
     stage(rank, "timed iterations (plain CSR)")
     with env_override(group, KRYST_SPMV_COMPRESS="0"):
         dt_plain, stats_plain, dts_plain = timed_iterations()
@@ -1228,12 +1237,30 @@ def rank_main(args, group, rank, world, dev, grid):
         line.update(roofline=None, provisional=what)
         _PROVISIONAL["line"] = line
 
+    def emit(out):
+        stage(rank, "gather / print")
+        _PROVISIONAL.clear()                       # (the real line follows: the watchdog must not print a second one)
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        group.close()
+
     keep = {} if args.dump_outputs else None
-    m = measure(K, ctx, group, grid, args.solver, args.warmup, args.steps, args.phase_iters, args.batches, args.gmres_steps, provisional, keep)
+    m = measure(K, ctx, group, grid, args.solver, args.warmup, args.steps, args.phase_iters, args.batches, args.gmres_steps, provisional, keep,
+                full=args.full)
     if keep is not None:
         dump_outputs(args.dump_outputs, keep, rank, world)
         del keep
     out = headline(m["dt"], m["stats"], m["enc"])
+    timing = {"batches": len(m["dts"]), "batch_ms": [d * 1e3 for d in m["dts"]],
+              "rule": "W warm-up iterations, then `batches` batches of exactly K iterations of ONE stepping session (GMRES: one solve of exactly K "
+                      "iterations per batch), each bracketed by device synchronize + barrier on both sides, max over ranks per batch; value = K / the MEAN batch when "
+                      "the batches agree within 10 % (x is updated in batches of 8 iterations: a window of K iterations holds a whole number of those "
+                      "passes only on average), K / the MEDIAN batch when one of them is disturbed"}
+    if not args.full:
+        out["timing"] = timing
+        if world > 1:
+            out["scalar_reduce"] = m["reduce_info"]        # which transport carried the headline, and every form's figure
+        return emit(out)
     roof = m["roofline"]
     rc = m["roofline_csr"]
     fb = roof.get("fused_direction_spmv")
@@ -1263,11 +1290,7 @@ def rank_main(args, group, rank, world, dev, grid):
                      "note": "north_star's '% of HBM roofline on CSR SpMV' and the iterations/s that go with it; `roofline.frac` above prices the "
                              "default (lossless, more compact) storage form at ITS bytes"}
     out.update({
-        "timing": {"batches": len(m["dts"]), "batch_ms": [d * 1e3 for d in m["dts"]], "batch_ms_plain_csr": [d * 1e3 for d in m["dts_plain"]],
-                   "rule": "W warm-up iterations, then `batches` batches of exactly K iterations of ONE stepping session (GMRES: one solve of exactly K "
-                           "iterations per batch), each bracketed by device synchronize + barrier on both sides, max over ranks per batch; value = K / the MEAN batch when "
-                           "the batches agree within 10 % (x is updated in batches of 8 iterations: a window of K iterations holds a whole number of those "
-                           "passes only on average), K / the MEDIAN batch when one of them is disturbed"},
+        "timing": dict(timing, batch_ms_plain_csr=[d * 1e3 for d in m["dts_plain"]]),
         "value_sec8d": args.steps / m["dt_plain"],
         "value_plain_csr": args.steps / m["dt_plain"], "ms_per_step_plain_csr": m["dt_plain"] / args.steps * 1e3,
         "roofline": roof, "roofline_csr": m["roofline_csr"], "roofline_blas1": m["blas1"],
@@ -1306,11 +1329,7 @@ def rank_main(args, group, rank, world, dev, grid):
         par = [b["parity_at_size"] for b in (out["cpu_baseline"], base256 or {}) if isinstance(b, dict) and "parity_at_size" in b]
         if par:
             out["parity_at_size"] = par
-    stage(rank, "gather / print")
-    _PROVISIONAL.clear()                       # (the real line follows: the watchdog must not print a second one)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    group.close()
+    emit(out)
 
 
 def main():
@@ -1322,12 +1341,15 @@ def main():
     ap.add_argument("--grid", type=int, default=0, help="grid edge (default 512 for every N)")
     ap.add_argument("--solver", default="cg", choices=["cg", "pcg", "gmres"],
                     help="headline iteration: cg (cg.rs), pcg = Jacobi-PCG (pcg.rs), gmres = GMRES(30) Left + Jacobi (gmres.rs; a batch is one solve of K iterations)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: plain CSR, kernel and phase timings, GMRES(30), PMC traffic, the other "
+                         "sizes and configurations, the CPU baseline (a plain run times the headline's iterations only)")
     ap.add_argument("--gmres-steps", type=int, default=60,
-                    help="iterations of the GMRES(30) + Jacobi block measured beside a cg / pcg headline (whole restart cycles; 0: skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-256", action="store_true", help="skip the config1_256 block (N = 1 measures BASELINE configs[1]'s 256^3 grid too)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE configs and the variable-coefficient blocks (N = 1)")
-    ap.add_argument("--phase-iters", type=int, default=56, help="iterations of the per-phase timing run (0: skip)")
+                    help="--full: iterations of the GMRES(30) + Jacobi block measured beside a cg / pcg headline (whole restart cycles; 0: skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-256", action="store_true", help="--full: skip the config1_256 block (N = 1 measures BASELINE configs[1]'s 256^3 grid too)")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the other BASELINE configs and the variable-coefficient blocks (N = 1)")
+    ap.add_argument("--phase-iters", type=int, default=56, help="--full: iterations of the per-phase timing run (0: skip)")
     ap.add_argument("--launcher", default="auto", choices=["auto", "torch", "socket"],
                     help="N > 1 plumbing for the RCCL id / barrier: torch.distributed gloo (default) or kryst_amd/launch.py (no torch)")
     ap.add_argument("--ranks-per-process", type=int, default=1,

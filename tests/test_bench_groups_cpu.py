@@ -3,6 +3,7 @@ around the timed region (ThreadedGroup: rehearsals of 8 ranks as 4 processes x 2
 process's leader applies between two barriers."""
 import importlib.util
 import os
+import re
 import sys
 import threading
 
@@ -56,6 +57,23 @@ def test_stage_markers_and_batches_argument(capsys):
     finally:
         sys.argv = old
     assert "--batches" in capsys.readouterr().out
+
+
+def test_side_measurements_are_behind_full(capsys):
+    """A plain run times the headline only; --full (off by default) adds the side measurements, which the trimming options apply to."""
+    B = _bench()
+    sys.argv, old = ["bench.py", "--help"], sys.argv
+    try:
+        try:
+            B.main()
+        except SystemExit:
+            pass
+    finally:
+        sys.argv = old
+    text = " ".join(capsys.readouterr().out.split())
+    assert "[--full]" in text
+    for opt in ("--gmres-steps", "--no-cpu-baseline", "--no-256", "--no-configs", "--phase-iters"):
+        assert re.search(rf"{opt}( [A-Z_]+)? --full: ", text), opt
 
 
 def test_plain_gpus_n_launches_its_own_ranks_without_touching_the_gpu(tmp_path):

@@ -12,14 +12,14 @@ export KRYST_RCCL_LIB=$PWD/tests/shim/librccl_shim.so KRYST_BENCH_DEVICE=0 HSA_E
 [ -f $KRYST_RCCL_LIB ] && [ ! tests/shim/rccl_shim.cpp -nt $KRYST_RCCL_LIB ] || /opt/rocm/bin/hipcc -O2 -std=c++17 -fPIC -shared -x hip --offload-arch=gfx950 tests/shim/rccl_shim.cpp -o $KRYST_RCCL_LIB -I/opt/rocm/include -lrt || exit 1
 for L in torch socket; do
   timeout -k 10 1000 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port $((29600 + RANDOM % 300)) \
-      bench.py --gpus 8 --solver pcg --steps $K --warmup 5 --grid $G --launcher $L --phase-iters 10 --ranks-per-process 2 \
+      bench.py --gpus 8 --solver pcg --steps $K --warmup 5 --grid $G --launcher $L --phase-iters 10 --ranks-per-process 2 --full \
       > $O/rehearsal_n8_${G}_$L.json 2> $O/rehearsal_n8_${G}_$L.err || { tail -30 $O/rehearsal_n8_${G}_$L.err; exit 1; }
 done
 # five PROCESSES (with the launcher's own process six have the GPU open: the most a GPU box admits), one rank each: the form in which the
 # peer-store halo exchange is available (rank threads that share a device are refused, kryst_amd/csrc/dist.cpp: ipc_map_peers); k-slabs of
 # 102 / 103 planes
 timeout -k 10 1000 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 5 --master-addr 127.0.0.1 --master-port $((29600 + RANDOM % 300)) \
-    bench.py --gpus 5 --solver pcg --steps $K --warmup 5 --grid $G --launcher torch --phase-iters 10 \
+    bench.py --gpus 5 --solver pcg --steps $K --warmup 5 --grid $G --launcher torch --phase-iters 10 --full \
     > $O/rehearsal_n5_${G}_torch.json 2> $O/rehearsal_n5_${G}_torch.err || { tail -30 $O/rehearsal_n5_${G}_torch.err; exit 1; }
 unset KRYST_RCCL_LIB KRYST_BENCH_DEVICE
 timeout -k 10 600 python3 bench.py --gpus 1 --solver pcg --steps $K --warmup 5 --grid $G --no-256 --no-configs --no-cpu-baseline --phase-iters 10 \

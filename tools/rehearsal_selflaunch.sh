@@ -11,14 +11,14 @@ export KRYST_RCCL_LIB=$PWD/tests/shim/librccl_shim.so KRYST_BENCH_DEVICE=0 HSA_E
 unset WORLD_SIZE RANK LOCAL_RANK MASTER_ADDR MASTER_PORT
 [ -f $KRYST_RCCL_LIB ] && [ ! tests/shim/rccl_shim.cpp -nt $KRYST_RCCL_LIB ] || /opt/rocm/bin/hipcc -O2 -std=c++17 -fPIC -shared -x hip --offload-arch=gfx950 tests/shim/rccl_shim.cpp -o $KRYST_RCCL_LIB -I/opt/rocm/include -lrt || exit 1
 for S in pcg cg; do
-  timeout -k 10 1000 python3 bench.py --gpus 8 --ranks-per-process 2 --solver $S --steps $K --warmup 5 --grid $G --phase-iters 10 --gmres-steps 30 \
+  timeout -k 10 1000 python3 bench.py --gpus 8 --ranks-per-process 2 --solver $S --steps $K --warmup 5 --grid $G --phase-iters 10 --gmres-steps 30 --full \
       > $O/selflaunch_n8_${G}_$S.json 2> $O/selflaunch_n8_${G}_$S.err || { tail -30 $O/selflaunch_n8_${G}_$S.err; exit 1; }
 done
-timeout -k 10 1000 python3 bench.py --gpus 5 --solver pcg --steps $K --warmup 5 --grid $G --phase-iters 10 --gmres-steps 30 \
+timeout -k 10 1000 python3 bench.py --gpus 5 --solver pcg --steps $K --warmup 5 --grid $G --phase-iters 10 --gmres-steps 30 --full \
     > $O/selflaunch_n5_${G}_pcg.json 2> $O/selflaunch_n5_${G}_pcg.err || { tail -30 $O/selflaunch_n5_${G}_pcg.err; exit 1; }
 unset KRYST_RCCL_LIB KRYST_BENCH_DEVICE
 for S in pcg cg; do
-  timeout -k 10 600 python3 bench.py --gpus 1 --solver $S --steps $K --warmup 5 --grid $G --no-256 --no-configs --no-cpu-baseline --phase-iters 10 --gmres-steps 30 \
+  timeout -k 10 600 python3 bench.py --gpus 1 --solver $S --steps $K --warmup 5 --grid $G --no-256 --no-configs --no-cpu-baseline --phase-iters 10 --gmres-steps 30 --full \
       > $O/selflaunch_n1_${G}_$S.json 2> $O/selflaunch_n1_${G}_$S.err || { tail -30 $O/selflaunch_n1_${G}_$S.err; exit 1; }
 done
 python3 - $O $G <<'PY'
