@@ -30,6 +30,10 @@ pub const KRYST_ILU_TRUE_ILU0: i32 = 2;
 pub const KRYST_AMG_AS_WRITTEN: i32 = 0;
 pub const KRYST_AMG_SMOOTHED: i32 = 1;
 pub const KRYST_AMG_DIRECT_MAX: i32 = 4096;
+pub const KRYST_ASM_AS_WRITTEN: i32 = 0;
+pub const KRYST_ASM_GROWN: i32 = 1;
+pub const KRYST_ASM_RESTRICTED: i32 = 2;
+pub const KRYST_ASM_MAX_ROWS: i32 = 128;
 
 /// kryst_params_t
 #[repr(C)]
@@ -132,6 +136,10 @@ extern "C" {
     pub fn kryst_pc_block_jacobi(a: Csr, blk_ptr: *const i64, blk_idx: *const i64, nblocks: i64, out: *mut Pc) -> i32;
     pub fn kryst_pc_block_jacobi_uniform(a: Csr, bsize: i32, out: *mut Pc) -> i32;
     pub fn kryst_pc_block_jacobi_export(pc: Pc, nnz: *mut i64, row_ptr: *mut i64, col: *mut i32, val: *mut f64) -> i32;
+    pub fn kryst_pc_asm(a: Csr, sub_ptr: *const i64, sub_idx: *const i64, nsub: i64, overlap: i32, variant: i32, out: *mut Pc) -> i32;
+    pub fn kryst_pc_asm_uniform(a: Csr, nparts: i64, overlap: i32, variant: i32, out: *mut Pc) -> i32;
+    pub fn kryst_pc_asm_info(pc: Pc, nsub: *mut i64, ext_rows: *mut i64, max_rows: *mut i32) -> i32;
+    pub fn kryst_pc_asm_export(pc: Pc, sub_ptr: *mut i64, sub_idx: *mut i32, owner: *mut i32, tiles: *mut f64) -> i32;
     pub fn kryst_pc_spai(a: Csr, pattern_kind: i32, pat_ptr: *const i64, pat_idx: *const i64, pat_n: i64, tol: f64, out: *mut Pc) -> i32;
     pub fn kryst_pc_spai_export(pc: Pc, nnz: *mut i64, row_ptr: *mut i64, col: *mut i32, val: *mut f64) -> i32;
     pub fn kryst_pc_amg(a: Csr, max_levels: i32, threshold: f64, variant: i32, nu_pre: i32, nu_post: i32, out: *mut Pc) -> i32;

@@ -337,6 +337,32 @@ impl HipBlockJacobi {
     pub fn uniform(bsize: usize) -> Self { Self::empty(Vec::new(), bsize) }
 }
 
+device_pc! {
+    /// `AdditiveSchwarz::new(overlap, subdomains)` + `setup` + `apply` (src/preconditioner/asm.rs:34-119) with the direct solve as the
+    /// inner solver, as a device `Preconditioner`: z = 0, then every subdomain in ascending order adds its product.  Empty `subdomains`:
+    /// `nparts` uniform parts (the reference's `capacity()`; 0 gives one part).  `variant`: `KRYST_ASM_AS_WRITTEN` (overlap ignored, as
+    /// written), `KRYST_ASM_GROWN` or `KRYST_ASM_RESTRICTED` (labelled extensions: growth by `overlap` layers; RAS).  Labelled deviations
+    /// (include/kryst_hip.h, kryst_pc_asm): explicit Gauss-Jordan inverses, sorted index sets, errors instead of non-finite z; subdomains
+    /// of at most 128 rows.  Unverified source like the rest of this crate (never compiled).
+    HipAdditiveSchwarz { overlap: usize = 0, subdomains: Vec<Vec<usize>> = Vec::new(), nparts: usize = 0, variant: i32 = ffi::KRYST_ASM_AS_WRITTEN } setup(s, a, out) {
+        let ov = s.overlap.min(i32::MAX as usize) as i32;
+        if s.subdomains.is_empty() {
+            ffi::kryst_pc_asm_uniform(a.h, s.nparts as i64, ov, s.variant, &mut out)
+        } else {
+            let mut ptr: Vec<i64> = vec![0];
+            let mut idx: Vec<i64> = Vec::new();
+            for g in &s.subdomains {
+                idx.extend(g.iter().map(|&i| i as i64));
+                ptr.push(idx.len() as i64);
+            }
+            ffi::kryst_pc_asm(a.h, ptr.as_ptr(), idx.as_ptr(), s.subdomains.len() as i64, ov, s.variant, &mut out)
+        }
+    }
+}
+impl HipAdditiveSchwarz {
+    pub fn new(overlap: usize, subdomains: Vec<Vec<usize>>) -> Self { Self::empty(overlap, subdomains, 0, ffi::KRYST_ASM_AS_WRITTEN) }
+}
+
 /// `SparsityPattern` (src/preconditioner/mod.rs) for the SPAI set-up: `Manual(pat)` (pat[j] = the rows of column j of M), `Auto` (as
 /// written: `Err(Unsupported)`, approxinv.rs:127-133), `Operator` (extension: the stored columns of row j of A).
 #[derive(Clone, Debug, Default)]

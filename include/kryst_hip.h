@@ -234,6 +234,31 @@ int32_t kryst_pc_block_jacobi_uniform(kryst_csr_t a, int32_t bsize, kryst_pc_t* 
 /* the preconditioner as the CSR matrix M with z = M r: row g[i] of the block that owns it stores (g[j], Binv[i][j]) for every j of the
  * block, ascending; other rows are empty.  row_ptr == NULL: *nnz only; else row_ptr (n + 1), col and val (*nnz each) are filled. */
 int32_t kryst_pc_block_jacobi_export(kryst_pc_t pc, int64_t* nnz, int64_t* row_ptr, int32_t* col, double* val);
+/* AdditiveSchwarz::new(overlap, subdomains) + setup + apply (src/preconditioner/asm.rs:34-119) with the direct solve as the inner
+ * solver, as a device Preconditioner on the CSR operator.  sub_ptr / sub_idx: the subdomains packed like CSR rows
+ * (sub_ptr[0] = 0, nsub + 1 entries), unsorted, possibly overlapping, possibly leaving rows uncovered.  The apply is asm.rs:76-119:
+ * z = 0, then for every subdomain in ascending order z[g[i]] = z[g[i]] + (B^-1 r|_g)[i] (a row in no subdomain stays +0.0).
+ * variant KRYST_ASM_AS_WRITTEN ignores `overlap`, as the reference does; KRYST_ASM_GROWN (labelled extension) first grows every subdomain
+ * by `overlap` layers of the symmetrised graph of A (row i's neighbours: the stored columns of rows i of A and of A^T, i excluded);
+ * KRYST_ASM_RESTRICTED (RAS, labelled extension) grows them too and keeps, for every row, only the product of the last un-grown
+ * subdomain that contains it.  Labelled deviations, those of kryst_pc_block_jacobi: explicit Gauss-Jordan inverses, index sets sorted
+ * ascending, KRYST_ZERO_PIVOT (kryst_hip_last_error_row() = the global row), KRYST_FACTOR_ERROR (NaN / Inf), KRYST_ERR_ARG (index out of
+ * range or repeated in a subdomain, non-square operator, overlap < 0), KRYST_UNSUPPORTED (a subdomain of more than KRYST_ASM_MAX_ROWS
+ * rows, before or after growth -- the message names it --, a distributed operator).  The set-up checks the device memory it needs
+ * (8 sum b_k^2 bytes of tiles and the index streams) against hipMemGetInfo -- for the un-grown sets before it allocates anything, for
+ * the grown ones again before the tiles --, giving the library's device pool back to the driver first when the figure falls short:
+ * KRYST_ERR_HIP with the byte count in kryst_hip_last_error() when it does not fit.  a is borrowed (must outlive the preconditioner). */
+enum { KRYST_ASM_AS_WRITTEN = 0, KRYST_ASM_GROWN = 1, KRYST_ASM_RESTRICTED = 2, KRYST_ASM_MAX_ROWS = 128 };
+int32_t kryst_pc_asm(kryst_csr_t a, const int64_t* sub_ptr, const int64_t* sub_idx, int64_t nsub, int32_t overlap, int32_t variant, kryst_pc_t* out);
+/* asm.rs:46-56, the subdomains left empty: p = max(nparts, 1) parts of chunk = ceil(n / p) rows, part i = [i chunk, min((i + 1) chunk, n));
+ * trailing parts may be empty.  nparts stands for the reference's subdomains.capacity() (0 for Vec::new(): ONE subdomain of all n rows). */
+int32_t kryst_pc_asm_uniform(kryst_csr_t a, int64_t nparts, int32_t overlap, int32_t variant, kryst_pc_t* out);
+/* the subdomain count, the sum of their (grown) rows and the largest; any pointer may be NULL */
+int32_t kryst_pc_asm_info(kryst_pc_t pc, int64_t* nsub, int64_t* ext_rows, int32_t* max_rows);
+/* the set-up, downloaded; any pointer may be NULL (size them with kryst_pc_asm_info and a first call for sub_ptr): sub_ptr (nsub + 1) and
+ * sub_idx (ext_rows) the grown subdomains sorted ascending, owner (n) the last un-grown subdomain that contains each row or -1, tiles
+ * (sum b_k^2) the inverses subdomain after subdomain, column-major inside a tile (tiles[off_k + j b_k + i] = Binv_k[i][j]). */
+int32_t kryst_pc_asm_export(kryst_pc_t pc, int64_t* sub_ptr, int32_t* sub_idx, int32_t* owner, double* tiles);
 /* ApproxInv::setup (src/preconditioner/approxinv.rs:123-264) on the device: column j of M minimises || A m_j - e_j ||_2 over the
  * vectors with support J_j; inv_rows[i] = the (j, M_ij) with |M_ij| > tol (strict: 0 and NaN are dropped), ascending j.  The apply is
  * kryst_pc_approx_inverse's (approxinv.rs:268-298); M is owned by the preconditioner.  pattern_kind: KRYST_SPAI_MANUAL

@@ -212,6 +212,28 @@ struct BlockJacobi : DevicePc {
         reset(h, a.context()->handle());
     }
 };
+// AdditiveSchwarz::new(overlap, subdomains) + setup + apply (asm.rs:34-119) with the direct solve as the inner solver (kryst_pc_asm): z = 0,
+// then every subdomain in ascending order adds its product.  Empty `subdomains`: `nparts` uniform parts (the reference's capacity(); 0 gives
+// one part).  The variant selects the labelled extensions: growth by `overlap` layers (Grown) and RAS (Restricted); AsWritten ignores
+// `overlap`, as the reference does.  PC{AdditiveSchwarzKind} keeps throwing KError{Unsupported}; construct AdditiveSchwarz directly.
+struct AdditiveSchwarz : DevicePc {
+    enum Variant { AsWritten = KRYST_ASM_AS_WRITTEN, Grown = KRYST_ASM_GROWN, Restricted = KRYST_ASM_RESTRICTED };
+    AdditiveSchwarz(size_t overlap = 0, std::vector<std::vector<size_t>> subdomains = {}, size_t nparts = 0, Variant variant = AsWritten)
+        : overlap(overlap), subdomains(std::move(subdomains)), nparts(nparts), variant(variant) {}
+    size_t overlap; std::vector<std::vector<size_t>> subdomains; size_t nparts; Variant variant;
+    void setup(const HipCsrMatrix& a) override {
+        kryst_pc_t h = nullptr;
+        const int32_t ov = (int32_t)std::min<size_t>(overlap, INT32_MAX);
+        if (subdomains.empty()) {
+            check(kryst_pc_asm_uniform(a.handle(), (int64_t)nparts, ov, (int32_t)variant, &h));
+        } else {
+            std::vector<int64_t> ptr(1, 0), idx;
+            for (auto& g : subdomains) { for (size_t i : g) idx.push_back((int64_t)i); ptr.push_back((int64_t)idx.size()); }
+            check(kryst_pc_asm(a.handle(), ptr.data(), idx.data(), (int64_t)subdomains.size(), ov, (int32_t)variant, &h));
+        }
+        reset(h, a.context()->handle());
+    }
+};
 // AMG::new(a, max_levels, threshold) (amg.rs:73-118) as written, set up on the host and applied on the device (kryst_pc_amg): one undamped
 // Jacobi sweep before and after the coarse correction, the finest level from the incoming z, CG on the coarsest level.  PC{AMGKind} keeps
 // throwing KError{Unsupported} (the mirror's tests pin that); construct Amg directly.

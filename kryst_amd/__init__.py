@@ -22,7 +22,7 @@ from . import _ffi
 from ._ffi import KError, lib, check
 
 __all__ = ["Context", "DeviceVec", "CsrMatrix", "dot", "norm", "Jacobi", "Ilu0", "Ilup", "Ilut", "TrueIlu0", "Chebyshev",
-           "ChebyshevPc", "IdentityPc", "ApproxInv", "BlockJacobi", "SparsityPattern", "Spai", "Amg", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
+           "ChebyshevPc", "IdentityPc", "ApproxInv", "BlockJacobi", "AdditiveSchwarz", "SparsityPattern", "Spai", "Amg", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
            "Preconditioning", "CgSolver", "PcgSolver", "GmresSolver", "FgmresSolver", "PcaGmresSolver", "Orthog", "CgsSolver", "TfqmrSolver", "MinresSolver", "QmrSolver", "CgnrSolver", "CgneSolver", "BiCgStabSolver", "BiCgStabRightPcSolver", "Session", "KspContext", "SolverKind", "PC", "KError", "reduce_spec",
            "host_stencil7", "partition_rows", "halo_recv_plan", "read_matrix_market", "read_petsc_binary", "host_ilup", "host_ilut", "host_amg", "host_levels"]
 
@@ -635,6 +635,94 @@ class BlockJacobi(_Pc):
         return rp, ci, va
 
 
+class AdditiveSchwarz(_Pc):
+    """AdditiveSchwarz::new(overlap, subdomains) + setup + apply (src/preconditioner/asm.rs:34-119) with the direct solve as the inner
+    solver, as a device preconditioner on the CSR operator: z = 0, then every subdomain in ascending order adds
+    (B^-1 r|_g) into z[g]; rows in no subdomain give +0.0.  `subdomains`: a list of index lists, or a (ptr, idx) tuple of numpy arrays packed
+    like CSR rows; None or empty: `nparts` uniform parts (asm.rs:46-56 with the reference's `capacity()`; None or 0 gives ONE part of all n
+    rows).  As written `overlap` is stored and not used.  Labelled extensions: `.with_overlap()` grows every subdomain by `overlap` layers
+    of the symmetrised graph of A; `.restricted()` grows them and keeps, per row, only the product of the last un-grown subdomain that
+    contains it (RAS: not symmetric, for GMRES, FGMRES and BiCGStab, not PCG).  Labelled deviations, those of BlockJacobi: explicit
+    Gauss-Jordan inverses, sorted index sets, errors (ZeroPivot with `.row`, FactorError, ArgumentError, Unsupported for a subdomain of
+    more than 128 rows before or after growth) where the reference gives non-finite z or panics."""
+    AS_WRITTEN, GROWN, RESTRICTED = 0, 1, 2
+    MAX_ROWS = 128
+
+    def __init__(self, overlap=0, subdomains=None, nparts=None):
+        super().__init__()
+        self.overlap = int(overlap)
+        self.nparts = 0 if nparts is None else int(nparts)
+        self.variant = self.AS_WRITTEN
+        self.ptr = self.idx = None
+        if subdomains is not None and len(subdomains) > 0:
+            if isinstance(subdomains, tuple) and len(subdomains) == 2 and all(isinstance(v, np.ndarray) for v in subdomains):
+                self.ptr = np.ascontiguousarray(subdomains[0], dtype=np.int64)
+                self.idx = np.ascontiguousarray(subdomains[1], dtype=np.int64)
+            else:
+                sets = [np.asarray(g, dtype=np.int64).ravel() for g in subdomains]
+                self.ptr = np.zeros(len(sets) + 1, dtype=np.int64)
+                np.cumsum([len(g) for g in sets], out=self.ptr[1:])
+                self.idx = np.concatenate(sets) if sets else np.zeros(0, dtype=np.int64)
+            if len(self.ptr) < 1 or int(self.ptr[-1]) != len(self.idx):
+                raise KError(102, "AdditiveSchwarz: inconsistent (ptr, idx)")
+
+    def with_overlap(self):
+        """Labelled extension: grow every subdomain by `overlap` layers before it is inverted."""
+        self.variant = self.GROWN
+        return self
+
+    def restricted(self):
+        """Labelled extension: restricted additive Schwarz (grown subdomains, each row from its last un-grown subdomain only)."""
+        self.variant = self.RESTRICTED
+        return self
+
+    @staticmethod
+    def grid_boxes(N, box=(4, 4, 2)):
+        """(ptr, idx) of the boxes of bx x by x bz grid points of the N^3 stencil operators (row = i + N (j + N k)), i fastest, the boxes
+        in the same order; boxes at the far faces are shorter when N is not a multiple of the box."""
+        bx, by, bz = (int(v) for v in box)
+        r = np.arange(N ** 3, dtype=np.int64)
+        i, j, k = r % N, (r // N) % N, r // (N * N)
+        nx, ny = -(-N // bx), -(-N // by)
+        box_of = i // bx + nx * (j // by + ny * (k // bz))
+        idx = np.argsort(box_of, kind="stable")             # natural row order inside a box: i fastest, then j, then k
+        ptr = np.zeros(nx * ny * -(-N // bz) + 1, dtype=np.int64)
+        np.cumsum(np.bincount(box_of, minlength=len(ptr) - 1), out=ptr[1:])
+        return ptr, idx.astype(np.int64)
+
+    def setup(self, a):
+        h = _ffi.Handle()
+        if self.ptr is None:
+            check(lib().kryst_pc_asm_uniform(a.h, self.nparts, self.overlap, self.variant, C.byref(h)))
+        else:
+            check(lib().kryst_pc_asm(a.h, self.ptr.ctypes.data_as(_ffi.c_i64p), self.idx.ctypes.data_as(_ffi.c_i64p), len(self.ptr) - 1,
+                                     self.overlap, self.variant, C.byref(h)))
+        self._set(a.ctx, h)
+        self._a = a
+        return self
+
+    def info(self):
+        """-> dict(nsub, ext_rows = the sum of the (grown) subdomain rows, max_rows)"""
+        if self.h is None:
+            raise KError(2, "preconditioner used before setup")
+        ns, ext, mx = C.c_int64(), C.c_int64(), C.c_int32()
+        check(lib().kryst_pc_asm_info(self.h, C.byref(ns), C.byref(ext), C.byref(mx)))
+        return {"nsub": ns.value, "ext_rows": ext.value, "max_rows": mx.value}
+
+    def export(self):
+        """-> (ptr int64, idx int32, owner int32, tiles float64): the (grown) subdomains sorted ascending, the last un-grown subdomain of
+        every row (-1: none), the inverses subdomain after subdomain, column-major inside a tile (tiles[off_k + j b + i] = Binv_k[i][j])."""
+        inf = self.info()
+        ptr = np.zeros(inf["nsub"] + 1, dtype=np.int64)
+        check(lib().kryst_pc_asm_export(self.h, ptr.ctypes.data_as(_ffi.c_i64p), None, None, None))
+        b = np.diff(ptr)
+        idx = np.zeros(inf["ext_rows"], dtype=np.int32)
+        owner = np.zeros(self._a.nrows(), dtype=np.int32)
+        tiles = np.zeros(int((b * b).sum()), dtype=np.float64)
+        check(lib().kryst_pc_asm_export(self.h, None, idx.ctypes.data_as(_ffi.c_i32p), owner.ctypes.data_as(_ffi.c_i32p), _dp(tiles)))
+        return ptr, idx, owner, tiles
+
+
 class SparsityPattern:
     """SparsityPattern (src/preconditioner/mod.rs) for the SPAI set-up.  `SparsityPattern.Manual(pat)`: pat[j] lists the rows of column j
     of M (n = len(pat)); a list of index lists, or a (ptr, idx) tuple of numpy arrays packed like CSR rows.  `SparsityPattern.Auto`: as
@@ -1066,8 +1154,9 @@ class PC:
     """PC<T> (src/context/pc_context.rs:36-76): the reference's configuration enum for preconditioners, plus the constructor it
     lacks -- `PC.Ilut(fill=10, droptol=1e-3).build(a)` returns the set-up device preconditioner.  PC::AMG carries no parameters in
     the reference; `PC.AMG()` builds Amg(max_levels=10, threshold=0.1), the as-written hierarchy (a bare `PC("AMG")` without them
-    still raises KError(Unsupported), as it did before AMG existed).  Kinds outside the hot path (Ssor, Multicolor, AdditiveSchwarz)
-    raise KError(Unsupported)."""
+    still raises KError(Unsupported), as it did before AMG existed).  `PC.AdditiveSchwarz(overlap=0, subdomains=None, nparts=None)`
+    builds AdditiveSchwarz as written; a bare `PC("AdditiveSchwarz")` without its parameters keeps raising KError(Unsupported), following
+    AMG.  Kinds outside the hot path (Ssor, Multicolor) raise KError(Unsupported)."""
 
     def __init__(self, kind, **params):
         self.kind, self.params = kind, params
@@ -1107,6 +1196,10 @@ class PC:
     def AMG(max_levels=10, threshold=0.1):            # pc_context.rs:72 AMG (no parameters there: these are the defaults)
         return PC("AMG", max_levels=max_levels, threshold=threshold)
 
+    @staticmethod
+    def AdditiveSchwarz(overlap=0, subdomains=None, nparts=None):   # pc_context.rs:75 AdditiveSchwarz (no parameters there); asm.rs:34 new(overlap, subdomains)
+        return PC("AdditiveSchwarz", overlap=overlap, subdomains=subdomains, nparts=nparts)
+
     def build(self, a):
         k, q = self.kind, self.params
         if k == "Jacobi":
@@ -1125,6 +1218,8 @@ class PC:
             return Spai(q["pattern"], q["tol"], q["max_iter"]).setup(a)
         if k == "AMG" and "max_levels" in q:          # PC.AMG(...); the bare PC("AMG") keeps raising Unsupported, as before
             return Amg(q["max_levels"], q["threshold"]).setup(a)
+        if k == "AdditiveSchwarz" and "overlap" in q:  # PC.AdditiveSchwarz(...); the bare PC("AdditiveSchwarz") keeps raising Unsupported
+            return AdditiveSchwarz(q["overlap"], q["subdomains"], q["nparts"]).setup(a)
         raise KError(6, f"preconditioner kind {k} is outside the accelerated path")
 
 

@@ -100,6 +100,10 @@ SIGNATURES = {
     "kryst_pc_block_jacobi": (C.c_int32, [Handle, c_i64p, c_i64p, C.c_int64, C.POINTER(Handle)]),
     "kryst_pc_block_jacobi_uniform": (C.c_int32, [Handle, C.c_int32, C.POINTER(Handle)]),
     "kryst_pc_block_jacobi_export": (C.c_int32, [Handle, c_i64p, c_i64p, c_i32p, c_dp]),
+    "kryst_pc_asm": (C.c_int32, [Handle, c_i64p, c_i64p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(Handle)]),
+    "kryst_pc_asm_uniform": (C.c_int32, [Handle, C.c_int64, C.c_int32, C.c_int32, C.POINTER(Handle)]),
+    "kryst_pc_asm_info": (C.c_int32, [Handle, c_i64p, c_i64p, c_i32p]),
+    "kryst_pc_asm_export": (C.c_int32, [Handle, c_i64p, c_i32p, c_i32p, c_dp]),
     "kryst_pc_spai": (C.c_int32, [Handle, C.c_int32, c_i64p, c_i64p, C.c_int64, C.c_double, C.POINTER(Handle)]),
     "kryst_pc_spai_export": (C.c_int32, [Handle, c_i64p, c_i64p, c_i32p, c_dp]),
     "kryst_pc_amg": (C.c_int32, [Handle, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Handle)]),

@@ -163,6 +163,7 @@ int32_t ensure_partials(kryst_ctx_t ctx, int64_t ntiles);
 hipError_t pool_malloc_bytes(void** p, size_t bytes);
 hipError_t pool_free(void* p);
 size_t pool_trim(int device);                         // -> bytes returned to the driver
+size_t pool_pooled(int device);                       // bytes the pool holds now (hipMemGetInfo counts them as used)
 template <class T> inline hipError_t pool_malloc(T** p, size_t bytes) { return pool_malloc_bytes(reinterpret_cast<void**>(p), bytes); }
 void phase_mark_slow(kryst_ctx_t ctx, int phase);                       // ctx.cpp
 inline void phase_mark(kryst_ctx_t ctx, int phase) { if (ctx->phase) phase_mark_slow(ctx, phase); }

@@ -82,6 +82,11 @@ hipError_t pool_free(void* p) {
     P->free_blocks.emplace(bytes, p); P->pooled += bytes;
     return hipSuccess;
 }
+size_t pool_pooled(int device) {
+    DevPool* P = &g_pools[device & 63];
+    std::lock_guard<std::mutex> g(P->mu);
+    return P->pooled;
+}
 size_t pool_trim(int device) {
     DevPool* P = &g_pools[device & 63];
     std::multimap<size_t, void*> blocks;

@@ -2,7 +2,7 @@
 #pragma once
 #include "csr.h"
 
-enum { KR_PC_IDENTITY = 1, KR_PC_JACOBI = 2, KR_PC_ILU = 3, KR_PC_CHEB_STUB = 6, KR_PC_CHEB = 7, KR_PC_SPAI = 9, KR_PC_BLOCK_JACOBI = 10, KR_PC_AMG = 11 };
+enum { KR_PC_IDENTITY = 1, KR_PC_JACOBI = 2, KR_PC_ILU = 3, KR_PC_CHEB_STUB = 6, KR_PC_CHEB = 7, KR_PC_SPAI = 9, KR_PC_BLOCK_JACOBI = 10, KR_PC_AMG = 11, KR_PC_ASM = 12 };
 
 namespace kr { struct AmgDev; }
 
@@ -35,6 +35,16 @@ struct kryst_pc_s {
     int32_t* d_bj_owner = nullptr;    // index-set form with overlapping blocks or uncovered rows: the last block containing a row, or -1
     std::vector<int64_t> bj_ptr_h; std::vector<int32_t> bj_idx_h;
     kr::AmgDev* amg = nullptr;        // AMG (amg.hip): the levels, their operators and work vectors
+    // additive Schwarz (asm.hip): the (grown) subdomains sorted ascending, their tiles block after block (column-major inside a tile), the
+    // products X of an apply (one entry per subdomain row) and the row -> positions-in-X map of the combine
+    int64_t asm_nsub = 0, asm_total = 0;   // subdomains; sum of their rows
+    int32_t asm_maxb = 0;
+    double* d_asm_tile = nullptr; int64_t* d_asm_toff = nullptr; double* d_asm_x = nullptr;
+    int32_t* d_asm_xoff = nullptr;    // subdomain k's rows: positions [xoff[k], xoff[k + 1]) of d_asm_idx / X
+    int32_t* d_asm_posk = nullptr;    // the subdomain of every position
+    int32_t* d_asm_idx = nullptr;
+    int32_t* d_asm_mptr = nullptr; int32_t* d_asm_mpos = nullptr;
+    std::vector<int64_t> asm_ptr_h; std::vector<int32_t> asm_idx_h, asm_owner_h;   // owner: the last un-grown set containing a row, or -1
 };
 
 namespace kr {
@@ -48,6 +58,8 @@ bool pc_fell_back(kryst_pc_t pc);
 int32_t bj_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done);   // block_jacobi.hip
 void bj_free(kryst_pc_t pc);
 int32_t amg_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done);   // amg.hip
+int32_t asm_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done);   // asm.hip
+void asm_free(kryst_pc_t pc);
 // whether the apply reads z on entry (AMG as written starts its finest level from the incoming z, amg.rs:211)
 bool pc_reads_z(kryst_pc_t pc);
 // pc_apply_dev for solvers whose reference apply gets a FRESH z: z = 0 (init == nullptr; gmres.rs:244, 250, 256, 283, 311, 339) or

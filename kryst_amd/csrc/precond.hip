@@ -133,6 +133,7 @@ static int32_t pc_apply_kind(kryst_pc_t pc, const double* r, double* z, const in
         case KR_PC_SPAI:      // ApproxInv::apply (approxinv.rs:268-298): z_i = sum_j M_ij r_j, ascending j from 0 -- an SpMV with M
             return launch_spmv(pc->a, r, z, 0, nullptr, done);
         case KR_PC_BLOCK_JACOBI: return bj_apply_dev(pc, r, z, done);
+        case KR_PC_ASM: return asm_apply_dev(pc, r, z, done);
         case KR_PC_AMG: return amg_apply_dev(pc, r, z, done);
         default: set_error("unknown preconditioner kind %d", pc->kind); return KRYST_UNSUPPORTED;
     }
@@ -264,6 +265,7 @@ int32_t kryst_pc_destroy(kryst_pc_t pc) {
     (void)hipFree(pc->d_inv_diag); (void)hipFree(pc->d_v0); (void)hipFree(pc->d_v1); (void)hipFree(pc->d_v2);
     ilu_free(pc);
     bj_free(pc);
+    asm_free(pc);
     amg_free(pc);
     if (pc->spai_m) kryst_csr_destroy(pc->spai_m);
     delete pc;
