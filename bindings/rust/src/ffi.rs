@@ -140,6 +140,9 @@ extern "C" {
     pub fn kryst_pc_asm_uniform(a: Csr, nparts: i64, overlap: i32, variant: i32, out: *mut Pc) -> i32;
     pub fn kryst_pc_asm_info(pc: Pc, nsub: *mut i64, ext_rows: *mut i64, max_rows: *mut i32) -> i32;
     pub fn kryst_pc_asm_export(pc: Pc, sub_ptr: *mut i64, sub_idx: *mut i32, owner: *mut i32, tiles: *mut f64) -> i32;
+    pub fn kryst_pc_sor(a: Csr, omega: f64, its: i64, lits: i64, sym_bits: u32, fshift: f64, colors: *const i32, out: *mut Pc) -> i32;
+    pub fn kryst_pc_sor_info(pc: Pc, groups_forward: *mut i32, groups_backward: *mut i32, rows: *mut i64, grid_forward: *mut i32, grid_backward: *mut i32) -> i32;
+    pub fn kryst_host_color_graph(n: i64, ptr: *const i64, col: *const i32, colors: *mut i32, ncolors: *mut i32) -> i32;
     pub fn kryst_pc_spai(a: Csr, pattern_kind: i32, pat_ptr: *const i64, pat_idx: *const i64, pat_n: i64, tol: f64, out: *mut Pc) -> i32;
     pub fn kryst_pc_spai_export(pc: Pc, nnz: *mut i64, row_ptr: *mut i64, col: *mut i32, val: *mut f64) -> i32;
     pub fn kryst_pc_amg(a: Csr, max_levels: i32, threshold: f64, variant: i32, nu_pre: i32, nu_post: i32, out: *mut Pc) -> i32;

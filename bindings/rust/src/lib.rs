@@ -363,6 +363,40 @@ impl HipAdditiveSchwarz {
     pub fn new(overlap: usize, subdomains: Vec<Vec<usize>>) -> Self { Self::empty(overlap, subdomains, 0, ffi::KRYST_ASM_AS_WRITTEN) }
 }
 
+/// `MatSorType` (src/preconditioner/sor.rs:32-44): the reference's bit values.
+#[allow(non_snake_case)]
+pub mod MatSorType {
+    pub const ZERO_INITIAL_GUESS: u32 = 0b000_00001;
+    pub const APPLY_LOWER: u32 = 0b000_00010;
+    pub const APPLY_UPPER: u32 = 0b000_00100;
+    pub const SYMMETRIC_SWEEP: u32 = APPLY_LOWER | APPLY_UPPER;
+    pub const LOCAL_FORWARD_SWEEP: u32 = 0b000_01000;
+    pub const LOCAL_BACKWARD_SWEEP: u32 = 0b000_10000;
+    pub const LOCAL_SYMMETRIC_SWEEP: u32 = LOCAL_FORWARD_SWEEP | LOCAL_BACKWARD_SWEEP;
+    pub const EISENSTAT: u32 = 0b0010_0000;
+}
+
+device_pc! {
+    /// `Sor::new(omega, its, lits, sym, fshift)` + `setup` + `apply` (src/preconditioner/sor.rs:71-170) as a device `Preconditioner`
+    /// (include/kryst_hip.h, kryst_pc_sor): the sweeps exactly as written, `lits` and the `LOCAL_*` bits stored and not used.  `colors`
+    /// (labelled extension; `PC::Multicolor` has no implementation in the reference): empty, or one colour per row -- the same sweeps in
+    /// the order (colour, row).  Unverified source like the rest of this crate (never compiled).
+    HipSor { omega: f64 = 1.0, its: usize = 1, lits: usize = 1, sym: u32 = MatSorType::SYMMETRIC_SWEEP, fshift: f64 = 0.0, colors: Vec<usize> = Vec::new() } setup(s, a, out) {
+        // the C entry point reads one colour per row and cannot know the slice's length: a wrong length or a colour past i32 is the
+        // argument error here (an empty vector: the order as written)
+        if !s.colors.is_empty() && (s.colors.len() != a.nrows || s.colors.iter().any(|&v| v > i32::MAX as usize)) {
+            ffi::KRYST_ERR_ARG
+        } else {
+            let c: Vec<i32> = s.colors.iter().map(|&v| v as i32).collect();
+            ffi::kryst_pc_sor(a.h, s.omega, s.its as i64, s.lits as i64, s.sym, s.fshift, if c.is_empty() { std::ptr::null() } else { c.as_ptr() }, &mut out)
+        }
+    }
+}
+impl HipSor {
+    pub fn new(omega: f64, its: usize, lits: usize, sym: u32, fshift: f64) -> Self { Self::empty(omega, its, lits, sym, fshift, Vec::new()) }
+    pub fn with_colors(mut self, colors: Vec<usize>) -> Self { self.colors = colors; self }
+}
+
 /// `SparsityPattern` (src/preconditioner/mod.rs) for the SPAI set-up: `Manual(pat)` (pat[j] = the rows of column j of M), `Auto` (as
 /// written: `Err(Unsupported)`, approxinv.rs:127-133), `Operator` (extension: the stored columns of row j of A).
 #[derive(Clone, Debug, Default)]

@@ -259,6 +259,25 @@ int32_t kryst_pc_asm_info(kryst_pc_t pc, int64_t* nsub, int64_t* ext_rows, int32
  * sub_idx (ext_rows) the grown subdomains sorted ascending, owner (n) the last un-grown subdomain that contains each row or -1, tiles
  * (sum b_k^2) the inverses subdomain after subdomain, column-major inside a tile (tiles[off_k + j b_k + i] = Binv_k[i][j]). */
 int32_t kryst_pc_asm_export(kryst_pc_t pc, int64_t* sub_ptr, int32_t* sub_idx, int32_t* owner, double* tiles);
+
+/* Sor::new(omega, its, lits, sym, fshift) + setup + apply (src/preconditioner/sor.rs:71-170) as a device preconditioner on the CSR operator
+ * (DESIGN.md section 4.11).  sym_bits: the MatSorType bits below.  Set-up: inv_diag[i] = 1 / (a_ii + fshift), a row without a stored
+ * diagonal counts as a_ii = 0; a sum of exactly zero is KRYST_ZERO_PIVOT with the lowest such row in kryst_hip_last_error_row().  apply:
+ * y = +0.0, then `its` times the forward sweep (APPLY_LOWER) and / or the backward sweep (APPLY_UPPER) exactly as written, every operation
+ * rounded on its own; `lits` and the ZERO_INITIAL_GUESS / LOCAL_* bits are stored and not used, as written.  The input and the output of an
+ * apply must be different vectors.  `colors` (labelled extension, the reference's PC::Multicolor has no implementation): NULL, or one
+ * non-negative colour per row; the sweeps then visit the rows by (colour, row) ascending (forward) and in the exact reverse (backward), "before"
+ * and "after" mean positions in that order and the terms of a group are summed in ascending position: the loops as written on P A P^T
+ * with P x, un-permuted.  Either way one persistent launch per sweep walks the dependency levels of the (permuted) pattern with a grid barrier between
+ * them.  Errors: KRYST_ERR_ARG (non-square operator, negative its / lits / colour, unknown bits), KRYST_UNSUPPORTED (distributed operator),
+ * KRYST_ZERO_PIVOT; also KRYST_UNSUPPORTED when levels x workgroups of a sweep reach 2^32.  kryst_pc_apply, kryst_bench_pc_apply, kryst_pc_destroy and every solver take the result. */
+enum { KRYST_SOR_ZERO_INITIAL_GUESS = 1, KRYST_SOR_APPLY_LOWER = 2, KRYST_SOR_APPLY_UPPER = 4, KRYST_SOR_SYMMETRIC_SWEEP = 6,
+       KRYST_SOR_LOCAL_FORWARD_SWEEP = 8, KRYST_SOR_LOCAL_BACKWARD_SWEEP = 16, KRYST_SOR_LOCAL_SYMMETRIC_SWEEP = 24, KRYST_SOR_EISENSTAT = 32 };
+int32_t kryst_pc_sor(kryst_csr_t a, double omega, int64_t its, int64_t lits, uint32_t sym_bits, double fshift, const int32_t* colors, kryst_pc_t* out);
+/* dependency levels (= grid-barrier separated passes) of the forward / backward sweep (0 for a sweep sym_bits does not ask for), rows, and the
+ * workgroups (of 1024 threads) a forward / backward sweep launches: min(CUs, ceil(widest level / 1024)); any pointer may be NULL */
+int32_t kryst_pc_sor_info(kryst_pc_t pc, int32_t* groups_forward, int32_t* groups_backward, int64_t* rows, int32_t* grid_forward,
+                          int32_t* grid_backward);
 /* ApproxInv::setup (src/preconditioner/approxinv.rs:123-264) on the device: column j of M minimises || A m_j - e_j ||_2 over the
  * vectors with support J_j; inv_rows[i] = the (j, M_ij) with |M_ij| > tol (strict: 0 and NaN are dropped), ascending j.  The apply is
  * kryst_pc_approx_inverse's (approxinv.rs:268-298); M is owned by the preconditioner.  pattern_kind: KRYST_SPAI_MANUAL
@@ -455,6 +474,10 @@ int32_t kryst_host_factors_destroy(kryst_host_factors_t f);
  * level[i] = 1 + the highest level among the rows that row i of a strictly-lower (forward != 0: rows ascending) or strictly-upper (rows
  * descending) factor depends on, 0 when it depends on none.  *nlevels (may be NULL): the number of levels. */
 int32_t kryst_host_levels(int64_t n, const int64_t* ptr, const int32_t* col, int32_t forward, int32_t* level, int32_t* nlevels);
+/* color_graph (src/utils/coloring.rs:7-64) on the stored pattern (ptr, col) of an n x n matrix, host only: adjacency symmetrised without the
+ * diagonal, distance-2 neighbourhoods, rows in ascending order take the lowest colour their neighbourhood does not hold yet.
+ * colors: n entries; *ncolors (may be NULL): the number of colours. */
+int32_t kryst_host_color_graph(int64_t n, const int64_t* ptr, const int32_t* col, int32_t* colors, int32_t* ncolors);
 
 /* AMG::new(a, max_levels, threshold) (src/preconditioner/amg.rs:73-118) as written, on host rows (strictly ascending columns, n x n): the
  * code kryst_pc_amg runs before the upload (kryst_amd/csrc/amg_setup.cpp).  level_budget: the most entries P_l, R*A and A_{l+1} of one level

@@ -234,6 +234,38 @@ struct AdditiveSchwarz : DevicePc {
         reset(h, a.context()->handle());
     }
 };
+// MatSorType (sor.rs:32-44), the reference's bit values, and Sor::new(omega, its, lits, sym, fshift) + setup + apply (sor.rs:71-170) as a
+// device preconditioner (kryst_pc_sor): the sweeps exactly as written; `lits` and the LOCAL_* bits are stored and not used.  The parameters
+// are read by setup().  `colors` (labelled extension; PC::Multicolor has no implementation in the reference): non-empty, one colour per
+// row -- the same sweeps in the order (colour, row).  PC{SsorKind} / PC{MulticolorKind} keep throwing KError{Unsupported}; construct Sor.
+namespace MatSorType {
+enum : uint32_t { ZERO_INITIAL_GUESS = KRYST_SOR_ZERO_INITIAL_GUESS, APPLY_LOWER = KRYST_SOR_APPLY_LOWER, APPLY_UPPER = KRYST_SOR_APPLY_UPPER,
+                  SYMMETRIC_SWEEP = KRYST_SOR_SYMMETRIC_SWEEP, LOCAL_FORWARD_SWEEP = KRYST_SOR_LOCAL_FORWARD_SWEEP,
+                  LOCAL_BACKWARD_SWEEP = KRYST_SOR_LOCAL_BACKWARD_SWEEP, LOCAL_SYMMETRIC_SWEEP = KRYST_SOR_LOCAL_SYMMETRIC_SWEEP,
+                  EISENSTAT = KRYST_SOR_EISENSTAT };
+}
+struct Sor : DevicePc {
+    Sor(double omega, size_t its, size_t lits, uint32_t sym, double fshift) : omega_(omega), its_(its), lits_(lits), sym_(sym), fshift_(fshift) {}
+    void set_omega(double v) { omega_ = v; }   double omega() const { return omega_; }
+    void set_its(size_t v) { its_ = v; }       size_t its() const { return its_; }
+    void set_lits(size_t v) { lits_ = v; }     size_t lits() const { return lits_; }
+    void set_sym(uint32_t v) { sym_ = v; }     uint32_t sym() const { return sym_; }
+    void set_fshift(double v) { fshift_ = v; } double fshift() const { return fshift_; }
+    Sor& with_colors(std::vector<size_t> c) { colors = std::move(c); return *this; }
+    std::vector<size_t> colors;
+    void setup(const HipCsrMatrix& a) override {
+        kryst_pc_t h = nullptr;
+        std::vector<int32_t> c;
+        if (!colors.empty()) {
+            if (colors.size() != a.nrows()) throw KError(KRYST_ERR_ARG);
+            for (size_t v : colors) { if (v > (size_t)INT32_MAX) throw KError(KRYST_ERR_ARG); c.push_back((int32_t)v); }
+        }
+        check(kryst_pc_sor(a.handle(), omega_, (int64_t)its_, (int64_t)lits_, sym_, fshift_, c.empty() ? nullptr : c.data(), &h));
+        reset(h, a.context()->handle());
+    }
+private:
+    double omega_; size_t its_, lits_; uint32_t sym_; double fshift_;
+};
 // AMG::new(a, max_levels, threshold) (amg.rs:73-118) as written, set up on the host and applied on the device (kryst_pc_amg): one undamped
 // Jacobi sweep before and after the coarse correction, the finest level from the incoming z, CG on the coarsest level.  PC{AMGKind} keeps
 // throwing KError{Unsupported} (the mirror's tests pin that); construct Amg directly.
@@ -477,7 +509,7 @@ protected:
 
 // ---- context/: PC<T> (src/context/pc_context.rs:36-76) and KspContext (src/context/ksp_context.rs:25-148) ---------------------
 // PC<T>: the reference's configuration enum for preconditioners, plus the constructor it lacks -- build(a) returns the set-up
-// device preconditioner.  Kinds outside the hot path (Ssor, Multicolor, AMG, AdditiveSchwarz) throw
+// device preconditioner.  Kinds without parameters here (Ssor, Multicolor, AMG, AdditiveSchwarz: construct Sor, Amg, AdditiveSchwarz) throw
 // KError{Unsupported}.
 struct PC {
     enum Kind { JacobiKind, SsorKind, Ilu0Kind, IlupKind, IlutKind, ChebyshevKind, ApproxInvKind, BlockJacobiKind, MulticolorKind, AMGKind, AdditiveSchwarzKind };

@@ -22,9 +22,9 @@ from . import _ffi
 from ._ffi import KError, lib, check
 
 __all__ = ["Context", "DeviceVec", "CsrMatrix", "dot", "norm", "Jacobi", "Ilu0", "Ilup", "Ilut", "TrueIlu0", "Chebyshev",
-           "ChebyshevPc", "IdentityPc", "ApproxInv", "BlockJacobi", "AdditiveSchwarz", "SparsityPattern", "Spai", "Amg", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
+           "ChebyshevPc", "IdentityPc", "ApproxInv", "BlockJacobi", "AdditiveSchwarz", "Sor", "MatSorType", "SparsityPattern", "Spai", "Amg", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
            "Preconditioning", "CgSolver", "PcgSolver", "GmresSolver", "FgmresSolver", "PcaGmresSolver", "Orthog", "CgsSolver", "TfqmrSolver", "MinresSolver", "QmrSolver", "CgnrSolver", "CgneSolver", "BiCgStabSolver", "BiCgStabRightPcSolver", "Session", "KspContext", "SolverKind", "PC", "KError", "reduce_spec",
-           "host_stencil7", "partition_rows", "halo_recv_plan", "read_matrix_market", "read_petsc_binary", "host_ilup", "host_ilut", "host_amg", "host_levels"]
+           "host_stencil7", "partition_rows", "halo_recv_plan", "read_matrix_market", "read_petsc_binary", "host_ilup", "host_ilut", "host_amg", "host_levels", "color_graph", "build_blocks_from_colors"]
 
 
 def _dp(a):
@@ -723,6 +723,118 @@ class AdditiveSchwarz(_Pc):
         return ptr, idx, owner, tiles
 
 
+class MatSorType(enum.IntFlag):
+    """MatSorType (src/preconditioner/sor.rs:32-44), the reference's bit values."""
+    ZERO_INITIAL_GUESS = 0b000_00001
+    APPLY_LOWER = 0b000_00010                     # forward Gauss-Seidel
+    APPLY_UPPER = 0b000_00100                     # backward
+    SYMMETRIC_SWEEP = APPLY_LOWER | APPLY_UPPER
+    LOCAL_FORWARD_SWEEP = 0b000_01000
+    LOCAL_BACKWARD_SWEEP = 0b000_10000
+    LOCAL_SYMMETRIC_SWEEP = LOCAL_FORWARD_SWEEP | LOCAL_BACKWARD_SWEEP
+    EISENSTAT = 0b0010_0000
+
+
+def _rust_float(v):
+    """`{}` of an f64 in Rust: the shortest digits that round-trip, no exponent, no trailing ".0" """
+    v = float(v)
+    if v != v or v in (float("inf"), float("-inf")):
+        return "NaN" if v != v else ("inf" if v > 0 else "-inf")
+    t = repr(v)
+    if "e" in t or "E" in t:
+        t = np.format_float_positional(v, unique=True, trim="-")
+    return t[:-2] if t.endswith(".0") else t
+
+
+class Sor(_Pc):
+    """Sor::new(omega, its, lits, sym, fshift) + setup + apply (src/preconditioner/sor.rs:71-170) as a device preconditioner on the CSR
+    operator: inv_diag = 1 / (a_ii + fshift) (ZeroPivot with `.row` where that sum is zero); apply: y = +0.0, then
+    `its` times the forward sweep (APPLY_LOWER; no omega in it) and / or the backward sweep (APPLY_UPPER) exactly as written.  `lits` and the
+    LOCAL_* / ZERO_INITIAL_GUESS bits are stored and not used, as in the reference.  The parameters are read by setup(): a setter called
+    later takes effect at the next setup.  Labelled extension: `.with_colors(colors)` runs the same sweeps in the order (colors[i], i)
+    (multicolour Gauss-Seidel; PC::Multicolor has no implementation in the reference)."""
+
+    def __init__(self, omega, its, lits, sym, fshift):
+        super().__init__()
+        self._omega, self._its, self._lits, self._sym, self._fshift = float(omega), int(its), int(lits), MatSorType(int(sym)), float(fshift)
+        self.colors = None
+
+    def set_omega(self, omega): self._omega = float(omega)
+    def omega(self): return self._omega
+    def set_its(self, its): self._its = int(its)
+    def its(self): return self._its
+    def set_lits(self, lits): self._lits = int(lits)
+    def lits(self): return self._lits
+    def set_sym(self, sym): self._sym = MatSorType(int(sym))
+    def sym(self): return self._sym
+    def set_fshift(self, fshift): self._fshift = float(fshift)
+    def fshift(self): return self._fshift
+
+    def __str__(self):                            # sor.rs:91-94; {:?} of a bitflags value: MatSorType(A | B)
+        names = [m.name for m in (MatSorType.ZERO_INITIAL_GUESS, MatSorType.APPLY_LOWER, MatSorType.APPLY_UPPER, MatSorType.LOCAL_FORWARD_SWEEP,
+                                  MatSorType.LOCAL_BACKWARD_SWEEP, MatSorType.EISENSTAT) if self._sym & m]
+        return (f"SOR(omega={_rust_float(self._omega)}, its={self._its}, lits={self._lits}, sym=MatSorType({' | '.join(names) or '0x0'}), "
+                f"fshift={_rust_float(self._fshift)})")
+
+    def with_colors(self, colors):
+        """Labelled extension: sweep in the order (colors[i], i) ascending (forward) and its exact reverse (backward)."""
+        self.colors = None if colors is None else np.ascontiguousarray(np.asarray(colors).ravel(), dtype=np.int64)
+        return self
+
+    def setup(self, a):
+        c = None
+        if self.colors is not None:
+            if len(self.colors) != a.nrows():
+                raise KError(102, f"Sor: {len(self.colors)} colours for {a.nrows()} rows")
+            if len(self.colors) and (self.colors.min() < 0 or self.colors.max() >= 2 ** 31):
+                raise KError(102, "Sor: a colour is negative or does not fit 31 bits")
+            c = np.ascontiguousarray(self.colors, dtype=np.int32)
+        if self._its < 0 or self._lits < 0:
+            raise KError(102, "Sor: its and lits are counts")
+        h = _ffi.Handle()
+        check(lib().kryst_pc_sor(a.h, self._omega, self._its, self._lits, int(self._sym), self._fshift,
+                                 c.ctypes.data_as(_ffi.c_i32p) if c is not None else None, C.byref(h)))
+        self._set(a.ctx, h)
+        self._a = a
+        return self
+
+    def info(self):
+        """-> dict(passes_forward, passes_backward: the dependency levels a sweep walks, one grid barrier between two; rows;
+        workgroups_forward, workgroups_backward: the 1024-thread workgroups a sweep launches)"""
+        if self.h is None:
+            raise KError(2, "preconditioner used before setup")
+        gf, gb, n, wf, wb = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32(), C.c_int32()
+        check(lib().kryst_pc_sor_info(self.h, C.byref(gf), C.byref(gb), C.byref(n), C.byref(wf), C.byref(wb)))
+        return {"passes_forward": gf.value, "passes_backward": gb.value, "rows": n.value, "workgroups_forward": wf.value,
+                "workgroups_backward": wb.value}
+
+
+def color_graph(a):
+    """color_graph (src/utils/coloring.rs:57-64) on the stored pattern, on the host (kryst_host_color_graph; no device call): `a` is a
+    CsrMatrix (its pattern is downloaded), a (row_ptr, col_idx) pair, or anything with .row_ptr and .col_idx.  -> colors, int64[n]."""
+    if isinstance(a, CsrMatrix):
+        rp, ci, _ = a.download()
+    elif isinstance(a, tuple):
+        rp, ci = a
+    else:
+        rp, ci = a.row_ptr, a.col_idx
+    rp = np.ascontiguousarray(rp, dtype=np.int64)
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    n = len(rp) - 1
+    colors = np.zeros(max(n, 1), dtype=np.int32)
+    check(lib().kryst_host_color_graph(n, rp.ctypes.data_as(_ffi.c_i64p), ci.ctypes.data_as(_ffi.c_i32p), colors.ctypes.data_as(_ffi.c_i32p), None))
+    return colors[:n].astype(np.int64)
+
+
+def build_blocks_from_colors(colors):
+    """build_blocks_from_colors (src/utils/coloring.rs:67-74): blocks[c] = the rows of colour c, ascending."""
+    colors = np.asarray(colors, dtype=np.int64)
+    blocks = [[] for _ in range(int(colors.max()) + 1 if len(colors) else 0)]
+    for i, c in enumerate(colors):
+        blocks[int(c)].append(i)
+    return blocks
+
+
 class SparsityPattern:
     """SparsityPattern (src/preconditioner/mod.rs) for the SPAI set-up.  `SparsityPattern.Manual(pat)`: pat[j] lists the rows of column j
     of M (n = len(pat)); a list of index lists, or a (ptr, idx) tuple of numpy arrays packed like CSR rows.  `SparsityPattern.Auto`: as
@@ -1156,7 +1268,8 @@ class PC:
     the reference; `PC.AMG()` builds Amg(max_levels=10, threshold=0.1), the as-written hierarchy (a bare `PC("AMG")` without them
     still raises KError(Unsupported), as it did before AMG existed).  `PC.AdditiveSchwarz(overlap=0, subdomains=None, nparts=None)`
     builds AdditiveSchwarz as written; a bare `PC("AdditiveSchwarz")` without its parameters keeps raising KError(Unsupported), following
-    AMG.  Kinds outside the hot path (Ssor, Multicolor) raise KError(Unsupported)."""
+    AMG.  `PC.Ssor(omega=1.0, its=1)` builds Sor(omega, its, 1, SYMMETRIC_SWEEP, 0.0) and `PC.Multicolor(colors)` the same sweeps in the
+    coloured order (labelled extension); the bare `PC("Ssor")` / `PC("Multicolor")` keep raising KError(Unsupported), following AMG."""
 
     def __init__(self, kind, **params):
         self.kind, self.params = kind, params
@@ -1200,6 +1313,14 @@ class PC:
     def AdditiveSchwarz(overlap=0, subdomains=None, nparts=None):   # pc_context.rs:75 AdditiveSchwarz (no parameters there); asm.rs:34 new(overlap, subdomains)
         return PC("AdditiveSchwarz", overlap=overlap, subdomains=subdomains, nparts=nparts)
 
+    @staticmethod
+    def Ssor(omega=1.0, its=1):                      # pc_context.rs:45 Ssor (no parameters there)
+        return PC("Ssor", omega=omega, its=its)
+
+    @staticmethod
+    def Multicolor(colors, omega=1.0, its=1):        # pc_context.rs:70 Multicolor { colors }
+        return PC("Multicolor", colors=colors, omega=omega, its=its)
+
     def build(self, a):
         k, q = self.kind, self.params
         if k == "Jacobi":
@@ -1220,6 +1341,10 @@ class PC:
             return Amg(q["max_levels"], q["threshold"]).setup(a)
         if k == "AdditiveSchwarz" and "overlap" in q:  # PC.AdditiveSchwarz(...); the bare PC("AdditiveSchwarz") keeps raising Unsupported
             return AdditiveSchwarz(q["overlap"], q["subdomains"], q["nparts"]).setup(a)
+        if k == "Ssor" and "omega" in q:              # PC.Ssor(...); the bare PC("Ssor") keeps raising Unsupported
+            return Sor(q["omega"], q["its"], 1, MatSorType.SYMMETRIC_SWEEP, 0.0).setup(a)
+        if k == "Multicolor" and "omega" in q:        # PC.Multicolor(colors); the bare PC("Multicolor") keeps raising Unsupported
+            return Sor(q["omega"], q["its"], 1, MatSorType.SYMMETRIC_SWEEP, 0.0).with_colors(q["colors"]).setup(a)
         raise KError(6, f"preconditioner kind {k} is outside the accelerated path")
 
 

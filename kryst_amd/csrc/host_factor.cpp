@@ -322,4 +322,47 @@ int32_t host_levels(int64_t n, const int64_t* ptr, const int32_t* col, bool forw
     return nl;
 }
 
+// ---- distance-2 greedy colouring (utils/coloring.rs:7-64)
+int32_t host_color_graph(int64_t n, const int64_t* ptr, const int32_t* col, int32_t* colors) {
+    // the symmetrised adjacency as CSR: the stored (i, j) and (j, i), i != j, sorted, each once
+    std::vector<int64_t> ap((size_t)n + 1, 0);
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t k = ptr[i]; k < ptr[i + 1]; ++k)
+            if (col[k] != i) { ++ap[(size_t)i + 1]; ++ap[(size_t)col[k] + 1]; }
+    for (int64_t i = 0; i < n; ++i) ap[(size_t)i + 1] += ap[(size_t)i];
+    std::vector<int32_t> ac((size_t)ap[(size_t)n]);
+    {
+        std::vector<int64_t> fill(ap.begin(), ap.end() - 1);
+        for (int64_t i = 0; i < n; ++i)
+            for (int64_t k = ptr[i]; k < ptr[i + 1]; ++k)
+                if (col[k] != i) { ac[(size_t)fill[(size_t)i]++] = col[k]; ac[(size_t)fill[(size_t)col[k]]++] = (int32_t)i; }
+    }
+    std::vector<int64_t> ae((size_t)n);                                  // end of row i's distinct entries
+    for (int64_t i = 0; i < n; ++i) {
+        auto b = ac.begin() + ap[(size_t)i], e = ac.begin() + ap[(size_t)i + 1];
+        std::sort(b, e);
+        ae[(size_t)i] = std::unique(b, e) - ac.begin();
+    }
+    std::vector<int64_t> banned;                                         // banned[c] == i + 1: colour c is held inside dist2[i]
+    int32_t ncol = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        auto ban = [&](int32_t k) {
+            if (k >= i) return;                                          // not coloured yet (k == i: itself)
+            const int32_t c = colors[k];
+            if ((size_t)c >= banned.size()) banned.resize((size_t)c + 1, 0);
+            banned[(size_t)c] = i + 1;
+        };
+        for (int64_t p = ap[(size_t)i]; p < ae[(size_t)i]; ++p) {
+            const int32_t j = ac[(size_t)p];
+            ban(j);
+            for (int64_t q = ap[(size_t)j]; q < ae[(size_t)j]; ++q) ban(ac[(size_t)q]);
+        }
+        int32_t c = 0;
+        while ((size_t)c < banned.size() && banned[(size_t)c] == i + 1) ++c;
+        colors[i] = c;
+        ncol = std::max(ncol, c + 1);
+    }
+    return ncol;
+}
+
 }  // namespace kr

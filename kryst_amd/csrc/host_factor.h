@@ -96,5 +96,9 @@ void host_ilut_rows(int64_t n, const int64_t* rp, const int32_t* col, const doub
 // dependency levels of a triangular factor given by its strictly-lower (forward) or strictly-upper (!forward) rows: lvl[i] = 1 + the highest
 // level among the rows i depends on (0 when it depends on none).  Returns the number of levels.
 int32_t host_levels(int64_t n, const int64_t* ptr, const int32_t* col, bool forward, int32_t* lvl);
+// color_graph of utils/coloring.rs on the stored pattern (ptr, col) of an n x n matrix (columns in [0, n), any order): adj[i] = the j != i with
+// (i, j) or (j, i) stored, dist2[i] = adj[i] + the adj[j] of its members + i, then rows in ascending order take the lowest colour no
+// already-coloured member of dist2[i] holds.  Returns the number of colours.
+int32_t host_color_graph(int64_t n, const int64_t* ptr, const int32_t* col, int32_t* colors);
 
 }  // namespace kr

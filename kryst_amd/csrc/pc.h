@@ -2,7 +2,7 @@
 #pragma once
 #include "csr.h"
 
-enum { KR_PC_IDENTITY = 1, KR_PC_JACOBI = 2, KR_PC_ILU = 3, KR_PC_CHEB_STUB = 6, KR_PC_CHEB = 7, KR_PC_SPAI = 9, KR_PC_BLOCK_JACOBI = 10, KR_PC_AMG = 11, KR_PC_ASM = 12 };
+enum { KR_PC_IDENTITY = 1, KR_PC_JACOBI = 2, KR_PC_ILU = 3, KR_PC_CHEB_STUB = 6, KR_PC_CHEB = 7, KR_PC_SPAI = 9, KR_PC_BLOCK_JACOBI = 10, KR_PC_AMG = 11, KR_PC_ASM = 12, KR_PC_SOR = 13 };
 
 namespace kr { struct AmgDev; }
 
@@ -45,6 +45,16 @@ struct kryst_pc_s {
     int32_t* d_asm_idx = nullptr;
     int32_t* d_asm_mptr = nullptr; int32_t* d_asm_mpos = nullptr;
     std::vector<int64_t> asm_ptr_h; std::vector<int32_t> asm_idx_h, asm_owner_h;   // owner: the last un-grown set containing a row, or -1
+    // SOR / SSOR (sor.hip): the parameters, 1 / (a_ii + fshift) in d_inv_diag, and per sweep direction (0 forward, 1 backward) the rows
+    // ordered by dependency level of the (coloured) sweep order with the level offsets
+    double sor_omega = 1.0, sor_fshift = 0.0;
+    int32_t sor_its = 1, sor_lits = 1, sor_sym = 0;
+    int32_t* d_sor_rows[2] = {nullptr, nullptr}; int32_t* d_sor_off[2] = {nullptr, nullptr};
+    int32_t sor_groups[2] = {0, 0}; uint32_t sor_grid[2] = {1, 1};
+    int32_t* d_sor_pos = nullptr;     // coloured order: the position of every row, or nullptr (position = row)
+    int32_t* d_sor_ent = nullptr;     // coloured order: every row's entries in ascending position, or nullptr (the stored order)
+    uint32_t* d_sor_sync = nullptr;   // the arrival counter of the sweep kernel's grid barrier, zeroed in front of every launch
+    uint32_t* h_sor_gave_up = nullptr; uint32_t* d_sor_gave_up = nullptr;   // mapped host word: a barrier's patience ran out (sticky until read)
 };
 
 namespace kr {
@@ -60,6 +70,9 @@ void bj_free(kryst_pc_t pc);
 int32_t amg_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done);   // amg.hip
 int32_t asm_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done);   // asm.hip
 void asm_free(kryst_pc_t pc);
+int32_t sor_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done);   // sor.hip
+void sor_free(kryst_pc_t pc);
+int32_t sor_health(kryst_pc_t pc);
 // whether the apply reads z on entry (AMG as written starts its finest level from the incoming z, amg.rs:211)
 bool pc_reads_z(kryst_pc_t pc);
 // pc_apply_dev for solvers whose reference apply gets a FRESH z: z = 0 (init == nullptr; gmres.rs:244, 250, 256, 283, 311, 339) or

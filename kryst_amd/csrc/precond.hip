@@ -114,7 +114,10 @@ void    ilu_free(kryst_pc_t pc);
 int32_t ilu_health(kryst_pc_t pc);
 bool    ilu_fell_back(kryst_pc_t pc);
 bool    ilu_is_wavefront(kryst_pc_t pc);
-int32_t pc_health(kryst_pc_t pc) { return (pc && pc->kind == KR_PC_ILU && pc->d_work) ? ilu_health(pc) : KRYST_OK; }
+int32_t pc_health(kryst_pc_t pc) {
+    if (pc && pc->kind == KR_PC_SOR) return sor_health(pc);
+    return (pc && pc->kind == KR_PC_ILU && pc->d_work) ? ilu_health(pc) : KRYST_OK;
+}
 bool pc_fell_back(kryst_pc_t pc) { return pc && pc->kind == KR_PC_ILU && pc->d_work && ilu_fell_back(pc); }
 
 static int32_t pc_apply_kind(kryst_pc_t pc, const double* r, double* z, const int* done) {
@@ -135,6 +138,7 @@ static int32_t pc_apply_kind(kryst_pc_t pc, const double* r, double* z, const in
         case KR_PC_BLOCK_JACOBI: return bj_apply_dev(pc, r, z, done);
         case KR_PC_ASM: return asm_apply_dev(pc, r, z, done);
         case KR_PC_AMG: return amg_apply_dev(pc, r, z, done);
+        case KR_PC_SOR: return sor_apply_dev(pc, r, z, done);
         default: set_error("unknown preconditioner kind %d", pc->kind); return KRYST_UNSUPPORTED;
     }
 }
@@ -216,6 +220,10 @@ int32_t kryst_pc_apply(kryst_pc_t pc, kryst_vec_t r, kryst_vec_t z) {
         return pc_apply_dev(&tmp, r->d, z->d, nullptr);
     }
     KR_TRY(pc_apply_dev(pc, r->d, z->d, nullptr));
+    if (pc->kind == KR_PC_SOR) {                         // a sweep whose grid barrier gave up is an error here, not a vector of NaNs
+        KR_HIP(hipStreamSynchronize(pc->ctx->s_main));
+        return pc_health(pc);
+    }
     if (pc->kind == KR_PC_ILU && pc->d_work && ilu_is_wavefront(pc)) {
         // the wavefront solve relies on in-order workgroup dispatch (tri_wave.h): wait, and if it gave up repeat the apply
         // with the plane kernels (same bits)
@@ -266,6 +274,7 @@ int32_t kryst_pc_destroy(kryst_pc_t pc) {
     ilu_free(pc);
     bj_free(pc);
     asm_free(pc);
+    sor_free(pc);
     amg_free(pc);
     if (pc->spai_m) kryst_csr_destroy(pc->spai_m);
     delete pc;
