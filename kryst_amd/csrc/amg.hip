@@ -27,14 +27,19 @@ struct AmgDevLevel {
     double* rv = nullptr; double* zv = nullptr;   // coarse levels: the restricted residual and the correction
     int64_t n = 0;
 };
-struct AmgDev {
-    int variant = KRYST_AMG_AS_WRITTEN;
-    int nu_pre = 1, nu_post = 1;
+struct AmgDev final : kryst_pc_s {    // the levels, their operators and work vectors
+    static constexpr int KIND = KR_PC_AMG;
+    const int variant, nu_pre, nu_post;
     std::vector<AmgDevLevel> lv;
     int32_t* c_ptr = nullptr; int32_t* c_col = nullptr; double* c_val = nullptr;   // the coarsest operator, plain CSR for the CG kernel
     double* c_work = nullptr;         // 3 n: residual, p, Ap
     kryst_pc_t bj = nullptr;          // smoothed aggregation: block Jacobi of 64 rows on the coarsest operator (owned)
     std::vector<int32_t*> agg;        // smoothed aggregation: the aggregate of every row, per coarsened level (owned)
+    AmgDev(kryst_csr_t a_, int variant_, int pre, int post) : kryst_pc_s(a_->ctx, KIND, a_, a_->nrows), variant(variant_), nu_pre(pre), nu_post(post) {}
+    ~AmgDev() override;
+    int32_t vcycle(size_t l, const double* r, double* z, const int* done);
+    int32_t apply(int64_t nv, const double* r, double* z, const int* done) override;
+    bool reads_z() const override { return variant == KRYST_AMG_AS_WRITTEN; }
 };
 
 struct AmgSweepOp {                  // z[i] += diag_inv[i] * (r[i] - (A z)[i])   (:183-185)
@@ -59,14 +64,6 @@ struct AmgAddOp {                    // z[i] += fine_correction[i]   (:244-246)
     __device__ __forceinline__ void pair(int64_t i, bool, bool, double (&)[1]) const {
         const d2 tt = ld2(t, i), zz = ld2(z, i);
         st2(z, i, zz.a + tt.a, zz.b + tt.b);
-    }
-};
-
-struct AmgSetOp {                    // z[i] = src ? src[i] : 0.0  (a fresh z for the apply)
-    static constexpr int NQ = 0; static constexpr const char* TAG = "AmgSet";
-    const double* src; double* z;
-    __device__ __forceinline__ void pair(int64_t i, bool, bool, double (&)[1]) const {
-        if (src) { const d2 v = ld2(src, i); st2(z, i, v.a, v.b); } else st2(z, i, 0.0, 0.0);
     }
 };
 
@@ -128,13 +125,12 @@ static int32_t amg_alloc(kryst_ctx_t ctx, double** p, int64_t n) {
 }
 
 // apply_recursive(level, r, z) (:200-250)
-static int32_t amg_vcycle(kryst_pc_t pc, size_t l, const double* r, double* z, const int* done) {
-    AmgDev& H = *pc->amg;
-    kryst_ctx_t ctx = pc->ctx;
+int32_t AmgDev::vcycle(size_t l, const double* r, double* z, const int* done) {
+    AmgDev& H = *this;
     AmgDevLevel& L = H.lv[l];
     if (l + 1 == H.lv.size()) {                                                           // :201-204
         if (L.n == 0) return KRYST_OK;
-        if (H.variant == KRYST_AMG_SMOOTHED) return bj_apply_dev(H.bj, r, z, done);        // exact inverse when A_c has <= 64 rows
+        if (H.variant == KRYST_AMG_SMOOTHED) return H.bj->apply(L.n, r, z, done);        // exact inverse when A_c has <= 64 rows
         hipLaunchKernelGGL(amg_coarse_cg_kernel, dim3(1), dim3(KR_AMG_CG_THREADS), 0, ctx->s_main, H.c_ptr, H.c_col, H.c_val,
                            (int32_t)L.n, r, z, H.c_work, done);
         KR_HIP(hipGetLastError());
@@ -149,7 +145,7 @@ static int32_t amg_vcycle(kryst_pc_t pc, size_t l, const double* r, double* z, c
     KR_TRY(launch_ew(ctx, AmgResidualOp{r, L.t}, L.n, done));
     KR_TRY(launch_spmv(L.r, L.t, C.rv, 0, nullptr, done));                                // :226-227
     KR_HIP(hipMemsetAsync(C.zv, 0, sizeof(double) * (size_t)amg_padded(C.n), ctx->s_main));   // :229
-    KR_TRY(amg_vcycle(pc, l + 1, C.rv, C.zv, done));                                      // :230-234
+    KR_TRY(vcycle(l + 1, C.rv, C.zv, done));                                      // :230-234
     KR_TRY(launch_spmv(L.p, C.zv, L.t, 0, nullptr, done));                                // :236-237
     KR_TRY(launch_ew(ctx, AmgAddOp{L.t, z}, L.n, done));                                  // :238-247
     for (int s = 0; s < H.nu_post; ++s) {                                                 // :249
@@ -159,23 +155,15 @@ static int32_t amg_vcycle(kryst_pc_t pc, size_t l, const double* r, double* z, c
     return KRYST_OK;
 }
 
-int32_t amg_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done) {
-    if (!pc->amg || pc->amg->lv.empty()) { set_error("amg: no hierarchy"); return KRYST_SOLVE_ERROR; }
-    if (pc->amg->variant == KRYST_AMG_SMOOTHED)                                            // z starts from zero: M is linear and symmetric
-        KR_TRY(launch_ew(pc->ctx, AmgSetOp{nullptr, z}, pc->n, done));
-    return amg_vcycle(pc, 0, r, z, done);
+int32_t AmgDev::apply(int64_t, const double* r, double* z, const int* done) {
+    if (lv.empty()) { set_error("amg: no hierarchy"); return KRYST_SOLVE_ERROR; }
+    if (variant == KRYST_AMG_SMOOTHED)                                                     // z starts from zero: M is linear and symmetric
+        KR_TRY(launch_ew(ctx, AmgSetOp{nullptr, z}, n, done));
+    return vcycle(0, r, z, done);
 }
 
-bool pc_reads_z(kryst_pc_t pc) { return pc && pc->kind == KR_PC_AMG && pc->amg && pc->amg->variant == KRYST_AMG_AS_WRITTEN; }
-
-int32_t pc_apply_dev_fresh(kryst_pc_t pc, const double* r, double* z, const int* done, const double* init) {
-    if (pc_reads_z(pc) && init != z) KR_TRY(launch_ew(pc->ctx, AmgSetOp{init, z}, pc->n, done));
-    return pc_apply_dev(pc, r, z, done);
-}
-
-void amg_free(kryst_pc_t pc) {
-    if (!pc->amg) return;
-    AmgDev& H = *pc->amg;
+AmgDev::~AmgDev() {
+    AmgDev& H = *this;
     for (size_t l = 0; l < H.lv.size(); ++l) {
         AmgDevLevel& L = H.lv[l];
         if (l > 0 && L.a) kryst_csr_destroy(L.a);
@@ -186,8 +174,6 @@ void amg_free(kryst_pc_t pc) {
     (void)hipFree(H.c_ptr); (void)hipFree(H.c_col); (void)hipFree(H.c_val); (void)hipFree(H.c_work);
     if (H.bj) kryst_pc_destroy(H.bj);
     for (int32_t* g : H.agg) (void)hipFree(g);
-    delete pc->amg;
-    pc->amg = nullptr;
 }
 
 static int32_t upload_csr_level(kryst_ctx_t ctx, const HostCsr& m, kryst_csr_t* out) {
@@ -203,9 +189,9 @@ static int32_t upload(kryst_ctx_t ctx, T** d, const T* h, size_t n, size_t alloc
 }
 
 // the hierarchy the host set-up built, on the device (level 0's operator is `a` itself)
-static int32_t amg_upload(kryst_pc_t pc, std::vector<AmgHostLevel>& hl) {
+static int32_t amg_upload(AmgDev* pc, std::vector<AmgHostLevel>& hl) {
     kryst_ctx_t ctx = pc->ctx;
-    AmgDev& H = *pc->amg;
+    AmgDev& H = *pc;
     H.lv.resize(hl.size());
     for (size_t l = 0; l < hl.size(); ++l) {
         AmgHostLevel& S = hl[l];
@@ -513,9 +499,9 @@ static int32_t sa_level(kryst_ctx_t ctx, const int32_t* ptr, const int32_t* col,
 }
 
 // the SA hierarchy: coarsen while n > 64, for at most max_levels levels, and until n_c > 0.8 n (a stalled level is dropped)
-static int32_t sa_build(kryst_pc_t pc, int32_t max_levels, double theta) {
+static int32_t sa_build(AmgDev* pc, int32_t max_levels, double theta) {
     kryst_ctx_t ctx = pc->ctx;
-    AmgDev& H = *pc->amg;
+    AmgDev& H = *pc;
     kryst_csr_t cur = pc->a;
     for (int32_t lv = 0; ; ++lv) {
         AmgDevLevel L;
@@ -566,10 +552,7 @@ int32_t kryst_pc_amg(kryst_csr_t a, int32_t max_levels, double threshold, int32_
     if (variant == KRYST_AMG_SMOOTHED) {                  // labelled extension: threshold is theta of the strength test
         KR_ARG(max_levels >= 1, "pc_amg: smoothed aggregation needs max_levels >= 1");
         KR_ARG(threshold >= 0.0, "pc_amg: theta must be >= 0");
-        kryst_pc_t pc = new kryst_pc_s();
-        pc->ctx = a->ctx; pc->kind = KR_PC_AMG; pc->a = a; pc->n = a->nrows;
-        pc->amg = new AmgDev();
-        pc->amg->variant = variant; pc->amg->nu_pre = nu_pre; pc->amg->nu_post = nu_post;
+        AmgDev* pc = new AmgDev(a, variant, nu_pre, nu_post);
         const int32_t rc = sa_build(pc, max_levels, threshold);
         if (rc != KRYST_OK) { kryst_pc_destroy(pc); return rc; }
         *out = pc;
@@ -587,42 +570,41 @@ int32_t kryst_pc_amg(kryst_csr_t a, int32_t max_levels, double threshold, int32_
                   (long long)hl.back().a.nrows, (int)KRYST_AMG_DIRECT_MAX);
         return KRYST_UNSUPPORTED;
     }
-    kryst_pc_t pc = new kryst_pc_s();
-    pc->ctx = a->ctx; pc->kind = KR_PC_AMG; pc->a = a; pc->n = n;
-    pc->amg = new AmgDev();
-    pc->amg->variant = variant; pc->amg->nu_pre = nu_pre; pc->amg->nu_post = nu_post;
+    AmgDev* pc = new AmgDev(a, variant, nu_pre, nu_post);
     const int32_t rc = amg_upload(pc, hl);
     if (rc != KRYST_OK) { kryst_pc_destroy(pc); return rc; }
     *out = pc;
     return KRYST_OK;
 }
 
-int32_t kryst_pc_amg_info(kryst_pc_t pc, int32_t* nlevels, int64_t* rows, int64_t* nnz, int32_t count) {
-    KR_ARG(pc && pc->kind == KR_PC_AMG && pc->amg, "pc_amg_info: not an AMG preconditioner");
-    const int32_t L = (int32_t)pc->amg->lv.size();
+int32_t kryst_pc_amg_info(kryst_pc_t h, int32_t* nlevels, int64_t* rows, int64_t* nnz, int32_t count) {
+    AmgDev* pc = pc_cast<AmgDev>(h);
+    KR_ARG(pc, "pc_amg_info: not an AMG preconditioner");
+    const int32_t L = (int32_t)pc->lv.size();
     if (nlevels) *nlevels = L;
     KR_ARG((!rows && !nnz) || count >= L, "pc_amg_info: count < levels");
     for (int32_t l = 0; l < L; ++l) {
-        if (rows) rows[l] = pc->amg->lv[l].n;
-        if (nnz) nnz[l] = pc->amg->lv[l].a->nnz;
+        if (rows) rows[l] = pc->lv[l].n;
+        if (nnz) nnz[l] = pc->lv[l].a->nnz;
     }
     return KRYST_OK;
 }
 
-int32_t kryst_pc_amg_export(kryst_pc_t pc, int32_t level, int32_t which, int64_t* nrows, int64_t* ncols, int64_t* nnz, int64_t* row_ptr,
+int32_t kryst_pc_amg_export(kryst_pc_t h, int32_t level, int32_t which, int64_t* nrows, int64_t* ncols, int64_t* nnz, int64_t* row_ptr,
                             int32_t* col, double* val) {
-    KR_ARG(pc && pc->kind == KR_PC_AMG && pc->amg, "pc_amg_export: not an AMG preconditioner");
-    KR_ARG(level >= 0 && level < (int32_t)pc->amg->lv.size(), "pc_amg_export: level out of range");
+    AmgDev* pc = pc_cast<AmgDev>(h);
+    KR_ARG(pc, "pc_amg_export: not an AMG preconditioner");
+    KR_ARG(level >= 0 && level < (int32_t)pc->lv.size(), "pc_amg_export: level out of range");
     KR_ARG(which >= 0 && which <= 4, "pc_amg_export: which must be 0 (A), 1 (P), 2 (R), 3 (D^-1) or 4 (aggregates)");
     KR_HIP(hipSetDevice(pc->ctx->device));
-    AmgDevLevel& L = pc->amg->lv[level];
+    AmgDevLevel& L = pc->lv[level];
     if (which == 4) {                                      // smoothed aggregation: the aggregate of every row (none on the last level)
-        const bool has = level < (int32_t)pc->amg->agg.size();
+        const bool has = level < (int32_t)pc->agg.size();
         if (nrows) *nrows = has ? L.n : 0;
         if (ncols) *ncols = 1;
         if (nnz) *nnz = has ? L.n : 0;
         if (has && col && L.n) {
-            KR_HIP(hipMemcpyAsync(col, pc->amg->agg[level], sizeof(int32_t) * (size_t)L.n, hipMemcpyDeviceToHost, pc->ctx->s_main));
+            KR_HIP(hipMemcpyAsync(col, pc->agg[level], sizeof(int32_t) * (size_t)L.n, hipMemcpyDeviceToHost, pc->ctx->s_main));
             KR_HIP(hipStreamSynchronize(pc->ctx->s_main));
         }
         return KRYST_OK;

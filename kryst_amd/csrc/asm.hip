@@ -264,29 +264,36 @@ __global__ __launch_bounds__(KR_ASM_T) void asm_combine_kernel(const int32_t* mp
     }
 }
 
-int32_t asm_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done) {
-    kryst_ctx_t ctx = pc->ctx;
-    const int64_t total = pc->asm_total;
+// the (grown) subdomains sorted ascending, their tiles block after block (column-major inside a tile), the products X of an apply (one
+// entry per subdomain row) and the row -> positions-in-X map of the combine
+struct AsmPc final : kryst_pc_s {
+    static constexpr int KIND = KR_PC_ASM;
+    int64_t nsub = 0, total = 0;      // subdomains; sum of their rows
+    int32_t maxb = 0;
+    double* d_tile = nullptr; int64_t* d_toff = nullptr; double* d_x = nullptr;
+    int32_t* d_xoff = nullptr;        // subdomain k's rows: positions [xoff[k], xoff[k + 1]) of d_idx / X
+    int32_t* d_posk = nullptr;        // the subdomain of every position
+    int32_t* d_idx = nullptr;
+    int32_t* d_mptr = nullptr; int32_t* d_mpos = nullptr;
+    std::vector<int64_t> ptr_h; std::vector<int32_t> idx_h, owner_h;   // owner: the last un-grown set containing a row, or -1
+    AsmPc(kryst_csr_t a_, int64_t nsub_, int64_t total_, int32_t maxb_) : kryst_pc_s(a_->ctx, KIND, a_, a_->nrows), nsub(nsub_), total(total_), maxb(maxb_) {}
+    ~AsmPc() override { for (void* p : {(void*)d_tile, (void*)d_toff, (void*)d_xoff, (void*)d_posk, (void*)d_idx, (void*)d_x, (void*)d_mptr, (void*)d_mpos}) (void)pool_free(p); }
+    int32_t apply(int64_t nv, const double* r, double* z, const int* done) override;
+};
+
+int32_t AsmPc::apply(int64_t, const double* r, double* z, const int* done) {
     if (total > 0) {
-        hipLaunchKernelGGL(asm_products_kernel, dim3(asm_grid(total, KR_ASM_T)), dim3(KR_ASM_T), 0, ctx->s_main, (const double*)pc->d_asm_tile,
-                           (const int64_t*)pc->d_asm_toff, (const int32_t*)pc->d_asm_xoff, (const int32_t*)pc->d_asm_posk,
-                           (const int32_t*)pc->d_asm_idx, total, r, pc->d_asm_x, done);
+        hipLaunchKernelGGL(asm_products_kernel, dim3(asm_grid(total, KR_ASM_T)), dim3(KR_ASM_T), 0, ctx->s_main, (const double*)d_tile,
+                           (const int64_t*)d_toff, (const int32_t*)d_xoff, (const int32_t*)d_posk,
+                           (const int32_t*)d_idx, total, r, d_x, done);
         KR_HIP(hipGetLastError());
     }
-    if (pc->n > 0) {
-        hipLaunchKernelGGL(asm_combine_kernel, dim3(asm_grid(pc->n, KR_ASM_T)), dim3(KR_ASM_T), 0, ctx->s_main, (const int32_t*)pc->d_asm_mptr,
-                           (const int32_t*)pc->d_asm_mpos, (const double*)pc->d_asm_x, pc->n, z, done);
+    if (n > 0) {
+        hipLaunchKernelGGL(asm_combine_kernel, dim3(asm_grid(n, KR_ASM_T)), dim3(KR_ASM_T), 0, ctx->s_main, (const int32_t*)d_mptr,
+                           (const int32_t*)d_mpos, (const double*)d_x, n, z, done);
         KR_HIP(hipGetLastError());
     }
     return KRYST_OK;
-}
-
-void asm_free(kryst_pc_t pc) {
-    for (void* p : {(void*)pc->d_asm_tile, (void*)pc->d_asm_toff, (void*)pc->d_asm_xoff, (void*)pc->d_asm_posk, (void*)pc->d_asm_idx,
-                    (void*)pc->d_asm_x, (void*)pc->d_asm_mptr, (void*)pc->d_asm_mpos})
-        (void)pool_free(p);
-    pc->d_asm_tile = nullptr; pc->d_asm_toff = nullptr; pc->d_asm_xoff = nullptr; pc->d_asm_posk = nullptr; pc->d_asm_idx = nullptr;
-    pc->d_asm_x = nullptr; pc->d_asm_mptr = nullptr; pc->d_asm_mpos = nullptr;
 }
 
 template <class T> static int32_t asm_upload(kryst_ctx_t ctx, T** d, const std::vector<T>& h, const char* what) {
@@ -374,13 +381,13 @@ static int32_t asm_grow(kryst_csr_t a, int overlap, std::vector<int64_t>& ptr, s
 }
 
 // inverts every subdomain: the sets of at most 64 rows with one wave, the others with two
-static int32_t asm_tiles_run(kryst_pc_t pc) {
+static int32_t asm_tiles_run(AsmPc* pc) {
     kryst_ctx_t ctx = pc->ctx;
     kryst_csr_t a = pc->a;
     std::vector<int32_t> small, large;
     int bsmall = 0, blarge = 0;
-    for (int64_t k = 0; k < pc->asm_nsub; ++k) {
-        const int b = (int)(pc->asm_ptr_h[(size_t)k + 1] - pc->asm_ptr_h[(size_t)k]);
+    for (int64_t k = 0; k < pc->nsub; ++k) {
+        const int b = (int)(pc->ptr_h[(size_t)k + 1] - pc->ptr_h[(size_t)k]);
         if (b == 0) continue;
         if (b <= 64) { small.push_back((int32_t)k); bsmall = std::max(bsmall, b); }
         else { large.push_back((int32_t)k); blarge = std::max(blarge, b); }
@@ -407,11 +414,11 @@ static int32_t asm_tiles_run(kryst_pc_t pc) {
         if (!small.empty())
             hipLaunchKernelGGL(asm_tiles_kernel<64>, dim3(asm_grid((int64_t)small.size(), 1)), dim3(64), sizeof(double) * bsmall * asm_stride(bsmall),
                                ctx->s_main, a->d_row_ptr, a->d_col, a->d_val, (const int32_t*)d_small, (int64_t)small.size(),
-                               (const int32_t*)pc->d_asm_xoff, (const int64_t*)pc->d_asm_toff, (const int32_t*)pc->d_asm_idx, pc->d_asm_tile, d_err);
+                               (const int32_t*)pc->d_xoff, (const int64_t*)pc->d_toff, (const int32_t*)pc->d_idx, pc->d_tile, d_err);
         if (!large.empty())
             hipLaunchKernelGGL(asm_tiles_kernel<128>, dim3(asm_grid((int64_t)large.size(), 1)), dim3(128), lds_large,
                                ctx->s_main, a->d_row_ptr, a->d_col, a->d_val, (const int32_t*)d_large, (int64_t)large.size(),
-                               (const int32_t*)pc->d_asm_xoff, (const int64_t*)pc->d_asm_toff, (const int32_t*)pc->d_asm_idx, pc->d_asm_tile, d_err);
+                               (const int32_t*)pc->d_xoff, (const int64_t*)pc->d_toff, (const int32_t*)pc->d_idx, pc->d_tile, d_err);
         if (hipGetLastError() != hipSuccess) { set_error("additive Schwarz: set-up launch failed"); rc = KRYST_ERR_HIP; }
     }
     unsigned long long e = KR_ASM_NOERR;
@@ -427,7 +434,7 @@ static int32_t asm_tiles_run(kryst_pc_t pc) {
         set_error("additive Schwarz: subdomain %lld holds a NaN or Inf", (long long)k);
         return KRYST_FACTOR_ERROR;
     }
-    const int64_t row = (int64_t)pc->asm_idx_h[(size_t)(pc->asm_ptr_h[(size_t)k] + pos)];
+    const int64_t row = (int64_t)pc->idx_h[(size_t)(pc->ptr_h[(size_t)k] + pos)];
     set_error("additive Schwarz: subdomain %lld is singular (zero pivot at row %lld)", (long long)k, (long long)row);
     set_error_row(row);
     return KRYST_ZERO_PIVOT;
@@ -504,25 +511,23 @@ static int32_t asm_setup(kryst_csr_t a, const int64_t* sub_ptr, const int64_t* s
         std::fill(posk.begin() + ptr[(size_t)k], posk.begin() + ptr[(size_t)k + 1], (int32_t)k);
     }
     xoff[(size_t)nsub] = (int32_t)ptr.back();
-    kryst_pc_t pc = new kryst_pc_s();
-    pc->ctx = a->ctx; pc->kind = KR_PC_ASM; pc->a = a; pc->n = n;
-    pc->asm_nsub = nsub; pc->asm_total = (int64_t)idx.size(); pc->asm_maxb = bmax;
+    AsmPc* pc = new AsmPc(a, nsub, (int64_t)idx.size(), bmax);
     kryst_ctx_t ctx = a->ctx;
-    int32_t rc = asm_upload(ctx, &pc->d_asm_xoff, xoff, "subdomain offsets");
-    if (rc == KRYST_OK) rc = asm_upload(ctx, &pc->d_asm_toff, toff, "tile offsets");
-    if (rc == KRYST_OK) rc = asm_upload(ctx, &pc->d_asm_idx, idx, "index sets");
-    if (rc == KRYST_OK) rc = asm_upload(ctx, &pc->d_asm_posk, posk, "position map");
-    if (rc == KRYST_OK) rc = asm_upload(ctx, &pc->d_asm_mptr, mptr, "row map");
-    if (rc == KRYST_OK) rc = asm_upload(ctx, &pc->d_asm_mpos, mpos, "row map");
-    if (rc == KRYST_OK && pool_malloc(&pc->d_asm_x, sizeof(double) * (size_t)std::max<int64_t>(pc->asm_total, 1)) != hipSuccess) {
-        (void)hipGetLastError(); pc->d_asm_x = nullptr;
-        set_error("additive Schwarz: out of device memory (%lld subdomain rows)", (long long)pc->asm_total); rc = KRYST_ERR_HIP;
+    int32_t rc = asm_upload(ctx, &pc->d_xoff, xoff, "subdomain offsets");
+    if (rc == KRYST_OK) rc = asm_upload(ctx, &pc->d_toff, toff, "tile offsets");
+    if (rc == KRYST_OK) rc = asm_upload(ctx, &pc->d_idx, idx, "index sets");
+    if (rc == KRYST_OK) rc = asm_upload(ctx, &pc->d_posk, posk, "position map");
+    if (rc == KRYST_OK) rc = asm_upload(ctx, &pc->d_mptr, mptr, "row map");
+    if (rc == KRYST_OK) rc = asm_upload(ctx, &pc->d_mpos, mpos, "row map");
+    if (rc == KRYST_OK && pool_malloc(&pc->d_x, sizeof(double) * (size_t)std::max<int64_t>(pc->total, 1)) != hipSuccess) {
+        (void)hipGetLastError(); pc->d_x = nullptr;
+        set_error("additive Schwarz: out of device memory (%lld subdomain rows)", (long long)pc->total); rc = KRYST_ERR_HIP;
     }
-    if (rc == KRYST_OK && pool_malloc(&pc->d_asm_tile, sizeof(double) * (size_t)std::max<int64_t>(toff.back(), 1)) != hipSuccess) {
-        (void)hipGetLastError(); pc->d_asm_tile = nullptr;
+    if (rc == KRYST_OK && pool_malloc(&pc->d_tile, sizeof(double) * (size_t)std::max<int64_t>(toff.back(), 1)) != hipSuccess) {
+        (void)hipGetLastError(); pc->d_tile = nullptr;
         set_error("additive Schwarz: out of device memory for %lld tile entries", (long long)toff.back()); rc = KRYST_ERR_HIP;
     }
-    pc->asm_ptr_h = std::move(ptr); pc->asm_idx_h = std::move(idx); pc->asm_owner_h = std::move(owner);
+    pc->ptr_h = std::move(ptr); pc->idx_h = std::move(idx); pc->owner_h = std::move(owner);
     if (rc == KRYST_OK) rc = asm_tiles_run(pc);
     if (rc != KRYST_OK) { kryst_pc_destroy(pc); return rc; }
     *out = pc;
@@ -565,27 +570,29 @@ int32_t kryst_pc_asm_uniform(kryst_csr_t a, int64_t nparts, int32_t overlap, int
     return asm_setup(a, ptr.data(), idx.data(), p, overlap, variant, out);
 }
 
-int32_t kryst_pc_asm_info(kryst_pc_t pc, int64_t* nsub, int64_t* ext_rows, int32_t* max_rows) {
-    KR_ARG(pc && pc->kind == KR_PC_ASM, "pc_asm_info");
-    if (nsub) *nsub = pc->asm_nsub;
-    if (ext_rows) *ext_rows = pc->asm_total;
-    if (max_rows) *max_rows = pc->asm_maxb;
+int32_t kryst_pc_asm_info(kryst_pc_t h, int64_t* nsub, int64_t* ext_rows, int32_t* max_rows) {
+    AsmPc* pc = pc_cast<AsmPc>(h);
+    KR_ARG(pc, "pc_asm_info");
+    if (nsub) *nsub = pc->nsub;
+    if (ext_rows) *ext_rows = pc->total;
+    if (max_rows) *max_rows = pc->maxb;
     return KRYST_OK;
 }
 
-int32_t kryst_pc_asm_export(kryst_pc_t pc, int64_t* sub_ptr, int32_t* sub_idx, int32_t* owner, double* tiles) {
-    KR_ARG(pc && pc->kind == KR_PC_ASM, "pc_asm_export");
-    if (sub_ptr) std::copy(pc->asm_ptr_h.begin(), pc->asm_ptr_h.end(), sub_ptr);
-    if (sub_idx) std::copy(pc->asm_idx_h.begin(), pc->asm_idx_h.end(), sub_idx);
-    if (owner) std::copy(pc->asm_owner_h.begin(), pc->asm_owner_h.end(), owner);
+int32_t kryst_pc_asm_export(kryst_pc_t h, int64_t* sub_ptr, int32_t* sub_idx, int32_t* owner, double* tiles) {
+    AsmPc* pc = pc_cast<AsmPc>(h);
+    KR_ARG(pc, "pc_asm_export");
+    if (sub_ptr) std::copy(pc->ptr_h.begin(), pc->ptr_h.end(), sub_ptr);
+    if (sub_idx) std::copy(pc->idx_h.begin(), pc->idx_h.end(), sub_idx);
+    if (owner) std::copy(pc->owner_h.begin(), pc->owner_h.end(), owner);
     if (tiles) {
         int64_t entries = 0;
-        for (int64_t k = 0; k < pc->asm_nsub; ++k) {
-            const int64_t b = pc->asm_ptr_h[(size_t)k + 1] - pc->asm_ptr_h[(size_t)k];
+        for (int64_t k = 0; k < pc->nsub; ++k) {
+            const int64_t b = pc->ptr_h[(size_t)k + 1] - pc->ptr_h[(size_t)k];
             entries += b * b;
         }
         KR_HIP(hipSetDevice(pc->ctx->device));
-        if (entries > 0) KR_HIP(hipMemcpyAsync(tiles, pc->d_asm_tile, sizeof(double) * (size_t)entries, hipMemcpyDeviceToHost, pc->ctx->s_main));
+        if (entries > 0) KR_HIP(hipMemcpyAsync(tiles, pc->d_tile, sizeof(double) * (size_t)entries, hipMemcpyDeviceToHost, pc->ctx->s_main));
         KR_HIP(hipStreamSynchronize(pc->ctx->s_main));
     }
     return KRYST_OK;

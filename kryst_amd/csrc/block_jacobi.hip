@@ -188,57 +188,64 @@ static unsigned bj_grid(int64_t waves, int waves_per_wg) {
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>((waves + waves_per_wg - 1) / waves_per_wg, KR_BJ_GRID_CAP));
 }
 
-static int64_t bj_nwaves(kryst_pc_t pc) {
-    return pc->bj_bsize > 0 ? (pc->bj_nblk + KR_BJ_MAX / pc->bj_bsize - 1) / (KR_BJ_MAX / pc->bj_bsize) : pc->bj_nblk;
-}
+// the inverted tiles block after block, column-major inside a tile
+struct BlockJacobiPc final : kryst_pc_s {
+    static constexpr int KIND = KR_PC_BLOCK_JACOBI;
+    int32_t bsize = 0;                // contiguous form: blocks of bsize consecutive rows, the last one shorter; 0: index-set form
+    int64_t nblk = 0;
+    int64_t uncovered = 0;            // rows in no block (index-set form): z = +0.0 there
+    double* d_tile = nullptr;
+    int64_t* d_ptr = nullptr; int64_t* d_toff = nullptr;   // index-set form: block offsets into d_idx, tile offsets
+    int32_t* d_idx = nullptr;         // index-set form: each block's indices, sorted ascending
+    int32_t* d_owner = nullptr;       // index-set form with overlapping blocks or uncovered rows: the last block containing a row, or -1
+    std::vector<int64_t> ptr_h; std::vector<int32_t> idx_h;
+    BlockJacobiPc(kryst_csr_t a_, int32_t bsize_, int64_t nblk_, int64_t uncovered_)
+        : kryst_pc_s(a_->ctx, KIND, a_, a_->nrows), bsize(bsize_), nblk(nblk_), uncovered(uncovered_) {}
+    ~BlockJacobiPc() override { (void)hipFree(d_tile); (void)hipFree(d_ptr); (void)hipFree(d_toff); (void)hipFree(d_idx); (void)hipFree(d_owner); }
+    int64_t nwaves() const { return bsize > 0 ? (nblk + KR_BJ_MAX / bsize - 1) / (KR_BJ_MAX / bsize) : nblk; }
+    int32_t apply(int64_t nv, const double* r, double* z, const int* done) override;
+};
 
-int32_t bj_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done) {
-    kryst_ctx_t ctx = pc->ctx;
-    if (pc->bj_uncovered > 0) {
-        hipLaunchKernelGGL(bj_zero_uncovered_kernel, dim3(bj_grid(pc->n, 256)), dim3(256), 0, ctx->s_main, pc->d_bj_owner, pc->n, z, done);
+int32_t BlockJacobiPc::apply(int64_t, const double* r, double* z, const int* done) {
+    if (uncovered > 0) {
+        hipLaunchKernelGGL(bj_zero_uncovered_kernel, dim3(bj_grid(n, 256)), dim3(256), 0, ctx->s_main, d_owner, n, z, done);
         KR_HIP(hipGetLastError());
     }
-    const int64_t waves = bj_nwaves(pc);
+    const int64_t waves = nwaves();
     if (waves == 0) return KRYST_OK;
-    if (pc->bj_bsize > 0)
+    if (bsize > 0)
         hipLaunchKernelGGL(bj_apply_kernel<false>, dim3(bj_grid(waves, KR_BJ_APPLY_T / 64)), dim3(KR_BJ_APPLY_T), 0, ctx->s_main,
-                           (const double*)pc->d_bj_tile, pc->n, pc->bj_nblk, pc->bj_bsize, (const int64_t*)nullptr, (const int64_t*)nullptr,
+                           (const double*)d_tile, n, nblk, bsize, (const int64_t*)nullptr, (const int64_t*)nullptr,
                            (const int32_t*)nullptr, (const int32_t*)nullptr, r, z, done);
     else
         hipLaunchKernelGGL(bj_apply_kernel<true>, dim3(bj_grid(waves, KR_BJ_APPLY_T / 64)), dim3(KR_BJ_APPLY_T), 0, ctx->s_main,
-                           (const double*)pc->d_bj_tile, pc->n, pc->bj_nblk, 0, (const int64_t*)pc->d_bj_ptr, (const int64_t*)pc->d_bj_toff,
-                           (const int32_t*)pc->d_bj_idx, (const int32_t*)pc->d_bj_owner, r, z, done);
+                           (const double*)d_tile, n, nblk, 0, (const int64_t*)d_ptr, (const int64_t*)d_toff,
+                           (const int32_t*)d_idx, (const int32_t*)d_owner, r, z, done);
     KR_HIP(hipGetLastError());
     return KRYST_OK;
 }
 
-void bj_free(kryst_pc_t pc) {
-    (void)hipFree(pc->d_bj_tile); (void)hipFree(pc->d_bj_ptr); (void)hipFree(pc->d_bj_toff); (void)hipFree(pc->d_bj_idx);
-    (void)hipFree(pc->d_bj_owner);
-    pc->d_bj_tile = nullptr; pc->d_bj_ptr = pc->d_bj_toff = nullptr; pc->d_bj_idx = pc->d_bj_owner = nullptr;
-}
-
 // runs the set-up kernel over pc's blocks and turns its error word into a status (bmax: the largest block)
-static int32_t bj_setup_run(kryst_pc_t pc, int bmax) {
+static int32_t bj_setup_run(BlockJacobiPc* pc, int bmax) {
     kryst_ctx_t ctx = pc->ctx;
     kryst_csr_t a = pc->a;
-    const int64_t waves = bj_nwaves(pc);
+    const int64_t waves = pc->nwaves();
     if (waves == 0 || bmax == 0) return KRYST_OK;
     unsigned long long* d_err = nullptr;
     KR_HIP(hipMalloc(&d_err, sizeof(unsigned long long)));
     int32_t rc = KRYST_OK;
     if (hipMemsetAsync(d_err, 0xFF, sizeof(unsigned long long), ctx->s_main) != hipSuccess) rc = KRYST_ERR_HIP;
     const int bs = bj_stride(bmax);
-    const size_t lds = sizeof(double) * (size_t)(pc->bj_bsize > 0 ? (KR_BJ_MAX / bmax) * bmax * bs : bmax * bs);
+    const size_t lds = sizeof(double) * (size_t)(pc->bsize > 0 ? (KR_BJ_MAX / bmax) * bmax * bs : bmax * bs);
     if (rc == KRYST_OK) {
-        if (pc->bj_bsize > 0)
+        if (pc->bsize > 0)
             hipLaunchKernelGGL(bj_setup_kernel<false>, dim3(bj_grid(waves, 1)), dim3(64), lds, ctx->s_main, a->d_row_ptr, a->d_col, a->d_val,
-                               pc->n, pc->bj_nblk, pc->bj_bsize, (const int64_t*)nullptr, (const int64_t*)nullptr, (const int32_t*)nullptr,
-                               pc->d_bj_tile, d_err);
+                               pc->n, pc->nblk, pc->bsize, (const int64_t*)nullptr, (const int64_t*)nullptr, (const int32_t*)nullptr,
+                               pc->d_tile, d_err);
         else
             hipLaunchKernelGGL(bj_setup_kernel<true>, dim3(bj_grid(waves, 1)), dim3(64), lds, ctx->s_main, a->d_row_ptr, a->d_col, a->d_val,
-                               pc->n, pc->bj_nblk, 0, (const int64_t*)pc->d_bj_ptr, (const int64_t*)pc->d_bj_toff, (const int32_t*)pc->d_bj_idx,
-                               pc->d_bj_tile, d_err);
+                               pc->n, pc->nblk, 0, (const int64_t*)pc->d_ptr, (const int64_t*)pc->d_toff, (const int32_t*)pc->d_idx,
+                               pc->d_tile, d_err);
         if (hipGetLastError() != hipSuccess) { set_error("block Jacobi: set-up launch failed"); rc = KRYST_ERR_HIP; }
     }
     unsigned long long e = KR_BJ_NOERR;
@@ -254,7 +261,7 @@ static int32_t bj_setup_run(kryst_pc_t pc, int bmax) {
         set_error("block Jacobi: block %lld holds a NaN or Inf", (long long)k);
         return KRYST_FACTOR_ERROR;
     }
-    const int64_t row = pc->bj_bsize > 0 ? k * pc->bj_bsize + pos : (int64_t)pc->bj_idx_h[(size_t)pc->bj_ptr_h[(size_t)k] + pos];
+    const int64_t row = pc->bsize > 0 ? k * pc->bsize + pos : (int64_t)pc->idx_h[(size_t)pc->ptr_h[(size_t)k] + pos];
     set_error("block Jacobi: block %lld is singular (zero pivot at row %lld)", (long long)k, (long long)row);
     set_error_row(row);
     return KRYST_ZERO_PIVOT;
@@ -317,17 +324,15 @@ int32_t kryst_pc_block_jacobi(kryst_csr_t a, const int64_t* blk_ptr, const int64
     }
     const int64_t uncovered = std::count(owner.begin(), owner.end(), -1);
     KR_HIP(hipSetDevice(a->ctx->device));
-    kryst_pc_t pc = new kryst_pc_s();
-    pc->ctx = a->ctx; pc->kind = KR_PC_BLOCK_JACOBI; pc->a = a; pc->n = n;
-    pc->bj_bsize = 0; pc->bj_nblk = nblocks; pc->bj_uncovered = uncovered;
-    int32_t rc = bj_upload(a->ctx, &pc->d_bj_ptr, ptr);
-    if (rc == KRYST_OK) rc = bj_upload(a->ctx, &pc->d_bj_toff, toff);
-    if (rc == KRYST_OK) rc = bj_upload(a->ctx, &pc->d_bj_idx, idx);
-    if (rc == KRYST_OK && (overlap || uncovered > 0)) rc = bj_upload(a->ctx, &pc->d_bj_owner, owner);   // only then is an owner test needed
-    if (rc == KRYST_OK && hipMalloc(&pc->d_bj_tile, sizeof(double) * (size_t)std::max<int64_t>(toff.back(), 1)) != hipSuccess) {
+    BlockJacobiPc* pc = new BlockJacobiPc(a, 0, nblocks, uncovered);
+    int32_t rc = bj_upload(a->ctx, &pc->d_ptr, ptr);
+    if (rc == KRYST_OK) rc = bj_upload(a->ctx, &pc->d_toff, toff);
+    if (rc == KRYST_OK) rc = bj_upload(a->ctx, &pc->d_idx, idx);
+    if (rc == KRYST_OK && (overlap || uncovered > 0)) rc = bj_upload(a->ctx, &pc->d_owner, owner);   // only then is an owner test needed
+    if (rc == KRYST_OK && hipMalloc(&pc->d_tile, sizeof(double) * (size_t)std::max<int64_t>(toff.back(), 1)) != hipSuccess) {
         set_error("block Jacobi: out of device memory for %lld tile entries", (long long)toff.back()); rc = KRYST_ERR_HIP;
     }
-    pc->bj_ptr_h = std::move(ptr); pc->bj_idx_h = std::move(idx);
+    pc->ptr_h = std::move(ptr); pc->idx_h = std::move(idx);
     if (rc == KRYST_OK) rc = bj_setup_run(pc, bmax);
     if (rc != KRYST_OK) { kryst_pc_destroy(pc); return rc; }
     *out = pc;
@@ -343,13 +348,11 @@ int32_t kryst_pc_block_jacobi_uniform(kryst_csr_t a, int32_t bsize, kryst_pc_t* 
     }
     const int64_t n = a->nrows;
     KR_HIP(hipSetDevice(a->ctx->device));
-    kryst_pc_t pc = new kryst_pc_s();
-    pc->ctx = a->ctx; pc->kind = KR_PC_BLOCK_JACOBI; pc->a = a; pc->n = n;
-    pc->bj_bsize = bsize; pc->bj_nblk = (n + bsize - 1) / bsize; pc->bj_uncovered = 0;
-    const int64_t last = n - (pc->bj_nblk - 1) * bsize;                    // rows of the last block
-    const int64_t entries = pc->bj_nblk > 0 ? (pc->bj_nblk - 1) * (int64_t)bsize * bsize + last * last : 0;
+    BlockJacobiPc* pc = new BlockJacobiPc(a, bsize, (n + bsize - 1) / bsize, 0);
+    const int64_t last = n - (pc->nblk - 1) * bsize;                    // rows of the last block
+    const int64_t entries = pc->nblk > 0 ? (pc->nblk - 1) * (int64_t)bsize * bsize + last * last : 0;
     int32_t rc = KRYST_OK;
-    if (hipMalloc(&pc->d_bj_tile, sizeof(double) * (size_t)std::max<int64_t>(entries, 1)) != hipSuccess) {
+    if (hipMalloc(&pc->d_tile, sizeof(double) * (size_t)std::max<int64_t>(entries, 1)) != hipSuccess) {
         set_error("block Jacobi: out of device memory for %lld tile entries", (long long)entries); rc = KRYST_ERR_HIP;
     }
     if (rc == KRYST_OK) rc = bj_setup_run(pc, bsize);
@@ -359,22 +362,23 @@ int32_t kryst_pc_block_jacobi_uniform(kryst_csr_t a, int32_t bsize, kryst_pc_t* 
 }
 
 // M as CSR: row g[i] of the block that owns it holds (g[j], Binv[i][j]) for every j of that block, ascending; other rows are empty
-int32_t kryst_pc_block_jacobi_export(kryst_pc_t pc, int64_t* nnz, int64_t* row_ptr, int32_t* col, double* val) {
-    KR_ARG(pc && nnz && pc->kind == KR_PC_BLOCK_JACOBI, "pc_block_jacobi_export");
+int32_t kryst_pc_block_jacobi_export(kryst_pc_t h, int64_t* nnz, int64_t* row_ptr, int32_t* col, double* val) {
+    BlockJacobiPc* pc = pc_cast<BlockJacobiPc>(h);
+    KR_ARG(pc && nnz, "pc_block_jacobi_export");
     KR_ARG(!row_ptr || (col && val), "pc_block_jacobi_export: col / val are NULL");
-    const int64_t n = pc->n, nblk = pc->bj_nblk;
-    const int64_t b = pc->bj_bsize;
-    auto block_lo = [&](int64_t k) { return b > 0 ? k * b : pc->bj_ptr_h[(size_t)k]; };
-    auto block_len = [&](int64_t k) { return b > 0 ? std::min<int64_t>(b, n - k * b) : pc->bj_ptr_h[(size_t)k + 1] - pc->bj_ptr_h[(size_t)k]; };
+    const int64_t n = pc->n, nblk = pc->nblk;
+    const int64_t b = pc->bsize;
+    auto block_lo = [&](int64_t k) { return b > 0 ? k * b : pc->ptr_h[(size_t)k]; };
+    auto block_len = [&](int64_t k) { return b > 0 ? std::min<int64_t>(b, n - k * b) : pc->ptr_h[(size_t)k + 1] - pc->ptr_h[(size_t)k]; };
     // the owning block of every row and the row's position in it (the index-set form keeps an owner stream only when blocks overlap or
     // leave rows uncovered; otherwise every row is in exactly one block)
     std::vector<int32_t> own, posn;
     if (b == 0) {
         own.assign((size_t)n, -1); posn.assign((size_t)n, -1);
         for (int64_t k = 0; k < nblk; ++k)
-            for (int64_t e = pc->bj_ptr_h[(size_t)k]; e < pc->bj_ptr_h[(size_t)k + 1]; ++e) {
-                const int32_t r = pc->bj_idx_h[(size_t)e];
-                own[(size_t)r] = (int32_t)k; posn[(size_t)r] = (int32_t)(e - pc->bj_ptr_h[(size_t)k]);   // the last block wins
+            for (int64_t e = pc->ptr_h[(size_t)k]; e < pc->ptr_h[(size_t)k + 1]; ++e) {
+                const int32_t r = pc->idx_h[(size_t)e];
+                own[(size_t)r] = (int32_t)k; posn[(size_t)r] = (int32_t)(e - pc->ptr_h[(size_t)k]);   // the last block wins
             }
     }
     auto owner = [&](int64_t r) -> int64_t { return b > 0 ? r / b : (int64_t)own[(size_t)r]; };
@@ -387,7 +391,7 @@ int32_t kryst_pc_block_jacobi_export(kryst_pc_t pc, int64_t* nnz, int64_t* row_p
     std::vector<double> tiles((size_t)toff.back());
     KR_HIP(hipSetDevice(pc->ctx->device));
     if (!tiles.empty())
-        KR_HIP(hipMemcpyAsync(tiles.data(), pc->d_bj_tile, sizeof(double) * tiles.size(), hipMemcpyDeviceToHost, pc->ctx->s_main));
+        KR_HIP(hipMemcpyAsync(tiles.data(), pc->d_tile, sizeof(double) * tiles.size(), hipMemcpyDeviceToHost, pc->ctx->s_main));
     KR_HIP(hipStreamSynchronize(pc->ctx->s_main));
     int64_t e = 0;
     row_ptr[0] = 0;
@@ -397,7 +401,7 @@ int32_t kryst_pc_block_jacobi_export(kryst_pc_t pc, int64_t* nnz, int64_t* row_p
             const int64_t lo = block_lo(k), bk = block_len(k);
             const int64_t i = b > 0 ? r - lo : posn[(size_t)r];
             for (int64_t j = 0; j < bk; ++j, ++e) {
-                col[e] = b > 0 ? (int32_t)(lo + j) : pc->bj_idx_h[(size_t)(lo + j)];
+                col[e] = b > 0 ? (int32_t)(lo + j) : pc->idx_h[(size_t)(lo + j)];
                 val[e] = tiles[(size_t)(toff[(size_t)k] + j * bk + i)];
             }
         }

@@ -131,4 +131,13 @@ inline int32_t launch_ew(kryst_ctx_t ctx, const Op& op, int64_t n, const int* do
     return launch_ew_gated(ctx, op, n, GateDone{done});
 }
 
+// used by amg.hip (a smoothed-aggregation apply starts from z = 0) and by pc_apply_dev_fresh (precond.hip)
+struct AmgSetOp {                    // z[i] = src ? src[i] : 0.0  (a fresh z for the apply)
+    static constexpr int NQ = 0; static constexpr const char* TAG = "AmgSet";
+    const double* src; double* z;
+    __device__ __forceinline__ void pair(int64_t i, bool, bool, double (&)[1]) const {
+        if (src) { const d2 v = ld2(src, i); st2(z, i, v.a, v.b); } else st2(z, i, 0.0, 0.0);
+    }
+};
+
 }  // namespace kr

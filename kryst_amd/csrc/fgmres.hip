@@ -275,8 +275,8 @@ int32_t fgmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32_t 
     KR_ARG(p->max_iters >= 0, "solve: max_iters < 0");
     KR_ARG(orthog == 0 || orthog == 1, "fgmres: orthog (0 Classical, 1 Modified)");
     KR_HIP(hipSetDevice(ctx->device));
-    kryst_pc_s pcl; kryst_pc_t pc = nullptr;
-    if (io.pc && io.pc->kind != KR_PC_IDENTITY) { KR_ARG(io.pc->ctx == ctx, "solve: preconditioner context"); pcl = *io.pc; if (pcl.n < 0) pcl.n = n; pc = &pcl; }
+    const kryst_pc_t pc = io.pc && io.pc->kind != KR_PC_IDENTITY ? io.pc : nullptr;
+    KR_ARG(!pc || pc->ctx == ctx, "solve: preconditioner context");
     const int64_t max_iters = p->max_iters;
     const int R = (int)std::min<int64_t>(p->restart, std::max<int64_t>(max_iters, 1));    // no cycle is ever longer than this
     Workspace ws(ctx, n);
@@ -320,7 +320,7 @@ int32_t fgmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32_t 
         for (int j = 0; j < m; ++j) {                                                             // :207
             hipLaunchKernelGGL(fg_gate_kernel, dim3(1), dim3(1), 0, ctx->s_main, st, fs, d_gate);
             KR_HIP(hipGetLastError());
-            if (pc) { rc = pc_apply_dev_fresh(pc, V[j], Z[j], d_gate, V[j]); if (rc) return rc; }             // :209-212
+            if (pc) { rc = pc_apply_dev_fresh(pc, n, V[j], Z[j], d_gate, V[j]); if (rc) return rc; }             // :209-212
             KR_TRY(launch_spmv(a, Z[j], w, 0, nullptr, d_gate));                                  // :214-215
             // all h_col[i] = (w, v_i) from the unmodified w (:220-222 / :231-233)
             for (int i0 = 0; i0 <= j; i0 += 8) {

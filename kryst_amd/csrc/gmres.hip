@@ -214,8 +214,8 @@ int32_t gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io) {
     a->halo_started_for = nullptr;            // (csr.h: an early halo start belongs to the CG / PCG solve that made it)
     KR_ARG(p->max_iters >= 0, "solve: max_iters < 0");
     KR_HIP(hipSetDevice(ctx->device));
-    kryst_pc_s pcl; kryst_pc_t pc = nullptr;
-    if (io.pc) { KR_ARG(io.pc->ctx == ctx, "solve: preconditioner context"); pcl = *io.pc; if (pcl.n < 0) pcl.n = n; pc = &pcl; }
+    const kryst_pc_t pc = io.pc;
+    KR_ARG(!pc || pc->ctx == ctx, "solve: preconditioner context");
     const int side = pc ? p->precond_side : 0;        // `match (self.preconditioning, pc)`: anything else takes the `_` arm
     // side 3 -- a LABELLED EXTENSION, not in the reference: textbook left preconditioning (Arnoldi on M^-1 A from M^-1 r0 / ||M^-1 r0||,
     // Gram-Schmidt against V, in-cycle test on the preconditioned residual, cycle-end test on the true one; oracle: kro_gmres side 3).
@@ -261,20 +261,20 @@ int32_t gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io) {
     for (int64_t outer = 0; outer < n_outer; ++outer) {                                           // :234
         // ---- cycle start
         if (side == 3) {                                                                          // extension: v0 = M^-1 r0 / ||M^-1 r0||
-            rc = pc_apply_dev_fresh(pc, r0, z, done, nullptr); if (rc) return rc;
+            rc = pc_apply_dev_fresh(pc, n, r0, z, done, nullptr); if (rc) return rc;
             KR_TRY(launch_ew(ctx, DotOneOp{z, z}, n, done));
             KR_TRY((reduce_then<1>(ctx, nt, ws.red, GmCycleLogic{lc, P, 2})));
             KR_TRY(launch_ew(ctx, DivOp{&P.gs->r0_norm, z, V[0]}, n, done));
         } else if (side == 2) {                                                                   // :248-260
-            rc = pc_apply_dev_fresh(pc, r0, z, done, nullptr); if (rc) return rc;
+            rc = pc_apply_dev_fresh(pc, n, r0, z, done, nullptr); if (rc) return rc;
             KR_TRY(launch_ew(ctx, DotOneOp{z, z}, n, done));
             KR_TRY((reduce_then<1>(ctx, nt, ws.red, GmCycleLogic{lc, P, 1})));
             KR_TRY(launch_ew(ctx, DivOp{&P.gs->r0_norm, z, V[0]}, n, done));
-            rc = pc_apply_dev_fresh(pc, V[0], Z[0], done, nullptr); if (rc) return rc;
+            rc = pc_apply_dev_fresh(pc, n, V[0], Z[0], done, nullptr); if (rc) return rc;
         } else {
             KR_TRY(logic_only(ctx, ws.red, GmCycleLogic{lc, P, 0}));
             KR_TRY(launch_ew(ctx, DivOp{&P.gs->r0_norm, r0, V[0]}, n, done));                     // :242 / :263
-            if (side == 1) { rc = pc_apply_dev_fresh(pc, V[0], Z[0], done, nullptr); if (rc) return rc; }       // :244-246
+            if (side == 1) { rc = pc_apply_dev_fresh(pc, n, V[0], Z[0], done, nullptr); if (rc) return rc; }       // :244-246
         }
         // ---- Arnoldi loop (:276-355); everything is gated on done || cyc_stop
         for (int j = 0; j < R; ++j) {
@@ -284,16 +284,16 @@ int32_t gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io) {
             double* zz; const std::vector<double*>& B = (side == 1) ? Z : V;
             if (side == 1) {                                                                      // :281-284
                 KR_TRY(launch_spmv(a, V[j], w, 0, nullptr, d_gate));
-                rc = pc_apply_dev_fresh(pc, w, z, d_gate, nullptr); if (rc) return rc;
+                rc = pc_apply_dev_fresh(pc, n, w, z, d_gate, nullptr); if (rc) return rc;
                 zz = z;
                 KR_TRY(launch_iter(ctx, DotOneOp{zz, B[0]}, n, st, gs));
             } else if (side == 3) {                                                               // extension: z = M^-1 A v_j against V
                 KR_TRY(launch_spmv(a, V[j], w, 0, nullptr, d_gate));
-                rc = pc_apply_dev_fresh(pc, w, z, d_gate, nullptr); if (rc) return rc;
+                rc = pc_apply_dev_fresh(pc, n, w, z, d_gate, nullptr); if (rc) return rc;
                 zz = z;
                 KR_TRY(launch_iter(ctx, DotOneOp{zz, B[0]}, n, st, gs));
             } else if (side == 2) {                                                               // :311-317
-                rc = pc_apply_dev_fresh(pc, V[j], w, d_gate, nullptr); if (rc) return rc;
+                rc = pc_apply_dev_fresh(pc, n, V[j], w, d_gate, nullptr); if (rc) return rc;
                 KR_TRY(launch_spmv(a, w, z, 1, V[0], d_gate));                                    // + (w2, V[0])
                 zz = z;
             } else {                                                                              // arnoldi :79-81
@@ -315,7 +315,7 @@ int32_t gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io) {
             if (side == 2) {
                 hipLaunchKernelGGL(gate_kernel, dim3(1), dim3(1), 0, ctx->s_main, st, gs, d_gate);
                 KR_HIP(hipGetLastError());
-                rc = pc_apply_dev_fresh(pc, V[j + 1], Z[j + 1], d_gate, nullptr); if (rc) return rc;
+                rc = pc_apply_dev_fresh(pc, n, V[j + 1], Z[j + 1], d_gate, nullptr); if (rc) return rc;
             }
         }
         // ---- cycle end (:357-398)

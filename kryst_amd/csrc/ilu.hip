@@ -140,6 +140,17 @@ struct IluData {
     int64_t n = 0;
 };
 
+struct IluPc final : kryst_pc_s {
+    static constexpr int KIND = KR_PC_ILU;
+    IluData d;
+    explicit IluPc(kryst_csr_t a_) : kryst_pc_s(a_->ctx, KIND, a_, a_->nrows) { d.n = a_->nrows; }
+    ~IluPc() override;
+    int32_t apply(int64_t nv, const double* r, double* z, const int* done) override;
+    int32_t health() override;
+    bool fell_back() override;
+    bool check_after_apply() const override;               // the wavefront forms wait for neighbour workgroups (tri_wave.h) and may give up
+};
+
 // forward:  y[i] = r[i] - sum l_ij y[j]            (ilu.rs:107-113, ilup.rs:143-149)
 // backward: z[i] = (y[i] - sum u_ij z[j]) / d_i     (ilu.rs:115-119 with d = 1, ilup.rs:151-165)
 // All level kernels work on LEVEL-PERMUTED vectors (`in`, `out` indexed by the level-order position p; the factor's column
@@ -1154,9 +1165,8 @@ static bool takes_quad_form(const IluData* D) {
     return env_int("KRYST_ILU_WAVE", default_wave_form(nb)) >= 2 && D->GL.d_blocked && D->GU.d_blocked;
 }
 
-int32_t ilu_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done) {
-    IluData* D = reinterpret_cast<IluData*>(pc->d_work);
-    kryst_ctx_t ctx = pc->ctx;
+int32_t IluPc::apply(int64_t, const double* r, double* z, const int* done) {
+    IluData* D = &d;
     if (D->n == 0) return KRYST_OK;
     if (takes_quad_form(D) && env_int("KRYST_ILU_GRAPH", 0) == 0 && env_int("KRYST_ILU_DIRECT_ARGS", 1) != 0) {
         // launched directly: the caller's vectors, the `done` flag and the apply's number travel as kernel arguments (tri_quad.h: TriDirect)
@@ -1191,9 +1201,9 @@ int32_t ilu_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done
 
 // After a stream synchronisation: has the wavefront solve given up during an apply since the last check?  If so the
 // preconditioner switches to the plane kernels for good (the captured graph is dropped) and the caller must repeat the work.
-int32_t ilu_health(kryst_pc_t pc) {
-    IluData* D = reinterpret_cast<IluData*>(pc->d_work);
-    if (!D || !D->h_gave_up || *(volatile int32_t*)D->h_gave_up == 0) return KRYST_OK;
+int32_t IluPc::health() {
+    IluData* D = &d;
+    if (!D->h_gave_up || *(volatile int32_t*)D->h_gave_up == 0) return KRYST_OK;
     *(volatile int32_t*)D->h_gave_up = 0;
     D->safe = true; D->fell_back = true;
     if (D->exec) { (void)hipGraphExecDestroy(D->exec); D->exec = nullptr; }
@@ -1202,26 +1212,19 @@ int32_t ilu_health(kryst_pc_t pc) {
               "order?); its result was discarded and this preconditioner now uses the level-per-launch plane kernels");
     return KRYST_SOLVE_ERROR;
 }
-bool ilu_fell_back(kryst_pc_t pc) {
-    IluData* D = reinterpret_cast<IluData*>(pc->d_work);
-    if (!D || !D->fell_back) return false;
-    D->fell_back = false;
+bool IluPc::fell_back() {
+    if (!d.fell_back) return false;
+    d.fell_back = false;
     return true;
 }
-bool ilu_is_wavefront(kryst_pc_t pc) {
-    IluData* D = reinterpret_cast<IluData*>(pc->d_work);
-    return D && ((D->GL.ok && D->GU.ok && !D->safe) || box_takes_wavefront(D));
-}
+bool IluPc::check_after_apply() const { return (d.GL.ok && d.GU.ok && !d.safe) || box_takes_wavefront(&d); }
 
-void ilu_free(kryst_pc_t pc) {
-    if (pc->kind != KR_PC_ILU || !pc->d_work) return;
-    IluData* D = reinterpret_cast<IluData*>(pc->d_work);
+IluPc::~IluPc() {
+    IluData* D = &d;
     if (D->h_gave_up) (void)hipHostFree(D->h_gave_up);
     if (D->exec) (void)hipGraphExecDestroy(D->exec);
     if (D->graph) (void)hipGraphDestroy(D->graph);
     D->L.free_all(); D->U.free_all(); D->GL.free_all(); D->GU.free_all(); D->BL.free_all(); D->BU.free_all(); (void)pool_free(D->d_args); (void)pool_free(D->d_flags); (void)pool_free(D->d_y); (void)pool_free(D->d_rL); (void)pool_free(D->d_yU); (void)pool_free(D->d_zU); (void)pool_free(D->d_mapLU);
-    delete D;
-    pc->d_work = nullptr;
 }
 
 // Every device initialisation of a preconditioner is issued on the context's compute stream and waited for.  That stream is
@@ -1604,17 +1607,14 @@ static int32_t finish_ilu_device(kryst_pc_t pc, IluData* D) {
 
 // shared tail of every host-side ILU-family setup: recognise a structured grid or level-order both factors, then hand out the
 // preconditioner object
-static int32_t finish_ilu_pc(kryst_csr_t a, int mode, bool divide, const FlatRows& le, const FlatRows& ue,
+static int32_t finish_ilu_pc(kryst_csr_t a, const FlatRows& le, const FlatRows& ue,
                              const hvec<double>& dg, kryst_pc_t* out) {
     kryst_ctx_t ctx = a->ctx;
     tl_setup_stream = ctx->s_main;
     const int64_t n = a->nrows;
     hvec<double> ones((size_t)n, 1.0);
-    kryst_pc_t pc = new kryst_pc_s();
-    pc->ctx = ctx; pc->kind = KR_PC_ILU; pc->a = a; pc->n = n; pc->ilu_mode = mode; pc->divide_diag = divide;
-    IluData* D = new IluData();
-    D->n = n;
-    pc->d_work = reinterpret_cast<double*>(D);
+    IluPc* pc = new IluPc(a);
+    IluData* D = &pc->d;
     // structured-grid factors take the wavefront kernel; everything else is level-ordered
     int32_t rc = build_grid(n, le, ones, true, &D->GL);
     if (rc == KRYST_OK) rc = build_grid(n, ue, dg, false, &D->GU);
@@ -1819,12 +1819,8 @@ static int32_t grid_setup_on_device(kryst_csr_t a, int mode, kryst_pc_t* out) {
     KR_HIP(hipStreamSynchronize(ctx->s_main));
     if (reject) return KRYST_OK;                                           // bands that wrap around line ends: the host path (level-ordered)
     // ---- the preconditioner object with its natural-order factor streams
-    kryst_pc_t pc = new kryst_pc_s();
-    const bool divide = mode != KRYST_ILU_KRYST_COMPAT;
-    pc->ctx = ctx; pc->kind = KR_PC_ILU; pc->a = a; pc->n = n; pc->ilu_mode = mode; pc->divide_diag = divide;
-    IluData* D = new IluData();
-    D->n = n;
-    pc->d_work = reinterpret_cast<double*>(D);
+    IluPc* pc = new IluPc(a);
+    IluData* D = &pc->d;
     int32_t rc = KRYST_OK;
     for (double** pp : {&D->GL.d_c1, &D->GL.d_c2, &D->GL.d_c3, &D->GU.d_c1, &D->GU.d_c2, &D->GU.d_c3, &D->GU.d_diag})
         if (rc == KRYST_OK && pool_malloc(pp, vb) != hipSuccess) { set_error("hipMalloc failed"); rc = KRYST_ERR_HIP; }
@@ -2293,11 +2289,8 @@ static int32_t general_setup_on_device(kryst_csr_t a, int mode, kryst_pc_t* out)
         return KRYST_SOLVE_ERROR;
     }
     lap("factor values, kept entries");
-    kryst_pc_t pc = new kryst_pc_s();
-    pc->ctx = ctx; pc->kind = KR_PC_ILU; pc->a = a; pc->n = n; pc->ilu_mode = mode; pc->divide_diag = divide;
-    IluData* D = new IluData();
-    D->n = n;
-    pc->d_work = reinterpret_cast<double*>(D);
+    IluPc* pc = new IluPc(a);
+    IluData* D = &pc->d;
     int32_t rc = KRYST_OK;
     if (box_ni > 0) {
         // ---- box stencil: 13 natural-order coefficient streams per factor, written by one kernel (no level machinery at all)
@@ -2503,7 +2496,7 @@ extern "C" int32_t kryst_pc_ilu0(kryst_csr_t a, int32_t mode, kryst_pc_t* out) {
         }
     });
     if (verbose) { fprintf(stderr, "[kryst ilu] split into L / U rows %.0f ms\n", ms_since(t_phase)); t_phase = now(); }
-    const int32_t rc = finish_ilu_pc(a, mode, divide, le, ue, dg, out);
+    const int32_t rc = finish_ilu_pc(a, le, ue, dg, out);
     if (verbose) fprintf(stderr, "[kryst ilu] device structures %.0f ms\n", ms_since(t_phase));
     return rc;
 }
@@ -2549,7 +2542,7 @@ static int32_t ilup_setup(kryst_csr_t a, int32_t fill, kryst_pc_t* out) {
     catch (const std::bad_alloc&) { hrc = 2; }
     if (hrc == 1) { set_error("ILUP: zero diagonal in U at row %lld", zero_col); return KRYST_SOLVE_ERROR; }
     if (hrc != 0) { set_error("ILUP: out of host memory during the elimination"); return KRYST_ERR_ARG; }
-    const int32_t rc = finish_ilu_pc(a, 10 + fill, true, le, ue, dg, out);
+    const int32_t rc = finish_ilu_pc(a, le, ue, dg, out);
     lap("device structures");
     // ~1 GB of host arrays at 128^3: unmapping them takes 60-70 ms, which the caller need not wait for
     struct Bundle { std::shared_ptr<void> scratch; FlatRows le, ue; hvec<int64_t> rp; hvec<int32_t> col; hvec<double> val; hvec<double> dg; };
@@ -2572,7 +2565,7 @@ extern "C" int32_t kryst_pc_ilut(kryst_csr_t a, int32_t fill, double droptol, kr
     FlatRows le, ue; hvec<double> dg;
     try { host_ilut_rows(n, rp.data(), col.data(), val.data(), fill, droptol, le, ue, dg); }     // (host_factor.cpp; ilut.rs:80-150)
     catch (const std::bad_alloc&) { set_error("ILUT: out of host memory"); return KRYST_ERR_ARG; }
-    return finish_ilu_pc(a, 100, true, le, ue, dg, out);
+    return finish_ilu_pc(a, le, ue, dg, out);
 }
 
 // ---- the host-side factorisations on plain host arrays (kryst_hip.h: no device, no context): what kryst_pc_ilup / kryst_pc_ilut run between the
@@ -2650,8 +2643,9 @@ extern "C" int32_t kryst_host_levels(int64_t n, const int64_t* ptr, const int32_
 //   info[12] stored entries of L + U (level-ordered forms)
 extern "C" int32_t kryst_pc_ilu_info(kryst_pc_t pc, int64_t* info, int32_t count) {
     KR_ARG(pc && info && count >= 13, "pc_ilu_info: need room for 13 values");
-    KR_ARG(pc->kind == KR_PC_ILU && pc->d_work, "pc_ilu_info: not an ILU-family preconditioner");
-    IluData* D = reinterpret_cast<IluData*>(pc->d_work);
+    IluPc* ilu = pc_cast<IluPc>(pc);
+    KR_ARG(ilu, "pc_ilu_info: not an ILU-family preconditioner");
+    IluData* D = &ilu->d;
     kryst_ctx_t ctx = pc->ctx;
     for (int i = 0; i < count; ++i) info[i] = 0;
     if (D->BL.ok && D->BU.ok) {                                            // box stencil (round 4): 4 = one launch per hyperplane i + 2 j + 4 k

@@ -507,8 +507,8 @@ int32_t pca_gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32
     }
     a->halo_started_for = nullptr;
     KR_HIP(hipSetDevice(ctx->device));
-    kryst_pc_s pcl; kryst_pc_t pc = nullptr;
-    if (io.pc && p->precond_side == 2) { KR_ARG(io.pc->ctx == ctx, "solve: preconditioner context"); pcl = *io.pc; if (pcl.n < 0) pcl.n = n; pc = &pcl; }
+    const kryst_pc_t pc = io.pc && p->precond_side == 2 ? io.pc : nullptr;
+    KR_ARG(!pc || pc->ctx == ctx, "solve: preconditioner context");
     const int S = textbook ? block_size : 1;
 
     Workspace ws(ctx, n);
@@ -578,7 +578,7 @@ int32_t pca_gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32
                 hipLaunchKernelGGL(pg_gate_kernel, dim3(1), dim3(1), 0, ctx->s_main, done, &P.gs->cyc_stop, d_gate);
                 KR_HIP(hipGetLastError());
                 KR_TRY(launch_spmv(a, V[j], w, 0, nullptr, d_gate));                                             // :151 / :163
-                if (pc) { rc = pc_apply_dev_fresh(pc, w, z, d_gate, nullptr); if (rc) return rc; }              // :152-156
+                if (pc) { rc = pc_apply_dev_fresh(pc, n, w, z, d_gate, nullptr); if (rc) return rc; }              // :152-156
                 // (v_i, w) for i = 0..j (:174-179) and (w, w) (:225) in one pass
                 PgPass ps{};
                 ps.q = d_qptr; ps.nb = j + 1; ps.qx = wsel; ps.w = d_qptr + R + 1; ps.s = 1; ps.dots = 1; ps.n = n;
@@ -609,7 +609,7 @@ int32_t pca_gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32
                 for (int cc = 0; cc < s_eff; ++cc) {
                     const double* in = (cc == 0) ? V[j] : u;
                     const double* zin = in;
-                    if (pc) { rc = pc_apply_dev_fresh(pc, in, z, done, nullptr); if (rc) return rc; zin = z; }
+                    if (pc) { rc = pc_apply_dev_fresh(pc, n, in, z, done, nullptr); if (rc) return rc; zin = z; }
                     KR_TRY(launch_spmv(a, zin, W[cc], 0, nullptr, done));
                     KR_TRY(launch_ew(ctx, DotOneOp{W[cc], W[cc]}, n, done));
                     KR_TRY((reduce_then<1>(ctx, nt, ws.red, PgNuLogic{lc, P, cc})));
@@ -639,7 +639,7 @@ int32_t pca_gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32
             KR_TRY(pg_logic(ctx, ws.red, PgBackLogic{lc, P, 1}));
             KR_TRY(launch_ew(ctx, PgUpdateOp{P.gs, P.y, d_qptr, nullptr, tmp, 1}, n, done));
             const double* add = tmp;
-            if (pc) { rc = pc_apply_dev_fresh(pc, tmp, z, done, nullptr); if (rc) return rc; add = z; }
+            if (pc) { rc = pc_apply_dev_fresh(pc, n, tmp, z, done, nullptr); if (rc) return rc; add = z; }
             KR_TRY(launch_ew(ctx, PgAddOp{add, xk}, n, done));
             KR_TRY(residual_dot(a, bv->d, xk, r0, tmp, done));
             KR_TRY((reduce_then<1>(ctx, nt, ws.red, PgCycleEndLogic{lc, P})));

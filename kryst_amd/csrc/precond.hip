@@ -109,48 +109,10 @@ int32_t chebyshev_dev(kryst_csr_t a, const double* r, double* z, double alpha, d
     return KRYST_OK;
 }
 
-int32_t ilu_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done);   // ilu.hip
-void    ilu_free(kryst_pc_t pc);
-int32_t ilu_health(kryst_pc_t pc);
-bool    ilu_fell_back(kryst_pc_t pc);
-bool    ilu_is_wavefront(kryst_pc_t pc);
-int32_t pc_health(kryst_pc_t pc) {
-    if (pc && pc->kind == KR_PC_SOR) return sor_health(pc);
-    return (pc && pc->kind == KR_PC_ILU && pc->d_work) ? ilu_health(pc) : KRYST_OK;
+int32_t pc_apply_dev_fresh(kryst_pc_t pc, int64_t n, const double* r, double* z, const int* done, const double* init) {
+    if (pc->reads_z() && init != z) KR_TRY(launch_ew(pc->ctx, AmgSetOp{init, z}, n, done));
+    return pc_apply_dev(pc, n, r, z, done);
 }
-bool pc_fell_back(kryst_pc_t pc) { return pc && pc->kind == KR_PC_ILU && pc->d_work && ilu_fell_back(pc); }
-
-static int32_t pc_apply_kind(kryst_pc_t pc, const double* r, double* z, const int* done) {
-    kryst_ctx_t ctx = pc->ctx;
-    switch (pc->kind) {
-        case KR_PC_IDENTITY:
-            if (r != z) KR_HIP(hipMemcpyAsync(z, r, sizeof(double) * (size_t)padded(pc->n), hipMemcpyDeviceToDevice, ctx->s_main));
-            return KRYST_OK;
-        case KR_PC_JACOBI: return launch_ew(ctx, JacobiOp{pc->d_inv_diag, r, z}, pc->n, done);
-        case KR_PC_ILU: return ilu_apply_dev(pc, r, z, done);
-        case KR_PC_CHEB_STUB:
-            set_error("Chebyshev preconditioner requires matrix argument; use apply_chebyshev free function.");   // chebyshev.rs:69
-            return KRYST_SOLVE_ERROR;
-        case KR_PC_CHEB:
-            return chebyshev_dev(pc->a, r, z, pc->cheb_alpha, pc->cheb_beta, pc->cheb_degree, pc->d_v0, pc->d_v1, pc->d_v2, done);
-        case KR_PC_SPAI:      // ApproxInv::apply (approxinv.rs:268-298): z_i = sum_j M_ij r_j, ascending j from 0 -- an SpMV with M
-            return launch_spmv(pc->a, r, z, 0, nullptr, done);
-        case KR_PC_BLOCK_JACOBI: return bj_apply_dev(pc, r, z, done);
-        case KR_PC_ASM: return asm_apply_dev(pc, r, z, done);
-        case KR_PC_AMG: return amg_apply_dev(pc, r, z, done);
-        case KR_PC_SOR: return sor_apply_dev(pc, r, z, done);
-        default: set_error("unknown preconditioner kind %d", pc->kind); return KRYST_UNSUPPORTED;
-    }
-}
-int32_t pc_apply_dev(kryst_pc_t pc, const double* r, double* z, const int* done) {
-    const int32_t rc = pc_apply_kind(pc, r, z, done);
-    phase_mark(pc->ctx, KR_PH_PC);
-    return rc;
-}
-
-}  // namespace kr
-
-using namespace kr;
 
 // all device work of a context is ordered on ctx->s_main (a non-blocking stream: the null stream does NOT order with it)
 static int32_t alloc_vec(kryst_ctx_t ctx, double** p, int64_t n) {
@@ -160,23 +122,59 @@ static int32_t alloc_vec(kryst_ctx_t ctx, double** p, int64_t n) {
     return KRYST_OK;
 }
 
+struct IdentityPc final : kryst_pc_s {
+    explicit IdentityPc(kryst_ctx_t c) : kryst_pc_s(c, KR_PC_IDENTITY, nullptr, -1) {}
+    int32_t apply(int64_t nv, const double* r, double* z, const int*) override {
+        if (r != z) KR_HIP(hipMemcpyAsync(z, r, sizeof(double) * (size_t)padded(nv), hipMemcpyDeviceToDevice, ctx->s_main));
+        return KRYST_OK;
+    }
+};
+
+struct JacobiPc final : kryst_pc_s {
+    static constexpr int KIND = KR_PC_JACOBI;
+    double* d_inv_diag = nullptr;
+    explicit JacobiPc(kryst_csr_t a_) : kryst_pc_s(a_->ctx, KIND, a_, a_->nrows) {}
+    ~JacobiPc() override { (void)hipFree(d_inv_diag); }
+    int32_t apply(int64_t, const double* r, double* z, const int* done) override { return launch_ew(ctx, JacobiOp{d_inv_diag, r, z}, n, done); }
+};
+const double* pc_jacobi_inv_diag(kryst_pc_t pc) { JacobiPc* j = pc_cast<JacobiPc>(pc); return j ? j->d_inv_diag : nullptr; }
+
+struct ChebStubPc final : kryst_pc_s {
+    explicit ChebStubPc(kryst_ctx_t c) : kryst_pc_s(c, KR_PC_CHEB_STUB, nullptr, -1) {}
+    int32_t apply(int64_t, const double*, double*, const int*) override {
+        set_error("Chebyshev preconditioner requires matrix argument; use apply_chebyshev free function.");   // chebyshev.rs:69
+        return KRYST_SOLVE_ERROR;
+    }
+};
+
+struct ChebPc final : kryst_pc_s {
+    double alpha, beta; int64_t degree;
+    double* d_v0 = nullptr; double* d_v1 = nullptr; double* d_v2 = nullptr;
+    ChebPc(kryst_csr_t a_, double al, double be, int64_t deg) : kryst_pc_s(a_->ctx, KR_PC_CHEB, a_, a_->nrows), alpha(al), beta(be), degree(deg) {}
+    ~ChebPc() override { (void)hipFree(d_v0); (void)hipFree(d_v1); (void)hipFree(d_v2); }
+    int32_t apply(int64_t, const double* r, double* z, const int* done) override {
+        return chebyshev_dev(a, r, z, alpha, beta, degree, d_v0, d_v1, d_v2, done);
+    }
+};
+
+}  // namespace kr
+
+using namespace kr;
+
 extern "C" {
 
 int32_t kryst_pc_identity(kryst_ctx_t ctx, kryst_pc_t* out) {
     KR_ARG(ctx && out, "pc_identity");
-    kryst_pc_t pc = new kryst_pc_s();
-    pc->ctx = ctx; pc->kind = KR_PC_IDENTITY; pc->n = -1;
-    *out = pc;
+    *out = new IdentityPc(ctx);
     return KRYST_OK;
 }
 
 int32_t kryst_pc_jacobi(kryst_csr_t a, kryst_pc_t* out) {
     KR_ARG(a && out, "pc_jacobi");
     KR_HIP(hipSetDevice(a->ctx->device));
-    kryst_pc_t pc = new kryst_pc_s();
-    pc->ctx = a->ctx; pc->kind = KR_PC_JACOBI; pc->a = a; pc->n = a->nrows;
+    JacobiPc* pc = new JacobiPc(a);
     int32_t rc = alloc_vec(a->ctx, &pc->d_inv_diag, pc->n);
-    if (rc != KRYST_OK) { delete pc; return rc; }
+    if (rc != KRYST_OK) { kryst_pc_destroy(pc); return rc; }
     if (pc->n > 0) {
         hipLaunchKernelGGL(jacobi_setup_kernel, dim3((unsigned)((pc->n + 255) / 256)), dim3(256), 0, a->ctx->s_main,
                            a->d_row_ptr, a->d_col, a->d_val, (int32_t)pc->n, pc->d_inv_diag);
@@ -188,9 +186,8 @@ int32_t kryst_pc_jacobi(kryst_csr_t a, kryst_pc_t* out) {
 
 int32_t kryst_pc_chebyshev_stub(kryst_ctx_t ctx, int32_t degree, kryst_pc_t* out) {
     KR_ARG(ctx && out, "pc_chebyshev_stub");
-    kryst_pc_t pc = new kryst_pc_s();
-    pc->ctx = ctx; pc->kind = KR_PC_CHEB_STUB; pc->cheb_degree = degree; pc->n = -1;
-    *out = pc;
+    (void)degree;                                        // the stub never applies (chebyshev.rs:69)
+    *out = new ChebStubPc(ctx);
     return KRYST_OK;
 }
 
@@ -198,9 +195,7 @@ int32_t kryst_pc_chebyshev(kryst_csr_t a, double alpha, double beta, int32_t deg
     KR_ARG(a && out && degree >= 0, "pc_chebyshev");
     KR_ARG(a->nrows == a->xlen, "pc_chebyshev: square operator required");
     KR_HIP(hipSetDevice(a->ctx->device));
-    kryst_pc_t pc = new kryst_pc_s();
-    pc->ctx = a->ctx; pc->kind = KR_PC_CHEB; pc->a = a; pc->n = a->nrows;
-    pc->cheb_alpha = alpha; pc->cheb_beta = beta; pc->cheb_degree = degree;
+    ChebPc* pc = new ChebPc(a, alpha, beta, degree);
     int32_t rc = alloc_vec(a->ctx, &pc->d_v0, pc->n);
     if (rc == KRYST_OK) rc = alloc_vec(a->ctx, &pc->d_v1, pc->n);
     if (rc == KRYST_OK) rc = alloc_vec(a->ctx, &pc->d_v2, pc->n);
@@ -215,23 +210,14 @@ int32_t kryst_pc_apply(kryst_pc_t pc, kryst_vec_t r, kryst_vec_t z) {
     KR_ARG(r->n == z->n, "pc_apply: length mismatch");
     KR_ARG(pc->n < 0 || pc->n == r->n, "pc_apply: vector length != operator size");
     KR_HIP(hipSetDevice(pc->ctx->device));
-    if (pc->n < 0) {                                     // identity / stub carry no size
-        kryst_pc_s tmp = *pc; tmp.n = r->n;
-        return pc_apply_dev(&tmp, r->d, z->d, nullptr);
-    }
-    KR_TRY(pc_apply_dev(pc, r->d, z->d, nullptr));
-    if (pc->kind == KR_PC_SOR) {                         // a sweep whose grid barrier gave up is an error here, not a vector of NaNs
+    KR_TRY(pc_apply_dev(pc, r->n, r->d, z->d, nullptr));
+    if (pc->check_after_apply()) {
+        // a SOR sweep whose grid barrier gave up is an error here, not a vector of NaNs; the ILU wavefront solve relies on in-order
+        // workgroup dispatch (tri_wave.h): if it gave up, the apply is repeated with the plane kernels (same bits)
         KR_HIP(hipStreamSynchronize(pc->ctx->s_main));
-        return pc_health(pc);
-    }
-    if (pc->kind == KR_PC_ILU && pc->d_work && ilu_is_wavefront(pc)) {
-        // the wavefront solve relies on in-order workgroup dispatch (tri_wave.h): wait, and if it gave up repeat the apply
-        // with the plane kernels (same bits)
-        KR_HIP(hipStreamSynchronize(pc->ctx->s_main));
-        if (pc_health(pc) != KRYST_OK) {
-            (void)pc_fell_back(pc);
-            KR_TRY(pc_apply_dev(pc, r->d, z->d, nullptr));
-        }
+        const int32_t rc = pc_health(pc);
+        if (rc != KRYST_OK && !pc_fell_back(pc)) return rc;
+        if (rc != KRYST_OK) KR_TRY(pc_apply_dev(pc, r->n, r->d, z->d, nullptr));
     }
     return KRYST_OK;
 }
@@ -243,11 +229,11 @@ int32_t kryst_bench_pc_apply(kryst_pc_t pc, kryst_vec_t r, kryst_vec_t z, int32_
     KR_ARG(r->ctx == pc->ctx && z->ctx == pc->ctx && r->n == z->n && pc->n == r->n, "bench_pc_apply: size or context mismatch");
     kryst_ctx_t ctx = pc->ctx;
     KR_HIP(hipSetDevice(ctx->device));
-    KR_TRY(pc_apply_dev(pc, r->d, z->d, nullptr));
+    KR_TRY(pc_apply_dev(pc, r->n, r->d, z->d, nullptr));
     KR_HIP(hipStreamSynchronize(ctx->s_main));
     if (pc_health(pc) != KRYST_OK) { (void)pc_fell_back(pc); }          // measure what the preconditioner now runs
     KR_HIP(hipEventRecord(ctx->tm0, ctx->s_main));
-    for (int k = 0; k < reps; ++k) KR_TRY(pc_apply_dev(pc, r->d, z->d, nullptr));
+    for (int k = 0; k < reps; ++k) KR_TRY(pc_apply_dev(pc, r->n, r->d, z->d, nullptr));
     KR_HIP(hipEventRecord(ctx->tm1, ctx->s_main));
     KR_HIP(hipEventSynchronize(ctx->tm1));
     float ms = 0.f;
@@ -257,26 +243,10 @@ int32_t kryst_bench_pc_apply(kryst_pc_t pc, kryst_vec_t r, kryst_vec_t z, int32_
     return pc_health(pc);
 }
 
-int32_t kryst_pc_approx_inverse(kryst_csr_t m, kryst_pc_t* out) {
-    KR_ARG(m && out, "pc_approx_inverse");
-    KR_ARG(m->nrows == m->xlen, "pc_approx_inverse: the inverse rows must form a square operator");
-    kryst_pc_t pc = new kryst_pc_s();
-    pc->ctx = m->ctx; pc->kind = KR_PC_SPAI; pc->a = m; pc->n = m->nrows;
-    *out = pc;
-    return KRYST_OK;
-}
-
 int32_t kryst_pc_destroy(kryst_pc_t pc) {
     if (!pc) return KRYST_OK;
     (void)hipSetDevice(pc->ctx->device);
     (void)hipStreamSynchronize(pc->ctx->s_main);
-    (void)hipFree(pc->d_inv_diag); (void)hipFree(pc->d_v0); (void)hipFree(pc->d_v1); (void)hipFree(pc->d_v2);
-    ilu_free(pc);
-    bj_free(pc);
-    asm_free(pc);
-    sor_free(pc);
-    amg_free(pc);
-    if (pc->spai_m) kryst_csr_destroy(pc->spai_m);
     delete pc;
     return KRYST_OK;
 }

@@ -45,7 +45,7 @@ struct SolverRun {
     kryst_vec_t bv, xv; SolveIO io; kryst_params_t prm;
     kryst_csr_t a; kryst_ctx_t ctx; int64_t n, nt;
     Workspace ws; LogicCtx lc; const int* done = nullptr; double* xw = nullptr;
-    kryst_pc_s pcl; kryst_pc_t pc = nullptr;
+    kryst_pc_t pc = nullptr;          // applied with the operator's size n: a sizeless preconditioner (Identity, the stub) takes any
     int64_t next_iter = 1;
     LiveMonitor mon;
     SolverRun(kryst_vec_t b, kryst_vec_t x, const SolveIO& io_)
@@ -58,7 +58,7 @@ struct SolverRun {
     int32_t common_begin(int64_t hist_entries, int work_vectors) {
         KR_HIP(hipSetDevice(ctx->device));
         a->halo_started_for = nullptr;        // (an early halo start belongs to ONE solve: work vectors of later solves reuse the addresses)
-        if (io.pc) { pcl = *io.pc; if (pcl.n < 0) pcl.n = n; pc = &pcl; }
+        pc = io.pc;
         KR_TRY(ws.init(hist_entries));
         KR_TRY(ws.reserve(work_vectors + 1));
         lc = ws.lctx(&prm, io.monitor != nullptr);

@@ -604,6 +604,7 @@ struct PcgRun : SolverRun {
     double *r = nullptr, *z = nullptr, *pp = nullptr, *ap = nullptr;
     double* p2 = nullptr;            // the fused form's second direction vector
     bool alias = false, jac = false;
+    const double* inv_diag = nullptr;  // jac: the Jacobi preconditioner's inverse diagonal, fused into the residual update
     bool fuse = false; long long fused_upto = 0;
     int xb = 1; std::vector<double*> ring;           // x in batches (see CgRun)
     bool ringdir = false;
@@ -621,6 +622,7 @@ struct PcgRun : SolverRun {
         KR_TRY(common_begin(prm.max_iters + 2, xb > 1 ? 4 + xb + 1 : fuse ? 5 : 4));              // pcg.rs:117
         alias = !pc || pc->kind == KR_PC_IDENTITY;      // z == r  (pcg.rs:130,186 clone_from / IdentityPC)
         jac = pc && pc->kind == KR_PC_JACOBI;
+        inv_diag = pc_jacobi_inv_diag(pc);
         KR_TRY(ws.vec(&r)); KR_TRY(ws.vec(&pp)); KR_TRY(ws.vec(&ap));
         if (xb > 1) {
             ring.assign((size_t)xb + 1, nullptr);
@@ -630,7 +632,7 @@ struct PcgRun : SolverRun {
         if (alias) z = r; else KR_TRY(ws.vec(&z));
         KR_TRY(launch_spmv(a, xw, ap, 0, nullptr, nullptr));                                      // :119-124
         KR_TRY(launch_ew(ctx, SubDotOp{bv->d, ap, r}, n, nullptr));
-        if (!alias) KR_TRY(pc_apply_dev(pc, r, z, nullptr));                                      // :127-131 (`?`)
+        if (!alias) KR_TRY(pc_apply_dev(pc, n, r, z, nullptr));                                      // :127-131 (`?`)
         KR_HIP(hipMemcpyAsync(pp, z, padded_bytes(n), hipMemcpyDeviceToDevice, ctx->s_main));      // :132
         const double* nq_a = (prm.norm_type == 0) ? z : r;      // Preconditioned: (z,z); Unpreconditioned: (r,r)
         KR_TRY(launch_ew(ctx, DotPairOp{r, z, nq_a, nq_a}, n, nullptr));
@@ -661,11 +663,11 @@ struct PcgRun : SolverRun {
                 if (keep) KR_TRY(launch_ew(ctx, PcgResidualOp<false, true>{&ws.st->alpha, ap, r, z, nullptr, nt_}, n, done));
                 else KR_TRY(launch_ew(ctx, PcgResidualOp<false, false>{&ws.st->alpha, ap, r, z, nullptr, nt_}, n, done));
             } else if (jac) {
-                if (keep) KR_TRY(launch_ew(ctx, PcgResidualOp<true, true>{&ws.st->alpha, ap, r, z, pc->d_inv_diag, nt_}, n, done));
-                else KR_TRY(launch_ew(ctx, PcgResidualOp<true, false>{&ws.st->alpha, ap, r, z, pc->d_inv_diag, nt_}, n, done));
+                if (keep) KR_TRY(launch_ew(ctx, PcgResidualOp<true, true>{&ws.st->alpha, ap, r, z, inv_diag, nt_}, n, done));
+                else KR_TRY(launch_ew(ctx, PcgResidualOp<true, false>{&ws.st->alpha, ap, r, z, inv_diag, nt_}, n, done));
             } else {
                 KR_TRY(launch_ew(ctx, CgResidual0Op{&ws.st->alpha, ap, r}, n, done));             // :179-181
-                KR_TRY(pc_apply_dev(pc, r, z, done));                                             // :183-187
+                KR_TRY(pc_apply_dev(pc, n, r, z, done));                                             // :183-187
                 const double* nq_a = (nt_ == 0) ? z : r;
                 KR_TRY(launch_ew(ctx, DotPairOp{r, z, nq_a, nq_a}, n, done));                     // :188-195
             }
@@ -689,11 +691,11 @@ struct PcgRun : SolverRun {
         if (alias) {
             KR_TRY(launch_ew(ctx, PcgUpdateOp<false>{&ws.st->alpha, pp, ap, xw, r, z, nullptr, nt_}, n, done));
         } else if (jac) {
-            if (keep_in_cache(n)) KR_TRY(launch_ew(ctx, PcgUpdateOp<true, true>{&ws.st->alpha, pp, ap, xw, r, z, pc->d_inv_diag, nt_}, n, done));
-            else KR_TRY(launch_ew(ctx, PcgUpdateOp<true, false>{&ws.st->alpha, pp, ap, xw, r, z, pc->d_inv_diag, nt_}, n, done));
+            if (keep_in_cache(n)) KR_TRY(launch_ew(ctx, PcgUpdateOp<true, true>{&ws.st->alpha, pp, ap, xw, r, z, inv_diag, nt_}, n, done));
+            else KR_TRY(launch_ew(ctx, PcgUpdateOp<true, false>{&ws.st->alpha, pp, ap, xw, r, z, inv_diag, nt_}, n, done));
         } else {
             KR_TRY(launch_ew(ctx, CgUpdate0{&ws.st->alpha, pp, ap, xw, r}, n, done));             // :175-181
-            KR_TRY(pc_apply_dev(pc, r, z, done));                                                 // :183-187
+            KR_TRY(pc_apply_dev(pc, n, r, z, done));                                                 // :183-187
             const double* nq_a = (nt_ == 0) ? z : r;
             KR_TRY(launch_ew(ctx, DotPairOp{r, z, nq_a, nq_a}, n, done));                         // :188-195
         }
@@ -845,12 +847,12 @@ struct BicgRun : SolverRun {
         const DevState* st = ws.st;
         if (keep_in_cache(n)) KR_TRY(launch_ew(ctx, BicgPOp<true>{st, r, v, pp}, n, done));
         else KR_TRY(launch_ew(ctx, BicgPOp<false>{st, r, v, pp}, n, done));                                   // :126-142
-        if (pc) { KR_TRY(pc_apply_dev_fresh(pc, pp, ph, done, nullptr)); KR_TRY(launch_spmv(a, ph, v, 1, rhat, done)); }
+        if (pc) { KR_TRY(pc_apply_dev_fresh(pc, n, pp, ph, done, nullptr)); KR_TRY(launch_spmv(a, ph, v, 1, rhat, done)); }
         else KR_TRY(launch_spmv(a, pp, v, 1, rhat, done));                                        // :144-146 + (rhat,v)
         KR_TRY((reduce_then<1>(ctx, nt, ws.red, BicgAlphaLogic{lc})));
         KR_TRY(launch_ew(ctx, BicgSOp{st, r, v, s}, n, done));                                    // :166-188
         KR_TRY((reduce_then<1>(ctx, nt, ws.red, BicgSLogic{lc})));
-        if (pc) { KR_TRY(pc_apply_dev_fresh(pc, s, sh, done, nullptr)); KR_TRY(launch_spmv(a, sh, t, 2, s, done)); }
+        if (pc) { KR_TRY(pc_apply_dev_fresh(pc, n, s, sh, done, nullptr)); KR_TRY(launch_spmv(a, sh, t, 2, s, done)); }
         else KR_TRY(launch_spmv(a, s, t, 2, s, done));                                            // :208-209 + (t,s),(t,t)
         KR_TRY((reduce_then<2>(ctx, nt, ws.red, BicgOmegaLogic{lc})));
         if (keep_in_cache(n)) KR_TRY(launch_ew_gated(ctx, BicgXROp<true>{st, pc ? ph : pp, pc ? sh : s, s, t, rhat, xw, r}, n, GateEarly{st}));

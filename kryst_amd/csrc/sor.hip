@@ -120,61 +120,73 @@ __global__ __launch_bounds__(KR_SOR_T) void sor_sweep_kernel(const int32_t* __re
     }
 }
 
-static void sor_launch(kryst_pc_t pc, bool forward, bool eis, const double* x, double* y, const int* done) {
-    kryst_csr_t a = pc->a;
+// the parameters, 1 / (a_ii + fshift), and per sweep direction (0 forward, 1 backward) the rows ordered by dependency level of the
+// (coloured) sweep order with the level offsets
+struct SorPc final : kryst_pc_s {
+    static constexpr int KIND = KR_PC_SOR;
+    double omega; int32_t its, sym;
+    double* d_inv_diag = nullptr;
+    int32_t* d_rows[2] = {nullptr, nullptr}; int32_t* d_off[2] = {nullptr, nullptr};
+    int32_t groups[2] = {0, 0}; uint32_t grid[2] = {1, 1};
+    int32_t* d_pos = nullptr;         // coloured order: the position of every row, or nullptr (position = row)
+    int32_t* d_ent = nullptr;         // coloured order: every row's entries in ascending position, or nullptr (the stored order)
+    uint32_t* d_sync = nullptr;       // the arrival counter of the sweep kernel's grid barrier, zeroed in front of every launch
+    uint32_t* h_gave_up = nullptr; uint32_t* d_gave_up = nullptr;   // mapped host word: a barrier's patience ran out (sticky until read)
+    SorPc(kryst_csr_t a_, double omega_, int32_t its_, int32_t sym_) : kryst_pc_s(a_->ctx, KIND, a_, a_->nrows), omega(omega_), its(its_), sym(sym_) {}
+    ~SorPc() override {
+        for (int d = 0; d < 2; ++d) { (void)pool_free(d_rows[d]); (void)pool_free(d_off[d]); }
+        (void)pool_free(d_pos); (void)pool_free(d_ent);
+        (void)hipFree(d_inv_diag); (void)hipFree(d_sync);
+        if (h_gave_up) (void)hipHostFree(h_gave_up);
+    }
+    void launch(bool forward, bool eis, const double* x, double* y, const int* done);
+    int32_t apply(int64_t nv, const double* x, double* y, const int* done) override;
+    int32_t health() override;        // after the stream has been synchronised: did a sweep since the last call give up?
+    bool check_after_apply() const override { return true; }
+};
+
+void SorPc::launch(bool forward, bool eis, const double* x, double* y, const int* done) {
     const int d = forward ? 0 : 1;
     auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(pc->sor_grid[d]), dim3(KR_SOR_T), 0, pc->ctx->s_main, (const int32_t*)a->d_row_ptr, (const int32_t*)a->d_col,
-                           (const double*)a->d_val, (const double*)pc->d_inv_diag, (const int32_t*)pc->d_sor_pos, (const int32_t*)pc->d_sor_ent, (const int32_t*)pc->d_sor_rows[d],
-                           (const int32_t*)pc->d_sor_off[d], pc->sor_groups[d], pc->sor_omega, x, y, pc->d_sor_sync, pc->d_sor_gave_up, done);
+        hipLaunchKernelGGL(kernel, dim3(grid[d]), dim3(KR_SOR_T), 0, ctx->s_main, (const int32_t*)a->d_row_ptr, (const int32_t*)a->d_col,
+                           (const double*)a->d_val, (const double*)d_inv_diag, (const int32_t*)d_pos, (const int32_t*)d_ent, (const int32_t*)d_rows[d],
+                           (const int32_t*)d_off[d], groups[d], omega, x, y, d_sync, d_gave_up, done);
     };
     if (forward) { if (eis) go(sor_sweep_kernel<true, true>); else go(sor_sweep_kernel<true, false>); }
     else { if (eis) go(sor_sweep_kernel<false, true>); else go(sor_sweep_kernel<false, false>); }
 }
 
-int32_t sor_apply_dev(kryst_pc_t pc, const double* x, double* y, const int* done) {
-    kryst_ctx_t ctx = pc->ctx;
+int32_t SorPc::apply(int64_t, const double* x, double* y, const int* done) {
     KR_ARG(x != y, "SOR apply: input and output must be different vectors");
-    const int64_t n = pc->n;
     if (n == 0) return KRYST_OK;
-    const bool lower = (pc->sor_sym & KR_SOR_LOWER) != 0, upper = (pc->sor_sym & KR_SOR_UPPER) != 0, eis = (pc->sor_sym & KR_SOR_EISENSTAT) != 0;
-    const bool sweeps = pc->sor_its > 0 && (lower || upper);
+    const bool lower = (sym & KR_SOR_LOWER) != 0, upper = (sym & KR_SOR_UPPER) != 0, eis = (sym & KR_SOR_EISENSTAT) != 0;
+    const bool sweeps = its > 0 && (lower || upper);
     // y = +0.0 (sor.rs:127).  A forward sweep reads no y it has not written itself, so with one the zeroes would never be looked at.
     if (!sweeps || !lower) {
         hipLaunchKernelGGL(sor_zero_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, ctx->s_main, y, n, done);
         KR_HIP(hipGetLastError());
     }
     if (!sweeps) return KRYST_OK;
-    for (int32_t it = 0; it < pc->sor_its; ++it) {
+    for (int32_t it = 0; it < its; ++it) {
         if (lower) {
-            KR_HIP(hipMemsetAsync(pc->d_sor_sync, 0, 16, ctx->s_main));      // (a whole 16-byte block at the start of its allocation)
-            sor_launch(pc, true, eis, x, y, done);
+            KR_HIP(hipMemsetAsync(d_sync, 0, 16, ctx->s_main));      // (a whole 16-byte block at the start of its allocation)
+            launch(true, eis, x, y, done);
             KR_HIP(hipGetLastError());
         }
         if (upper) {
-            KR_HIP(hipMemsetAsync(pc->d_sor_sync, 0, 16, ctx->s_main));      // (a whole 16-byte block at the start of its allocation)
-            sor_launch(pc, false, eis, x, y, done);
+            KR_HIP(hipMemsetAsync(d_sync, 0, 16, ctx->s_main));      // (a whole 16-byte block at the start of its allocation)
+            launch(false, eis, x, y, done);
             KR_HIP(hipGetLastError());
         }
     }
     return KRYST_OK;
 }
 
-// after the stream has been synchronised: did a sweep since the last call give up?
-int32_t sor_health(kryst_pc_t pc) {
-    if (!pc->h_sor_gave_up || *(volatile uint32_t*)pc->h_sor_gave_up == 0u) return KRYST_OK;
-    *(volatile uint32_t*)pc->h_sor_gave_up = 0u;
+int32_t SorPc::health() {
+    if (!h_gave_up || *(volatile uint32_t*)h_gave_up == 0u) return KRYST_OK;
+    *(volatile uint32_t*)h_gave_up = 0u;
     set_error("SOR: a sweep's grid barrier was abandoned (the device is shared or time-sliced); the result holds NaNs");
     return KRYST_SOLVE_ERROR;
-}
-
-void sor_free(kryst_pc_t pc) {
-    for (int d = 0; d < 2; ++d) { (void)pool_free(pc->d_sor_rows[d]); (void)pool_free(pc->d_sor_off[d]); pc->d_sor_rows[d] = nullptr; pc->d_sor_off[d] = nullptr; }
-    (void)pool_free(pc->d_sor_pos); pc->d_sor_pos = nullptr;
-    (void)pool_free(pc->d_sor_ent); pc->d_sor_ent = nullptr;
-    (void)hipFree(pc->d_sor_sync); pc->d_sor_sync = nullptr;
-    if (pc->h_sor_gave_up) (void)hipHostFree(pc->h_sor_gave_up);
-    pc->h_sor_gave_up = nullptr; pc->d_sor_gave_up = nullptr;
 }
 
 template <class T> static int32_t sor_upload(kryst_ctx_t ctx, T** d, const std::vector<T>& h, const char* what) {
@@ -243,20 +255,18 @@ int32_t kryst_pc_sor(kryst_csr_t a, double omega, int64_t its, int64_t lits, uin
         for (int64_t i = 0; i < n; ++i) KR_ARG(colors[i] >= 0, "pc_sor: negative colour");
     kryst_ctx_t ctx = a->ctx;
     KR_HIP(hipSetDevice(ctx->device));
-    kryst_pc_t pc = new kryst_pc_s();
-    pc->ctx = ctx; pc->kind = KR_PC_SOR; pc->a = a; pc->n = n;
-    pc->sor_omega = omega; pc->sor_fshift = fshift; pc->sor_its = (int32_t)its; pc->sor_lits = (int32_t)lits; pc->sor_sym = (int32_t)sym_bits;
+    SorPc* pc = new SorPc(a, omega, (int32_t)its, (int32_t)sym_bits);
     unsigned long long* d_err = nullptr;
     unsigned long long e = ~0ull;
     auto fail = [&](int32_t rc) { (void)hipStreamSynchronize(ctx->s_main); (void)hipFree(d_err); kryst_pc_destroy(pc); return rc; };
     // ---- the diagonal (device)
     if (hipMalloc(&pc->d_inv_diag, sizeof(double) * (size_t)std::max<int64_t>(n, 1)) != hipSuccess || hipMalloc(&d_err, sizeof e) != hipSuccess ||
-        hipMalloc(&pc->d_sor_sync, 16) != hipSuccess ||
-        hipHostMalloc((void**)&pc->h_sor_gave_up, sizeof(uint32_t), hipHostMallocMapped) != hipSuccess) {
+        hipMalloc(&pc->d_sync, 16) != hipSuccess ||
+        hipHostMalloc((void**)&pc->h_gave_up, sizeof(uint32_t), hipHostMallocMapped) != hipSuccess) {
         (void)hipGetLastError(); set_error("SOR: out of device memory (%lld rows)", (long long)n); return fail(KRYST_ERR_HIP);
     }
-    *pc->h_sor_gave_up = 0u;
-    if (hipHostGetDevicePointer((void**)&pc->d_sor_gave_up, pc->h_sor_gave_up, 0) != hipSuccess ||
+    *pc->h_gave_up = 0u;
+    if (hipHostGetDevicePointer((void**)&pc->d_gave_up, pc->h_gave_up, 0) != hipSuccess ||
         hipMemsetAsync(d_err, 0xFF, sizeof e, ctx->s_main) != hipSuccess) { set_error("SOR: set-up failed on the device"); return fail(KRYST_ERR_HIP); }
     if (n > 0) {
         hipLaunchKernelGGL(sor_setup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->s_main, (const int32_t*)a->d_row_ptr,
@@ -285,25 +295,25 @@ int32_t kryst_pc_sor(kryst_csr_t a, double omega, int64_t its, int64_t lits, uin
         for (int64_t i = 0; i < n; ++i)
             std::sort(ent.begin() + rp[(size_t)i], ent.begin() + rp[(size_t)i + 1],
                       [&](int32_t u, int32_t v) { return pos[(size_t)col[(size_t)u]] < pos[(size_t)col[(size_t)v]]; });
-        rc = sor_upload(ctx, &pc->d_sor_pos, pos, "sweep order");
-        if (rc == KRYST_OK) rc = sor_upload(ctx, &pc->d_sor_ent, ent, "entry order");
+        rc = sor_upload(ctx, &pc->d_pos, pos, "sweep order");
+        if (rc == KRYST_OK) rc = sor_upload(ctx, &pc->d_ent, ent, "entry order");
         if (rc == KRYST_OK && hipStreamSynchronize(ctx->s_main) != hipSuccess) { set_error("SOR: set-up failed on the device"); rc = KRYST_ERR_HIP; }
     }
     const bool need[2] = {(sym_bits & KR_SOR_LOWER) != 0, (sym_bits & KR_SOR_UPPER) != 0};
     for (int d = 0; d < 2 && rc == KRYST_OK; ++d) {
         if (!need[d]) continue;
         std::vector<int32_t> rows, off;
-        pc->sor_groups[d] = sor_schedule(n, rp, col, order, pos, d == 0, d == 1 && !(sym_bits & KR_SOR_EISENSTAT), rows, off);
+        pc->groups[d] = sor_schedule(n, rp, col, order, pos, d == 0, d == 1 && !(sym_bits & KR_SOR_EISENSTAT), rows, off);
         int32_t maxw = 1;
-        for (int32_t g = 0; g < pc->sor_groups[d]; ++g) maxw = std::max(maxw, off[(size_t)g + 1] - off[(size_t)g]);
+        for (int32_t g = 0; g < pc->groups[d]; ++g) maxw = std::max(maxw, off[(size_t)g + 1] - off[(size_t)g]);
         // one workgroup per CU at most: all of them resident, whatever else the kernel needs
-        pc->sor_grid[d] = (uint32_t)std::max(1, std::min(ctx->num_cu, (maxw + KR_SOR_T - 1) / KR_SOR_T));
-        if ((unsigned long long)pc->sor_groups[d] * pc->sor_grid[d] >= (1ull << 32)) {       // the barrier's arrival count is 32 bits
-            set_error("SOR: %d dependency levels times %u workgroups do not fit the barrier's counter", pc->sor_groups[d], pc->sor_grid[d]);
+        pc->grid[d] = (uint32_t)std::max(1, std::min(ctx->num_cu, (maxw + KR_SOR_T - 1) / KR_SOR_T));
+        if ((unsigned long long)pc->groups[d] * pc->grid[d] >= (1ull << 32)) {       // the barrier's arrival count is 32 bits
+            set_error("SOR: %d dependency levels times %u workgroups do not fit the barrier's counter", pc->groups[d], pc->grid[d]);
             rc = KRYST_UNSUPPORTED; break;
         }
-        rc = sor_upload(ctx, &pc->d_sor_rows[d], rows, "rows by level");
-        if (rc == KRYST_OK) rc = sor_upload(ctx, &pc->d_sor_off[d], off, "level offsets");
+        rc = sor_upload(ctx, &pc->d_rows[d], rows, "rows by level");
+        if (rc == KRYST_OK) rc = sor_upload(ctx, &pc->d_off[d], off, "level offsets");
         if (rc == KRYST_OK && hipStreamSynchronize(ctx->s_main) != hipSuccess) { set_error("SOR: set-up failed on the device"); rc = KRYST_ERR_HIP; }
     }
     if (rc == KRYST_OK && hipStreamSynchronize(ctx->s_main) != hipSuccess) { set_error("SOR: set-up failed on the device"); rc = KRYST_ERR_HIP; }
@@ -313,14 +323,15 @@ int32_t kryst_pc_sor(kryst_csr_t a, double omega, int64_t its, int64_t lits, uin
     return KRYST_OK;
 }
 
-int32_t kryst_pc_sor_info(kryst_pc_t pc, int32_t* groups_forward, int32_t* groups_backward, int64_t* rows, int32_t* grid_forward,
+int32_t kryst_pc_sor_info(kryst_pc_t h, int32_t* groups_forward, int32_t* groups_backward, int64_t* rows, int32_t* grid_forward,
                           int32_t* grid_backward) {
-    KR_ARG(pc && pc->kind == KR_PC_SOR, "pc_sor_info");
-    if (groups_forward) *groups_forward = pc->sor_groups[0];
-    if (groups_backward) *groups_backward = pc->sor_groups[1];
+    SorPc* pc = pc_cast<SorPc>(h);
+    KR_ARG(pc, "pc_sor_info");
+    if (groups_forward) *groups_forward = pc->groups[0];
+    if (groups_backward) *groups_backward = pc->groups[1];
     if (rows) *rows = pc->n;
-    if (grid_forward) *grid_forward = pc->sor_groups[0] ? (int32_t)pc->sor_grid[0] : 0;
-    if (grid_backward) *grid_backward = pc->sor_groups[1] ? (int32_t)pc->sor_grid[1] : 0;
+    if (grid_forward) *grid_forward = pc->groups[0] ? (int32_t)pc->grid[0] : 0;
+    if (grid_backward) *grid_backward = pc->groups[1] ? (int32_t)pc->grid[1] : 0;
     return KRYST_OK;
 }
 

@@ -478,6 +478,15 @@ static int32_t spai_run(kryst_csr_t a, SpaiTmp& tp, const int32_t* pptr, const i
     return KRYST_OK;
 }
 
+// ApproxInv::apply (approxinv.rs:268-298): z_i = sum_j M_ij r_j, ascending j from 0 -- an SpMV with M, the operator `a` of this object
+struct SpaiPc final : kryst_pc_s {
+    static constexpr int KIND = KR_PC_SPAI;
+    const bool owns_m;                // M of a set-up on the device; rows handed in by the caller stay the caller's
+    SpaiPc(kryst_csr_t m, bool owns) : kryst_pc_s(m->ctx, KIND, m, m->nrows), owns_m(owns) {}
+    ~SpaiPc() override { if (owns_m) kryst_csr_destroy(a); }
+    int32_t apply(int64_t, const double* r, double* z, const int* done) override { return launch_spmv(a, r, z, 0, nullptr, done); }
+};
+
 }  // namespace kr
 
 using namespace kr;
@@ -545,14 +554,20 @@ int32_t kryst_pc_spai(kryst_csr_t a, int32_t pattern_kind, const int64_t* pat_pt
         (void)hipStreamSynchronize(a->ctx->s_main);             // the temporaries go with tp, after the last kernel that reads them
     }
     if (rc != KRYST_OK) return rc;
-    kryst_pc_t pc = new kryst_pc_s();
-    pc->ctx = a->ctx; pc->kind = KR_PC_SPAI; pc->a = m; pc->spai_m = m; pc->n = n;
-    *out = pc;
+    *out = new SpaiPc(m, true);
     return KRYST_OK;
 }
 
-int32_t kryst_pc_spai_export(kryst_pc_t pc, int64_t* nnz, int64_t* row_ptr, int32_t* col, double* val) {
-    KR_ARG(pc && nnz && pc->kind == KR_PC_SPAI && pc->a, "pc_spai_export");
+int32_t kryst_pc_approx_inverse(kryst_csr_t m, kryst_pc_t* out) {
+    KR_ARG(m && out, "pc_approx_inverse");
+    KR_ARG(m->nrows == m->xlen, "pc_approx_inverse: the inverse rows must form a square operator");
+    *out = new SpaiPc(m, false);
+    return KRYST_OK;
+}
+
+int32_t kryst_pc_spai_export(kryst_pc_t h, int64_t* nnz, int64_t* row_ptr, int32_t* col, double* val) {
+    SpaiPc* pc = pc_cast<SpaiPc>(h);
+    KR_ARG(pc && nnz, "pc_spai_export");
     KR_ARG(!row_ptr || (col && val), "pc_spai_export: col / val are NULL");
     *nnz = pc->a->nnz;
     if (!row_ptr) return KRYST_OK;
