@@ -270,9 +270,7 @@ struct TfqmrRun : SolverRun {
         KR_TRY(launch_ew(ctx, TfResNormOp{st, r, v}, n, done));                                   // :149-152
         KR_TRY((reduce_then<1>(ctx, nt, ws.red, TfStepLogic{lc, tf})));
         KR_TRY(launch_ew_gated(ctx, TfXdyOp{st, tf, u, q, d, xw, y}, n, GateEarly{st}));
-        hipLaunchKernelGGL((logic_kernel<ClearEarlyLogic>), dim3(1), dim3(64), 0, ctx->s_main, ws.red, ClearEarlyLogic{lc});
-        KR_HIP(hipGetLastError());
-        return KRYST_OK;
+        return logic_only(ctx, ws.red, ClearEarlyLogic{lc});
     }
 };
 

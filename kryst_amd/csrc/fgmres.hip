@@ -9,7 +9,7 @@
 // step are independent, so they are taken 8 at a time in ONE pass over w (9n words for 8 dots instead of 16n), and the
 // j+1 subtractions 8 at a time in one read-modify-write of w (10n words for 8 axpys instead of 24n); the last
 // batch also produces ||w||^2.  Per basis vector the step moves 2.4n words against the reference's 5n.
-#include "solver_common.h"
+#include "restart_common.h"
 
 namespace kr {
 
@@ -19,7 +19,7 @@ struct FgState {                     // device
     int converged;                   // the cycle-local `converged` (:205)
     int apply;                       // Modified refinement: |corr| > 1e-10 (:242)
     long long total_iters;
-    long long k;                     // arnoldi_steps
+    int k;                           // arnoldi_steps
     double hj1, corr, beta, beta0;
 };
 struct FgPtrs { FgState* fs; double* h; double* cs; double* sn; double* s; double* hcol; double* y; int ld; int restart; };
@@ -87,44 +87,13 @@ struct NextBasisOp {                 // v_{j+1} = w / h[j+1][j], or zeros on hap
         st2(out, i, a.a / d, a.b / d);
     }
 };
-struct ScaleByOp {                   // v_0 = r / beta (:167-169, :332-334)
-    static constexpr int NQ = 0; static constexpr const char* TAG = "ScaleBy";
-    const double* s; const double* in; double* out;
-    __device__ __forceinline__ void pair(int64_t i, bool, bool, double (&)[1]) const {
-        const double d = *s;
-        const d2 a = ld2(in, i);
-        st2(out, i, a.a / d, a.b / d);
-    }
-};
-struct FgUpdateOp {                  // build_solution (:344-356): x += y[i] z_i, i ascending per element
-    static constexpr int NQ = 0; static constexpr const char* TAG = "FgUpdate";
-    const FgState* fs; const double* y; double* const* z; double* x;
-    __device__ __forceinline__ void pair(int64_t i, bool, bool, double (&)[1]) const {
-        const int m = (int)fs->k;
-        d2 xx = ld2(x, i);
-        for (int j0 = 0; j0 < m; j0 += 8) {                  // 8 basis vectors in flight; the sum keeps its ascending order
-            d2 uu[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) uu[k] = ld2(z[min(j0 + k, m - 1)], i);
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (j0 + k < m) { const double yj = y[j0 + k]; xx.a = xx.a + yj * uu[k].a; xx.b = xx.b + yj * uu[k].b; }
-        }
-        st2(x, i, xx.a, xx.b);
-    }
-};
 
-// kernels of the Arnoldi loop are gated on done || cyc_stop
-struct GateFgCycle {
-    const DevState* st; const FgState* fs;
-    __device__ __forceinline__ bool skip() const { return st->done || fs->cyc_stop; }
-};
+// kernels of the Arnoldi loop are gated on done || cyc_stop (CycleGate)
 template <class Op>
-static int32_t fg_launch(kryst_ctx_t ctx, const Op& op, int64_t n, const DevState* st, const FgState* fs, int bpc = 0) {
+static int32_t fg_launch(kryst_ctx_t ctx, const Op& op, int64_t n, const CycleGate& cyc, int bpc = 0) {
     static const int dflt = [] { const char* e = getenv("KRYST_FG_BLOCKS_PER_CU"); return e ? atoi(e) : 2; }();
-    return launch_ew_gated(ctx, op, n, GateFgCycle{st, fs}, bpc > 0 ? bpc : std::max(dflt, ew_bpc<Op>::value));
+    return launch_ew_gated(ctx, op, n, cyc, bpc > 0 ? bpc : std::max(dflt, ew_bpc<Op>::value));
 }
-__global__ void fg_gate_kernel(const DevState* st, const FgState* fs, int* gate) { *gate = (st->done || fs->cyc_stop) ? 1 : 0; }
 
 // ---- logic
 #define HH(i, k) P.h[(size_t)(i) * P.ld + (k)]
@@ -174,21 +143,7 @@ struct FgNormLogic {                 // :250-301 ; red0 = (w,w)
         for (int i = 0; i <= j; ++i) HH(i, j) = P.hcol[i];              // :251
         const double hapbnd = haptol * fabs(P.s[j]);                    // :253
         fs->happy = (fabs(hj1) < hapbnd) ? 1 : 0;                       // :254
-        for (int i = 0; i < j; ++i) {                                   // :263-267
-            const double temp = P.cs[i] * HH(i, j) + P.sn[i] * HH(i + 1, j);
-            HH(i + 1, j) = -P.sn[i] * HH(i, j) + P.cs[i] * HH(i + 1, j);
-            HH(i, j) = temp;
-        }
-        const double h1 = HH(j, j), h2 = HH(j + 1, j);                  // :269-278
-        const double denom = dsqrt(h1 * h1 + h2 * h2);
-        double cc, ss;
-        if (denom == 0.0) { cc = 1.0; ss = 0.0; } else { cc = h1 / denom; ss = h2 / denom; }
-        P.cs[j] = cc; P.sn[j] = ss;
-        const double temp = cc * P.s[j] + ss * P.s[j + 1];              // :281-283
-        P.s[j + 1] = -ss * P.s[j] + cc * P.s[j + 1];
-        P.s[j] = temp;
-        HH(j, j) = cc * HH(j, j) + ss * HH(j + 1, j);                   // :284-285
-        HH(j + 1, j) = 0.0;
+        givens_column(P.h, P.ld, P.cs, P.sn, P.s, j, ZeroGuard{});      // :263-285
         const double res_norm = fabs(P.s[j + 1]);                       // :286
         fs->total_iters = fs->total_iters + 1;                          // :287
         c.push(res_norm);                                               // :289-292
@@ -199,14 +154,7 @@ struct FgNormLogic {                 // :250-301 ; red0 = (w,w)
 struct FgBackLogic {                 // :304-314 (no pivot guard)
     static constexpr bool RUN_WHEN_DONE = false;
     LogicCtx c; FgPtrs P;
-    __device__ void run(const double*) const {
-        const int k = (int)P.fs->k;
-        for (int i = k - 1; i >= 0; --i) {
-            double sum = P.s[i];
-            for (int l = i + 1; l < k; ++l) sum = sum - HH(i, l) * P.y[l];
-            P.y[i] = sum / HH(i, i);
-        }
-    }
+    __device__ void run(const double*) const { back_substitute(P.h, P.ld, P.s, P.y, P.fs->k, NoGuard{}); }
 };
 struct FgCycleEndLogic {             // :323-337 then :339-340 ; red0 = (r_new, r_new)
     static constexpr bool RUN_WHEN_DONE = false;
@@ -232,67 +180,52 @@ struct FgCycleEndLogic {             // :323-337 then :339-340 ; red0 = (r_new, 
 };
 #undef HH
 
-template <class L>
-static int32_t fg_logic_only(kryst_ctx_t ctx, const double* red, const L& l) {
-    hipLaunchKernelGGL((logic_kernel<L>), dim3(1), dim3(64), 0, ctx->s_main, red, l);
-    KR_HIP(hipGetLastError());
-    return KRYST_OK;
-}
-
 // one batch of up to 8 dots + its fold; slots past cnt alias the first vector and are ignored by the logic
 template <int NB>
 static int32_t dot_batch(kryst_ctx_t ctx, int64_t n, int64_t nt, double* red, const LogicCtx& lc, const FgPtrs& P,
-                         const DevState* st, const double* w, double* const* v, int i0, int cnt) {
+                         const CycleGate& cyc, const double* w, double* const* v, int i0, int cnt) {
     static const int bpc = [] { const char* e = getenv("KRYST_DOT_BLOCKS_PER_CU"); return e ? atoi(e) : 4; }();   // read-only reductions want more waves in flight than the mixed streams
     auto go = [&](auto op) -> int32_t {
         op.w = w;
         for (int k = 0; k < NB; ++k) op.v[k] = v[i0 + (k < cnt ? k : 0)];
-        return fg_launch(ctx, op, n, st, P.fs, bpc);
+        return fg_launch(ctx, op, n, cyc, bpc);
     };
     if (keep_in_cache(n)) KR_TRY(go(MultiDotOp<NB, true>{})); else KR_TRY(go(MultiDotOp<NB, false>{}));
     return reduce_then<NB>(ctx, nt, red, FgHcolLogic<NB>{lc, P, i0, cnt});
 }
 template <int NB>
-static int32_t axpy_batch(kryst_ctx_t ctx, int64_t n, const FgPtrs& P, const DevState* st, double* w, double* const* v,
+static int32_t axpy_batch(kryst_ctx_t ctx, int64_t n, const FgPtrs& P, const CycleGate& cyc, double* w, double* const* v,
                           int i0, const double* next) {
     auto go = [&](auto op) -> int32_t {
         op.h = P.hcol + i0; op.next = next; op.w = w;
         for (int k = 0; k < NB; ++k) op.v[k] = v[i0 + k];
-        return fg_launch(ctx, op, n, st, P.fs);
+        return fg_launch(ctx, op, n, cyc);
     };
     return keep_in_cache(n) ? go(MultiAxpyOp<NB, true>{}) : go(MultiAxpyOp<NB, false>{});
 }
 
 int32_t fgmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32_t orthog, double haptol, int32_t preallocate) {
     const EnvFreeze knobs;                    // the tuning knobs are read once per solve, not per launch
-    KR_ARG(io.a && io.params && bv && xv, "solve: null argument");
+    KR_ARG(io.a && io.params, "solve: null argument");
     const kryst_params_t* p = io.params;
-    kryst_csr_t a = io.a; kryst_ctx_t ctx = a->ctx; const int64_t n = a->nrows, nt = ntiles_of(n);
-    KR_ARG(bv->ctx == ctx && xv->ctx == ctx, "solve: context mismatch");
-    KR_ARG(a->nrows == a->xlen && bv->n == n && xv->n == n, "solve: size mismatch");
-    KR_ARG(p->restart >= 1 && p->restart <= 4096, "fgmres: restart out of range (restart = 0 never terminates in the reference)");
-    a->halo_started_for = nullptr;            // (csr.h: an early halo start belongs to the CG / PCG solve that made it)
-    KR_ARG(p->max_iters >= 0, "solve: max_iters < 0");
-    KR_ARG(orthog == 0 || orthog == 1, "fgmres: orthog (0 Classical, 1 Modified)");
-    KR_HIP(hipSetDevice(ctx->device));
     const kryst_pc_t pc = io.pc && io.pc->kind != KR_PC_IDENTITY ? io.pc : nullptr;
-    KR_ARG(!pc || pc->ctx == ctx, "solve: preconditioner context");
+    RestartRun run(bv, xv, io);
+    KR_TRY(run.check(pc, "fgmres: restart out of range (restart = 0 never terminates in the reference)"));
+    KR_ARG(orthog == 0 || orthog == 1, "fgmres: orthog (0 Classical, 1 Modified)");
     const int64_t max_iters = p->max_iters;
     const int R = (int)std::min<int64_t>(p->restart, std::max<int64_t>(max_iters, 1));    // no cycle is ever longer than this
-    Workspace ws(ctx, n);
-    KR_TRY(ws.init(max_iters + (int64_t)p->restart + 2));
-    KR_TRY(ws.reserve(4 + (R + 1) + (pc ? R : 0)));
-    // small device arrays: H (R+1 x R), cs, sn, s, hcol, y, state, gate, pointer table
-    const size_t nsmall = (size_t)(R + 1) * R + 2 * (size_t)R + (size_t)p->restart + 2 + 2 * (size_t)(R + 8) + 64;
-    double* d_small = nullptr;
-    KR_HIP(hipMalloc(&d_small, sizeof(double) * nsmall + sizeof(double*) * (size_t)(R + 1)));
-    ws.vecs.push_back(d_small);
-    KR_HIP(hipMemsetAsync(d_small, 0, sizeof(double) * nsmall, ctx->s_main));
-    FgPtrs P;
-    P.h = d_small; P.cs = P.h + (size_t)(R + 1) * R; P.sn = P.cs + R; P.s = P.sn + R; P.hcol = P.s + p->restart + 2;
-    P.y = P.hcol + R + 8; P.fs = reinterpret_cast<FgState*>(P.y + R + 8); P.ld = R; P.restart = p->restart;
-    int* d_gate = reinterpret_cast<int*>(P.y + R + 8 + 32);
-    double** d_zptr = reinterpret_cast<double**>(d_small + nsmall);
+    KR_TRY(run.begin(max_iters + (int64_t)p->restart + 2, 4 + (R + 1) + (pc ? R : 0)));
+    kryst_csr_t a = run.a; kryst_ctx_t ctx = run.ctx; const int64_t n = run.n, nt = run.nt;
+    Workspace& ws = run.ws; const LogicCtx& lc = run.lc; LiveMonitor& mon = run.mon; const int* done = run.done;
+    FgPtrs P; P.ld = R; P.restart = p->restart;
+    int* d_gate = nullptr; double** d_zptr = nullptr;
+    SmallArena small;
+    auto carve = [&] {
+        P.h = small.take<double>((size_t)(R + 1) * R); P.cs = small.take<double>(R); P.sn = small.take<double>(R);
+        P.s = small.take<double>((size_t)p->restart + 2); P.hcol = small.take<double>(R + 8); P.y = small.take<double>(R + 8);
+        P.fs = small.take<FgState>(1); d_gate = small.take<int>(1); d_zptr = small.take<double*>(R + 1);
+    };
+    carve(); KR_TRY(small.alloc(ws)); carve();
     double *xk, *r, *w, *tmp;
     KR_TRY(ws.vec(&xk)); KR_TRY(ws.vec(&r)); KR_TRY(ws.vec(&w)); KR_TRY(ws.vec(&tmp));
     std::vector<double*> V((size_t)R + 1), Z((size_t)R + 1, nullptr);
@@ -301,10 +234,8 @@ int32_t fgmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32_t 
     if (pc) { for (int k = 0; k < R; ++k) KR_TRY(ws.vec(&Z[k])); } else Z = V;
     KR_HIP(hipMemcpyAsync(d_zptr, Z.data(), sizeof(double*) * (size_t)(R + 1), hipMemcpyHostToDevice, ctx->s_main));
     KR_HIP(hipStreamSynchronize(ctx->s_main));
-    const LogicCtx lc = ws.lctx(p, io.monitor != nullptr);
-    LiveMonitor mon; mon.io = &io; mon.ws = &ws; mon.first = 1;
-    const DevState* st = ws.st; const FgState* fs = P.fs;
-    const int* done = &ws.st->done;
+    const FgState* fs = P.fs;
+    const CycleGate cyc{done, &P.fs->cyc_stop};
     int32_t rc = KRYST_OK;
 
     KR_HIP(hipMemcpyAsync(xk, xv->d, padded_bytes(n), hipMemcpyDeviceToDevice, ctx->s_main));
@@ -315,20 +246,19 @@ int32_t fgmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32_t 
     while (total < max_iters) {                                                                   // :175
         const int m = (int)(preallocate ? std::min<int64_t>(max_iters, p->restart)
                                         : std::min<int64_t>(p->restart, max_iters - total));      // :203
-        KR_TRY(fg_logic_only(ctx, ws.red, FgCycleLogic{lc, P, m}));
-        KR_TRY(launch_ew(ctx, ScaleByOp{&P.fs->beta, r, V[0]}, n, done));                         // :167-169 / :332-334
+        KR_TRY(logic_only(ctx, ws.red, FgCycleLogic{lc, P, m}));
+        KR_TRY(launch_ew(ctx, DivOp{&P.fs->beta, r, V[0]}, n, done));                             // :167-169 / :332-334
         for (int j = 0; j < m; ++j) {                                                             // :207
-            hipLaunchKernelGGL(fg_gate_kernel, dim3(1), dim3(1), 0, ctx->s_main, st, fs, d_gate);
-            KR_HIP(hipGetLastError());
+            KR_TRY(write_cycle_gate(ctx, cyc, d_gate));
             if (pc) { rc = pc_apply_dev_fresh(pc, n, V[j], Z[j], d_gate, V[j]); if (rc) return rc; }             // :209-212
             KR_TRY(launch_spmv(a, Z[j], w, 0, nullptr, d_gate));                                  // :214-215
             // all h_col[i] = (w, v_i) from the unmodified w (:220-222 / :231-233)
             for (int i0 = 0; i0 <= j; i0 += 8) {
                 const int cnt = std::min(8, j + 1 - i0);
-                if (cnt > 4) KR_TRY(dot_batch<8>(ctx, n, nt, ws.red, lc, P, st, w, V.data(), i0, cnt));
-                else if (cnt > 2) KR_TRY(dot_batch<4>(ctx, n, nt, ws.red, lc, P, st, w, V.data(), i0, cnt));
-                else if (cnt > 1) KR_TRY(dot_batch<2>(ctx, n, nt, ws.red, lc, P, st, w, V.data(), i0, cnt));
-                else KR_TRY(dot_batch<1>(ctx, n, nt, ws.red, lc, P, st, w, V.data(), i0, cnt));
+                if (cnt > 4) KR_TRY(dot_batch<8>(ctx, n, nt, ws.red, lc, P, cyc, w, V.data(), i0, cnt));
+                else if (cnt > 2) KR_TRY(dot_batch<4>(ctx, n, nt, ws.red, lc, P, cyc, w, V.data(), i0, cnt));
+                else if (cnt > 1) KR_TRY(dot_batch<2>(ctx, n, nt, ws.red, lc, P, cyc, w, V.data(), i0, cnt));
+                else KR_TRY(dot_batch<1>(ctx, n, nt, ws.red, lc, P, cyc, w, V.data(), i0, cnt));
             }
             // w -= h_col[i] v_i, i ascending (:223-228 / :234-236); the last batch carries (w,w) or the first refinement dot
             for (int i0 = 0; i0 <= j; ) {
@@ -336,25 +266,25 @@ int32_t fgmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32_t 
                 const int nb = left >= 8 ? 8 : left >= 4 ? 4 : left >= 2 ? 2 : 1;
                 const bool last = (i0 + nb == j + 1);
                 const double* next = (last && orthog == 1) ? V[0] : nullptr;
-                if (nb == 8) KR_TRY(axpy_batch<8>(ctx, n, P, st, w, V.data(), i0, next));
-                else if (nb == 4) KR_TRY(axpy_batch<4>(ctx, n, P, st, w, V.data(), i0, next));
-                else if (nb == 2) KR_TRY(axpy_batch<2>(ctx, n, P, st, w, V.data(), i0, next));
-                else KR_TRY(axpy_batch<1>(ctx, n, P, st, w, V.data(), i0, next));
+                if (nb == 8) KR_TRY(axpy_batch<8>(ctx, n, P, cyc, w, V.data(), i0, next));
+                else if (nb == 4) KR_TRY(axpy_batch<4>(ctx, n, P, cyc, w, V.data(), i0, next));
+                else if (nb == 2) KR_TRY(axpy_batch<2>(ctx, n, P, cyc, w, V.data(), i0, next));
+                else KR_TRY(axpy_batch<1>(ctx, n, P, cyc, w, V.data(), i0, next));
                 i0 += nb;
             }
             if (orthog == 1)                                                                      // :239-247
                 for (int i = 0; i <= j; ++i) {
                     KR_TRY((reduce_then<1>(ctx, nt, ws.red, FgCorrLogic{lc, P})));
-                    if (keep_in_cache(n)) KR_TRY(fg_launch(ctx, RefineLinkOp<true>{fs, V[i], i < j ? V[i + 1] : nullptr, w}, n, st, fs));
-                    else KR_TRY(fg_launch(ctx, RefineLinkOp<false>{fs, V[i], i < j ? V[i + 1] : nullptr, w}, n, st, fs));
+                    if (keep_in_cache(n)) KR_TRY(fg_launch(ctx, RefineLinkOp<true>{fs, V[i], i < j ? V[i + 1] : nullptr, w}, n, cyc));
+                    else KR_TRY(fg_launch(ctx, RefineLinkOp<false>{fs, V[i], i < j ? V[i + 1] : nullptr, w}, n, cyc));
                 }
             KR_TRY((reduce_then<1>(ctx, nt, ws.red, FgNormLogic{lc, P, j, haptol})));
-            KR_TRY(fg_launch(ctx, NextBasisOp{fs, w, V[j + 1]}, n, st, fs, 4));                   // :255-261 (fp64 divisions: 4 workgroups per CU)
+            KR_TRY(fg_launch(ctx, NextBasisOp{fs, w, V[j + 1]}, n, cyc, 4));                   // :255-261 (fp64 divisions: 4 workgroups per CU)
         }
         // ---- cycle end (:303-337)
         total += m;
-        KR_TRY(fg_logic_only(ctx, ws.red, FgBackLogic{lc, P}));
-        KR_TRY(launch_ew(ctx, FgUpdateOp{fs, P.y, d_zptr, xk}, n, done));
+        KR_TRY(logic_only(ctx, ws.red, FgBackLogic{lc, P}));
+        KR_TRY(launch_ew(ctx, BasisUpdateOp<false>{&P.fs->k, P.y, d_zptr, xk}, n, done));
         KR_TRY(residual_dot(a, bv->d, xk, r, tmp, done));
         KR_TRY((reduce_then<1>(ctx, nt, ws.red, FgCycleEndLogic{lc, P, total >= max_iters ? 1 : 0})));
         KR_HIP(hipStreamSynchronize(ctx->s_main));                  // one host sync per restart cycle
@@ -362,15 +292,7 @@ int32_t fgmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32_t 
         mon.poll();                                                                               // live monitor: once per restart cycle
         if (ctx->h_prog->done) break;
     }
-    KR_HIP(hipStreamSynchronize(ctx->s_main));
-    const int32_t status = finish_solve(ws, io);
-    if (status == KRYST_OK) KR_HIP(hipMemcpyAsync(xv->d, xk, padded_bytes(n), hipMemcpyDeviceToDevice, ctx->s_main));
-    KR_HIP(hipStreamSynchronize(ctx->s_main));
-    if (io.monitor) {
-        DevState h;
-        if (read_state(ws, &h) == hipSuccess) mon.upto(h.hist_len);
-    }
-    return status;
+    return run.end(xk);
 }
 
 }  // namespace kr

@@ -24,17 +24,12 @@
 // (common.h), so every coefficient has the bits of oracle.dot(..., Reduce.tiled(*reduce_spec())).  Fused: the second BCGS dot pass
 // into the first update (pass B), the first Gram matrix into the second update (pass C), the second Gram matrix into the first
 // triangular solve (pass D); pass E writes the new basis vectors.  The scalar work runs in one-thread logic kernels.
-#include "solver_common.h"
+#include "restart_common.h"
 
 namespace kr {
 
 constexpr int PG_SMAX = 16;          // largest s of the s-step form (and of the block kernels)
 constexpr int PG_NW = KR_T / 64;
-
-struct PgGate {                      // a launch is a no-op once the solve has ended or the cycle has been left
-    const int* a; const int* b;
-    __device__ __forceinline__ bool skip() const { return (a && *a) || (b && *b); }
-};
 
 struct PgState {                     // device
     long long iteration;
@@ -42,7 +37,6 @@ struct PgState {                     // device
     int m;                           // columns that enter the update of this cycle
     int j;                           // s-step: basis vectors in the cycle minus one (the index of the last one)
     int keep;                        // s-step: columns kept by the first CholQR pass of the current block
-    int pad0, pad1;
     double beta, res0, inv;
 };
 
@@ -88,7 +82,7 @@ struct PgPass {
     int64_t n; double* part; int64_t pstride;
 };
 
-__global__ __launch_bounds__(KR_T) void pg_pass_kernel(PgPass p, PgGate gate) {
+__global__ __launch_bounds__(KR_T) void pg_pass_kernel(PgPass p, CycleGate gate) {
     if (gate.skip()) return;
     const int s = p.sdev ? min(*p.sdev, p.s) : p.s;
     if (s <= 0) return;
@@ -165,7 +159,7 @@ __global__ __launch_bounds__(KR_T) void pg_pass_kernel(PgPass p, PgGate gate) {
 
 // fold2's tree for many quantities: stage 1 per chunk of KR_F tile partials (blockIdx.y = quantity), stage 2 over the chunks
 __global__ __launch_bounds__(KR_F) void pg_fold1_kernel(const double* part, int64_t pstride, int64_t ntiles, int64_t nchunks,
-                                                        double* chunks, double* out, PgGate gate) {
+                                                        double* chunks, double* out, CycleGate gate) {
     if (gate.skip()) return;
     __shared__ double lds[KR_F / 64];
     const int64_t qn = blockIdx.y, c = blockIdx.x;
@@ -177,7 +171,7 @@ __global__ __launch_bounds__(KR_F) void pg_fold1_kernel(const double* part, int6
         else chunks[qn * nchunks + c] = v[0];
     }
 }
-__global__ __launch_bounds__(KR_F) void pg_fold2_kernel(const double* chunks, int64_t nchunks, double* out, PgGate gate) {
+__global__ __launch_bounds__(KR_F) void pg_fold2_kernel(const double* chunks, int64_t nchunks, double* out, CycleGate gate) {
     if (gate.skip()) return;
     __shared__ double lds[KR_F / 64];
     const int64_t qn = blockIdx.x;
@@ -193,7 +187,7 @@ struct PgBuf {                       // tile partials and chunk values of up to 
 };
 
 // one block pass and, when it has inner products, their fold into out[0..nq)
-static int32_t pg_pass(kryst_ctx_t ctx, PgPass p, int nq, double* out, const PgBuf& buf, PgGate gate) {
+static int32_t pg_pass(kryst_ctx_t ctx, PgPass p, int nq, double* out, const PgBuf& buf, CycleGate gate) {
     p.part = buf.part; p.pstride = buf.ntiles;
     if (p.dots && nq > buf.nq) { set_error("pca_gmres: %d block inner products exceed the work area", nq); return KRYST_ERR_ARG; }
     static const int bpc = [] { const char* e = getenv("KRYST_PG_BLOCKS_PER_CU"); return e ? std::max(1, atoi(e)) : 4; }();
@@ -214,15 +208,6 @@ static int32_t pg_pass(kryst_ctx_t ctx, PgPass p, int nq, double* out, const PgB
 }
 
 // ---- vector ops
-struct PgDivOp {                     // out = in / s    (:124 `ri / beta`; the s-step basis inputs w_k / ||w_k||)
-    static constexpr int NQ = 0; static constexpr const char* TAG = "PgDiv";
-    const double* s; const double* in; double* out;
-    __device__ __forceinline__ void pair(int64_t i, bool, bool, double (&)[1]) const {
-        const double d = *s;
-        const d2 a = ld2(in, i);
-        st2(out, i, a.a / d, a.b / d);
-    }
-};
 struct PgMulOp {                     // out = in * s    (:227-228 `*vki *= inv`)
     static constexpr int NQ = 0; static constexpr const char* TAG = "PgMul";
     const double* s; const double* in; double* out;
@@ -230,24 +215,6 @@ struct PgMulOp {                     // out = in * s    (:227-228 `*vki *= inv`)
         const double d = *s;
         const d2 a = ld2(in, i);
         st2(out, i, a.a * d, a.b * d);
-    }
-};
-struct PgUpdateOp {                  // acc (+)= sum_i y[i] U[i], i ascending per element; from_zero: acc starts at 0.0 (:289-295 / Q y)
-    static constexpr int NQ = 0; static constexpr const char* TAG = "PgUpdate";
-    const PgState* gs; const double* y; double* const* u; const double* x; double* out; int from_zero;
-    __device__ __forceinline__ void pair(int64_t i, bool, bool, double (&)[1]) const {
-        const int m = gs->m;
-        d2 xx{0.0, 0.0};
-        if (!from_zero) xx = ld2(x, i);
-        for (int j0 = 0; j0 < m; j0 += 8) {
-            d2 uu[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) uu[k] = ld2(u[min(j0 + k, m - 1)], i);
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (j0 + k < m) { const double yj = y[j0 + k]; xx.a = xx.a + yj * uu[k].a; xx.b = xx.b + yj * uu[k].b; }
-        }
-        st2(out, i, xx.a, xx.b);
     }
 };
 struct PgAddOp {                     // x = x + z
@@ -262,25 +229,6 @@ struct PgAddOp {                     // x = x + z
 // ---- logic
 #define HH(i, k) P.h[(size_t)(i) * P.R + (k)]
 #define HU(i, k) P.hu[(size_t)(i) * P.R + (k)]
-
-// Givens step of column col (:238-262): previous rotations, the new one (epsilon guard), g
-__device__ inline void pg_givens(const PgPtrs& P, int col) {
-    const double eps = DBL_EPSILON;
-    for (int i = 0; i < col; ++i) {
-        const double temp = P.cs[i] * HH(i, col) + P.sn[i] * HH(i + 1, col);
-        HH(i + 1, col) = -P.sn[i] * HH(i, col) + P.cs[i] * HH(i + 1, col);
-        HH(i, col) = temp;
-    }
-    const double h_kk = HH(col, col), h_k1k = HH(col + 1, col);
-    const double r = dsqrt(h_kk * h_kk + h_k1k * h_k1k);
-    if (fabs(r) < eps) { P.cs[col] = 1.0; P.sn[col] = 0.0; }
-    else { P.cs[col] = h_kk / r; P.sn[col] = h_k1k / r; }
-    HH(col, col) = P.cs[col] * h_kk + P.sn[col] * h_k1k;
-    HH(col + 1, col) = 0.0;
-    const double temp = P.cs[col] * P.g[col] + P.sn[col] * P.g[col + 1];
-    P.g[col + 1] = -P.sn[col] * P.g[col] + P.cs[col] * P.g[col + 1];
-    P.g[col] = temp;
-}
 
 struct PgInitLogic {                 // :113-116 (as written) / r0 = b - A x0 (s-step) ; red0 = (r0, r0)
     static constexpr bool RUN_WHEN_DONE = false;
@@ -317,7 +265,7 @@ struct PgStepLogic {                 // as written, block of one vector at colum
         const double norm_vk = dsqrt(red[j + 1]);                      // :225-226
         HH(j + 1, j) = norm_vk;
         gs->inv = 1.0 / norm_vk;                                       // :227
-        pg_givens(P, j);
+        givens_column(P.h, P.R, P.cs, P.sn, P.g, j, EpsGuard{DBL_EPSILON});   // :238-262
         const double gnorm = fabs(P.g[j + 1]);                         // :266
         gs->iteration = gs->iteration + 1;                             // :267
         c.push(gnorm);                                                 // history (an addition): the value handed to the check
@@ -330,15 +278,9 @@ struct PgBackLogic {                 // as written :278-286 (epsilon guard, y = 
     static constexpr bool RUN_WHEN_DONE = false;
     LogicCtx c; PgPtrs P; int textbook;
     __device__ void run(const double*) const {
-        const double eps = DBL_EPSILON;
-        const int m = P.gs->m;
         for (int i = 0; i < P.R; ++i) P.y[i] = 0.0;
-        for (int i = m - 1; i >= 0; --i) {
-            double sum = P.g[i];
-            for (int k = i + 1; k < m; ++k) sum = sum - HH(i, k) * P.y[k];
-            if (textbook) P.y[i] = sum / HH(i, i);
-            else if (fabs(HH(i, i)) > eps) P.y[i] = sum / HH(i, i);
-        }
+        if (textbook) back_substitute(P.h, P.R, P.g, P.y, P.gs->m, NoGuard{});
+        else back_substitute(P.h, P.R, P.g, P.y, P.gs->m, EpsGuard{DBL_EPSILON});
     }
 };
 struct PgCycleEndLogic {             // :298-307 ; red0 = (r0, r0) of the true residual
@@ -449,7 +391,7 @@ struct PgBlockLogic {                // R2, R = R2 R1, C = C1 + C2, the new Hess
                 }
             }
             for (int l = 0; l <= col + 1; ++l) HH(l, col) = HU(l, col);
-            pg_givens(P, col);
+            givens_column(P.h, P.R, P.cs, P.sn, P.g, col, EpsGuard{DBL_EPSILON});
             gs->iteration = gs->iteration + 1;
             const double res = fabs(P.g[col + 1]);
             c.push(res);
@@ -465,16 +407,6 @@ struct PgBlockLogic {                // R2, R = R2 R1, C = C1 + C2, the new Hess
 #undef HH
 #undef HU
 
-// "gate" kernel: done || cyc_stop in one int, for the `done` hook of launch_spmv / pc_apply_dev_fresh
-__global__ void pg_gate_kernel(const int* done, const int* cyc_stop, int* gate) { *gate = (*done || *cyc_stop) ? 1 : 0; }
-
-template <class L>
-static int32_t pg_logic(kryst_ctx_t ctx, const double* red, const L& l) {
-    hipLaunchKernelGGL((logic_kernel<L>), dim3(1), dim3(64), 0, ctx->s_main, red, l);
-    KR_HIP(hipGetLastError());
-    return KRYST_OK;
-}
-
 static int32_t read_pg(kryst_ctx_t ctx, const PgState* d, PgState* h) {
     KR_HIP(hipMemcpyAsync(h, d, sizeof(PgState), hipMemcpyDeviceToHost, ctx->s_main));
     KR_HIP(hipStreamSynchronize(ctx->s_main));
@@ -485,14 +417,13 @@ int32_t pca_gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32
                         bool textbook) {
     (void)pipeline_depth; (void)tau;          // never read (pca_gmres.rs: pipeline_depth, tau)
     const EnvFreeze knobs;
-    KR_ARG(io.a && io.params && bv && xv, "solve: null argument");
+    KR_ARG(io.a && io.params, "solve: null argument");
     const kryst_params_t* p = io.params;
-    kryst_csr_t a = io.a; kryst_ctx_t ctx = a->ctx; const int64_t n = a->nrows, nt = ntiles_of(n);
-    KR_ARG(bv->ctx == ctx && xv->ctx == ctx, "solve: context mismatch");
-    KR_ARG(a->nrows == a->xlen && bv->n == n && xv->n == n, "solve: size mismatch");
-    KR_ARG(p->max_iters >= 0, "solve: max_iters < 0");
+    const kryst_pc_t pc = io.pc && p->precond_side == 2 ? io.pc : nullptr;     // Left and None never call pc
+    RestartRun run(bv, xv, io);
+    KR_TRY(run.check(pc, "pca_gmres: restart must be in 1..4096 (restart = 0 divides by zero, pca_gmres.rs:120)"));
+    kryst_csr_t a = run.a; kryst_ctx_t ctx = run.ctx; const int64_t n = run.n, nt = run.nt;
     if (a->dist || ctx->nranks > 1) { set_error("pca_gmres: distributed operators are not supported"); return KRYST_UNSUPPORTED; }
-    KR_ARG(p->restart >= 1 && p->restart <= 4096, "pca_gmres: restart must be in 1..4096 (restart = 0 divides by zero, pca_gmres.rs:120)");
     KR_ARG(block_size >= 1, "pca_gmres: block_size = 0 never advances (pca_gmres.rs:273)");
     const int R = p->restart;
     const int64_t n_outer = (p->max_iters + R - 1) / R;                                           // :120
@@ -505,35 +436,25 @@ int32_t pca_gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32
         set_error("pca_gmres: the s-step form is right preconditioned only (Left with a preconditioner)");
         return KRYST_UNSUPPORTED;
     }
-    a->halo_started_for = nullptr;
-    KR_HIP(hipSetDevice(ctx->device));
-    const kryst_pc_t pc = io.pc && p->precond_side == 2 ? io.pc : nullptr;
-    KR_ARG(!pc || pc->ctx == ctx, "solve: preconditioner context");
     const int S = textbook ? block_size : 1;
-
-    Workspace ws(ctx, n);
-    KR_TRY(ws.init(textbook ? p->max_iters + 2 : n_outer * R + 2));
-    KR_TRY(ws.reserve(5 + (R + 1) + (textbook ? S + 1 : 0)));
-    // small device arrays
-    const size_t hsz = (size_t)(R + 1) * R;
-    const size_t nsmall = 2 * hsz + (R + 1) + 3 * (size_t)R + 8 + (size_t)(R + 2) * S + 2 * (size_t)(R + 1) * S + 2 * (size_t)S * S
-                        + 2 * (size_t)S + 2 * (size_t)S * S + 64;
-    double* d_small = nullptr;
-    KR_HIP(hipMalloc(&d_small, sizeof(double) * nsmall + sizeof(double*) * (size_t)(R + 2 + S)));
-    ws.vecs.push_back(d_small);
-    KR_HIP(hipMemsetAsync(d_small, 0, sizeof(double) * nsmall, ctx->s_main));
-    PgPtrs P;
-    double* c = d_small;
-    P.h = c; c += hsz; P.hu = c; c += hsz; P.g = c; c += R + 1; P.cs = c; c += R; P.sn = c; c += R; P.y = c; c += R + 1;
-    P.gs = reinterpret_cast<PgState*>(c); c += 8;
-    P.red = c; c += (size_t)(R + 2) * S;
-    P.c1 = c; c += (size_t)(R + 1) * S; P.c2 = c; c += (size_t)(R + 1) * S;
-    P.g1 = c; c += (size_t)S * S; P.g2 = c; c += (size_t)S * S;
-    P.nu2 = c; c += S; P.nu = c; c += S;
-    P.r1 = c; c += (size_t)S * S; P.r2 = c; c += (size_t)S * S;
-    P.R = R; P.S = S;
-    double** d_qptr = reinterpret_cast<double**>(d_small + nsmall);     // [V_0 .. V_R, w] (as written: the last slot is the block vector)
-    double** d_wptr = d_qptr + (R + 2);                                // s-step block columns
+    KR_TRY(run.begin(textbook ? p->max_iters + 2 : n_outer * R + 2, 5 + (R + 1) + (textbook ? S + 1 : 0)));
+    Workspace& ws = run.ws; const LogicCtx& lc = run.lc; LiveMonitor& mon = run.mon; const int* done = run.done;
+    PgPtrs P; P.R = R; P.S = S;
+    int* d_gate = nullptr;                  // as written: done || cyc_stop in one word, for the SpMV / pc hooks
+    double** d_qptr = nullptr;              // [V_0 .. V_R, w] (as written: the last slot is the block vector)
+    double** d_wptr = nullptr;              // s-step block columns
+    SmallArena small;
+    auto carve = [&] {
+        const size_t hsz = (size_t)(R + 1) * R, rs = (size_t)(R + 1) * S, ss = (size_t)S * S;
+        P.h = small.take<double>(hsz); P.hu = small.take<double>(hsz); P.g = small.take<double>(R + 1);
+        P.cs = small.take<double>(R); P.sn = small.take<double>(R); P.y = small.take<double>(R + 1);
+        P.gs = small.take<PgState>(1); d_gate = small.take<int>(1);
+        P.red = small.take<double>((size_t)(R + 2) * S);
+        P.c1 = small.take<double>(rs); P.c2 = small.take<double>(rs); P.g1 = small.take<double>(ss); P.g2 = small.take<double>(ss);
+        P.nu2 = small.take<double>(S); P.nu = small.take<double>(S); P.r1 = small.take<double>(ss); P.r2 = small.take<double>(ss);
+        d_qptr = small.take<double*>((size_t)R + 2 + S); d_wptr = d_qptr + (R + 2);       // one table: uploaded in one copy
+    };
+    carve(); KR_TRY(small.alloc(ws)); carve();
     // tile partials of the block inner products
     PgBuf buf;
     buf.ntiles = nt; buf.nchunks = nchunks_of(nt);
@@ -555,10 +476,7 @@ int32_t pca_gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32
         KR_HIP(hipMemcpyAsync(d_qptr, tab.data(), sizeof(double*) * tab.size(), hipMemcpyHostToDevice, ctx->s_main));
         KR_HIP(hipStreamSynchronize(ctx->s_main));
     }
-    const LogicCtx lc = ws.lctx(p, io.monitor != nullptr);
-    LiveMonitor mon; mon.io = &io; mon.ws = &ws; mon.first = 1;
-    const int* done = &ws.st->done;
-    const PgGate gdone{done, nullptr}, gcyc{done, &P.gs->cyc_stop};
+    const CycleGate gdone{done, nullptr}, gcyc{done, &P.gs->cyc_stop};
     int32_t rc = KRYST_OK;
 
     if (textbook) KR_HIP(hipMemcpyAsync(xk, xv->d, padded_bytes(n), hipMemcpyDeviceToDevice, ctx->s_main));   // x0 honoured
@@ -569,25 +487,22 @@ int32_t pca_gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32
     if (!textbook) {
         double* const wsel = pc ? z : w;                   // the block vector: A v_j, or M^-1 A v_j (Right, :152-156)
         KR_HIP(hipMemcpyAsync(d_qptr + R + 1, &wsel, sizeof(double*), hipMemcpyHostToDevice, ctx->s_main));
-        int* d_gate = &P.gs->pad0;
         for (int64_t outer = 0; outer < n_outer; ++outer) {                                                    // :121
-            KR_TRY(pg_logic(ctx, ws.red, PgCycleLogic{lc, P}));
-            KR_TRY(launch_ew(ctx, PgDivOp{&P.gs->beta, r0, V[0]}, n, done));                                    // :124
+            KR_TRY(logic_only(ctx, ws.red, PgCycleLogic{lc, P}));
+            KR_TRY(launch_ew(ctx, DivOp{&P.gs->beta, r0, V[0]}, n, done));                                    // :124
             for (int j = 0; j < R; ++j) {
-                // the SpMV / pc hooks take one flag: done || cyc_stop, copied into pad0
-                hipLaunchKernelGGL(pg_gate_kernel, dim3(1), dim3(1), 0, ctx->s_main, done, &P.gs->cyc_stop, d_gate);
-                KR_HIP(hipGetLastError());
+                KR_TRY(write_cycle_gate(ctx, gcyc, d_gate));
                 KR_TRY(launch_spmv(a, V[j], w, 0, nullptr, d_gate));                                             // :151 / :163
                 if (pc) { rc = pc_apply_dev_fresh(pc, n, w, z, d_gate, nullptr); if (rc) return rc; }              // :152-156
                 // (v_i, w) for i = 0..j (:174-179) and (w, w) (:225) in one pass
                 PgPass ps{};
                 ps.q = d_qptr; ps.nb = j + 1; ps.qx = wsel; ps.w = d_qptr + R + 1; ps.s = 1; ps.dots = 1; ps.n = n;
                 KR_TRY(pg_pass(ctx, ps, j + 2, P.red, buf, gcyc));
-                KR_TRY(pg_logic(ctx, ws.red, PgStepLogic{lc, P, j}));
+                KR_TRY(logic_only(ctx, ws.red, PgStepLogic{lc, P, j}));
                 KR_TRY(launch_ew_gated(ctx, PgMulOp{&P.gs->inv, wsel, V[j + 1]}, n, gcyc));                    // :227-233
             }
-            KR_TRY(pg_logic(ctx, ws.red, PgBackLogic{lc, P, 0}));
-            KR_TRY(launch_ew(ctx, PgUpdateOp{P.gs, P.y, d_qptr, xk, xk, 0}, n, done));                          // :289-295
+            KR_TRY(logic_only(ctx, ws.red, PgBackLogic{lc, P, 0}));
+            KR_TRY(launch_ew(ctx, BasisUpdateOp<false>{&P.gs->m, P.y, d_qptr, xk}, n, done));                   // :289-295
             KR_TRY(residual_dot(a, bv->d, xk, r0, tmp, done));                                                  // :298-302
             KR_TRY((reduce_then<1>(ctx, nt, ws.red, PgCycleEndLogic{lc, P})));
             KR_HIP(hipStreamSynchronize(ctx->s_main));                                                          // one host sync per cycle
@@ -598,8 +513,8 @@ int32_t pca_gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32
         PgState hs{};
         KR_TRY(read_pg(ctx, P.gs, &hs));
         while (!ctx->h_prog->done) {
-            KR_TRY(pg_logic(ctx, ws.red, PgCycleLogic{lc, P}));
-            KR_TRY(launch_ew(ctx, PgDivOp{&P.gs->beta, r0, V[0]}, n, done));                                    // q0 = r0 / ||r0||
+            KR_TRY(logic_only(ctx, ws.red, PgCycleLogic{lc, P}));
+            KR_TRY(launch_ew(ctx, DivOp{&P.gs->beta, r0, V[0]}, n, done));                                    // q0 = r0 / ||r0||
             int j = 0;
             long long it = hs.iteration;
             while (true) {
@@ -613,7 +528,7 @@ int32_t pca_gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32
                     KR_TRY(launch_spmv(a, zin, W[cc], 0, nullptr, done));
                     KR_TRY(launch_ew(ctx, DotOneOp{W[cc], W[cc]}, n, done));
                     KR_TRY((reduce_then<1>(ctx, nt, ws.red, PgNuLogic{lc, P, cc})));
-                    if (cc + 1 < s_eff) KR_TRY(launch_ew(ctx, PgDivOp{P.nu + cc, W[cc], u}, n, done));
+                    if (cc + 1 < s_eff) KR_TRY(launch_ew(ctx, DivOp{P.nu + cc, W[cc], u}, n, done));
                 }
                 const int nb = j + 1, ng = s_eff * (s_eff + 1) / 2;
                 PgPass ps{};
@@ -624,10 +539,10 @@ int32_t pca_gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32
                 KR_TRY(pg_pass(ctx, ps, nb * s_eff, P.c2, buf, gdone));
                 ps.coef = P.c2; ps.dots = 2;                                                  // pass C: W -= Q C2, G1 = W^T W
                 KR_TRY(pg_pass(ctx, ps, ng, P.g1, buf, gdone));
-                KR_TRY(pg_logic(ctx, ws.red, PgChol1Logic{lc, P, s_eff}));
+                KR_TRY(logic_only(ctx, ws.red, PgChol1Logic{lc, P, s_eff}));
                 ps.update = 2; ps.rm = P.r1; ps.rs = S; ps.out = d_wptr; ps.sdev = &P.gs->keep; ps.dots = 2;   // pass D: W R1^-1, G2
                 KR_TRY(pg_pass(ctx, ps, ng, P.g2, buf, gdone));
-                KR_TRY(pg_logic(ctx, ws.red, PgBlockLogic{lc, P, j, s_eff}));
+                KR_TRY(logic_only(ctx, ws.red, PgBlockLogic{lc, P, j, s_eff}));
                 ps.rm = P.r2; ps.out = d_qptr + j + 1; ps.dots = 0;                           // pass E: Q_new = W R2^-1
                 KR_TRY(pg_pass(ctx, ps, 0, nullptr, buf, gdone));
                 KR_TRY(read_pg(ctx, P.gs, &hs));                                               // one host sync per block
@@ -636,8 +551,8 @@ int32_t pca_gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32
                 j = hs.j;
             }
             // cycle end: x += M^-1 (Q y), the true residual
-            KR_TRY(pg_logic(ctx, ws.red, PgBackLogic{lc, P, 1}));
-            KR_TRY(launch_ew(ctx, PgUpdateOp{P.gs, P.y, d_qptr, nullptr, tmp, 1}, n, done));
+            KR_TRY(logic_only(ctx, ws.red, PgBackLogic{lc, P, 1}));
+            KR_TRY(launch_ew(ctx, BasisUpdateOp<true>{&P.gs->m, P.y, d_qptr, tmp}, n, done));
             const double* add = tmp;
             if (pc) { rc = pc_apply_dev_fresh(pc, n, tmp, z, done, nullptr); if (rc) return rc; add = z; }
             KR_TRY(launch_ew(ctx, PgAddOp{add, xk}, n, done));
@@ -647,16 +562,7 @@ int32_t pca_gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32
             mon.poll();
         }
     }
-    KR_HIP(hipStreamSynchronize(ctx->s_main));
-    const int32_t status = finish_solve(ws, io);
-    if (status == KRYST_OK)
-        KR_HIP(hipMemcpyAsync(xv->d, xk, padded_bytes(n), hipMemcpyDeviceToDevice, ctx->s_main));                // :310
-    KR_HIP(hipStreamSynchronize(ctx->s_main));
-    if (io.monitor) {
-        DevState h;
-        if (read_state(ws, &h) == hipSuccess) mon.upto(h.hist_len);
-    }
-    return status;
+    return run.end(xk);
 }
 
 }  // namespace kr

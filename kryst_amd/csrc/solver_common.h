@@ -94,6 +94,13 @@ __global__ void logic_kernel(const double* red, L logic) {
     if (logic.c.st->done && !L::RUN_WHEN_DONE) return;
     if (threadIdx.x == 0) logic.run(red);
 }
+// a scalar step that follows no inner product: thread 0 of one wave runs it, on the values the last fold left in `red`
+template <class L>
+inline int32_t logic_only(kryst_ctx_t ctx, const double* red, const L& l) {
+    hipLaunchKernelGGL((logic_kernel<L>), dim3(1), dim3(64), 0, ctx->s_main, red, l);
+    KR_HIP(hipGetLastError());
+    return KRYST_OK;
+}
 // several ranks: fold the all-gathered rank results in rank order (total = r0; total = total + r_p), then the logic
 template <int NQ, class L>
 __global__ void rank_fold_logic_kernel(const double* gathered, int nranks, const unsigned int* err, double* red_out, L logic) {

@@ -457,8 +457,7 @@ struct CgRun : SolverRun {
             KR_TRY(launch_ew(ctx, DotPairOp{pp, pp, xw, xw}, n, done));
             KR_TRY((reduce_then<2>(ctx, nt, ws.red, CgRadiusLogic{lc, prm.radius})));
             KR_TRY(launch_ew_gated(ctx, AxpyIfOp{ws.st, pp, xw}, n, GateIfEarly{ws.st}));
-            hipLaunchKernelGGL((logic_kernel<ClearEarlyLogic>), dim3(1), dim3(64), 0, ctx->s_main, ws.red, ClearEarlyLogic{lc});
-            KR_HIP(hipGetLastError());
+            KR_TRY(logic_only(ctx, ws.red, ClearEarlyLogic{lc}));
         }
         const bool nat = prm.norm_type == 2;
         if (nat) KR_TRY(launch_ew(ctx, CgUpdate2{&ws.st->alpha, pp, ap, xw, r}, n, done));
@@ -474,8 +473,7 @@ struct CgRun : SolverRun {
             KR_TRY((reduce_then<1>(ctx, nt, ws.red, StoreLogic{lc, &ws.st->omega})));
             KR_TRY(launch_ew(ctx, DotOneOp{xw, bv->d}, n, done));                                 // (x, b)
             KR_TRY((reduce_then<1>(ctx, nt, ws.red, CgObjLogic{lc, &ws.st->omega, prm.obj_target})));
-            hipLaunchKernelGGL((logic_kernel<CgBetaStoredLogic>), dim3(1), dim3(64), 0, ctx->s_main, ws.red, CgBetaStoredLogic{lc});
-            KR_HIP(hipGetLastError());
+            KR_TRY(logic_only(ctx, ws.red, CgBetaStoredLogic{lc}));
         }
         if (keep_in_cache(n)) return launch_ew(ctx, AypxDevOp<true>{&ws.st->beta, r, pp}, n, done);
         return launch_ew(ctx, AypxDevOp<false>{&ws.st->beta, r, pp}, n, done);                           // :274-276

@@ -60,6 +60,23 @@ def test_fgmres_bit_exact(ctx, rs, orthog, pcname, restart):
     assert st.final_residual == np.sqrt(O.dot(b, b, rs))          # the stats quirk: the INITIAL residual norm
 
 
+@pytest.mark.parametrize("restart", [1, 2, 7, 33])
+def test_fgmres_small_arrays_at_odd_restarts(ctx, rs, restart):
+    """H, the rotations, s, h_col, y, the state struct, the gate word and the table of z pointers are slices of one allocation
+    (restart_common.h: SmallArena), sized by R = min(restart, max_iters) except s (restart + 2).  Odd element counts in every slice, with
+    R == restart and with max_iters < restart (R < restart): a wrong slice size or alignment moves a neighbour."""
+    a = O.stencil7(8, "convdiff")
+    assert a.nrows == 512
+    b = a.spmv(np.ones(a.nrows))
+    d = to_dev(ctx, a)
+    for mx in sorted({40, restart - 1} - {0}):
+        for orthog in (K.Orthog.Classical, K.Orthog.Modified):
+            res = O.solve("fgmres", a, b, pc=O.Pc.jacobi(a), tol=1e-8, max_iters=mx, restart=restart, rs=rs, orthog=int(orthog))
+            s = K.FgmresSolver(1e-8, mx, restart).with_orthog(orthog)
+            x = np.zeros(a.nrows)
+            check(res, s.solve_flex(d, K.Jacobi().setup(d), b, x), s, x)
+
+
 def test_fgmres_large_batches_and_serial_agreement(ctx, rs):
     # restart 40: dot/axpy batches of 8, 4, 2 and 1 all occur; vs the strict serial fold: equal counts, close history
     a = O.stencil7(12, "convdiff")

@@ -11,6 +11,7 @@ from oracle import oracle as O
 import asm_ref as A
 import sor_ref as S
 import bjacobi_ref as BR
+import pca_gmres_ref as PR
 from test_gpu_block_jacobi import sets_ref
 from test_gpu_spai import check_values
 
@@ -217,3 +218,71 @@ def test_setups_and_failed_setups_give_back_their_device_memory(ctx):
     assert released >= 8 * n + 64 * n, released
     assert free_bytes() == before
 
+
+# ------------------------------------------------------------------------------------------------ 4. the restarted solvers' scaffold
+PCN = K.Preconditioning
+RESTARTED = {        # name -> a fresh solver; every one of them applies the preconditioner it is given
+    "gmres_left": lambda: K.GmresSolver(5, 1e-8, 40).with_preconditioning(PCN.Left),
+    "gmres_right": lambda: K.GmresSolver(5, 1e-8, 40).with_preconditioning(PCN.Right),
+    "gmres_left_textbook": lambda: K.GmresSolver(5, 1e-8, 40).with_preconditioning(PCN.LeftTextbook),
+    "fgmres": lambda: K.FgmresSolver(1e-8, 40, 5),
+    "pca_gmres_right": lambda: K.PcaGmresSolver(5, 1, 1, 1e-8, 40).with_preconditioning(PCN.Right),
+    "sstep_right": lambda: K.PcaGmresSolver(5, 1, 3, 1e-8, 40).with_preconditioning(PCN.Right).with_textbook(),
+}
+
+
+def test_restarted_solvers_reject_a_preconditioner_of_another_size(ctx):
+    """A sized preconditioner launches over its own n: one built on another operator is an argument error (KRYST_ERR_ARG, what PCG
+    answers), raised before any device work, and x comes back as it went in.  The sizeless Identity still serves both operators."""
+    ops = [O.stencil7(N, "poisson") for N in (8, 9)]
+    assert [a.nrows for a in ops] == [512, 729]
+    devs = [to_dev(ctx, a) for a in ops]
+    jac = [K.Jacobi().setup(d) for d in devs]
+    ident = K.IdentityPc().setup(devs[0])
+    for k in (0, 1):
+        a, d, n = ops[k], devs[k], ops[k].nrows
+        bv = K.DeviceVec(ctx, a.spmv(np.linspace(0.5, 1.5, n)))
+        x_in = np.random.default_rng(k).standard_normal(n)
+        for name, make in RESTARTED.items():
+            xv = K.DeviceVec(ctx, x_in)
+            with pytest.raises(K.KError) as e:
+                make().solve(d, jac[1 - k], bv, xv)
+            assert e.value.code == 102, (n, name)
+            assert np.array_equal(xv.to_host(), x_in), (n, name)
+            xv = K.DeviceVec(ctx, x_in)
+            st = make().solve(d, ident, bv, xv)
+            assert st.iterations > 1 and np.all(np.isfinite(xv.to_host())), (n, name)
+
+
+@pytest.mark.parametrize("restart", [1, 2, 7, 33])
+def test_restarted_solvers_small_arrays_at_odd_restarts(ctx, restart):
+    """H, g, the rotations, y, the state struct, the gate word and the pointer tables of a solve are slices of one allocation
+    (restart_common.h: SmallArena).  At these restart values (and s-step blocks of 1, 3 and 16) every slice has an odd element count, so a
+    wrong slice size or alignment moves a neighbour: each whole solve is bit for bit its oracle's -- history, iteration count and x."""
+    rs = O.Reduce.tiled(*K.reduce_spec())
+    a = O.stencil7(8, "convdiff")
+    assert a.nrows == 512
+    d = to_dev(ctx, a)
+    b = a.spmv(np.ones(a.nrows))
+    x0 = np.linspace(-0.5, 0.5, a.nrows)
+    kpc, opc = K.Jacobi().setup(d), O.Pc.jacobi(a)
+
+    def same(ref, st, s, x):
+        assert (st.iterations, st.converged, st.final_residual) == (ref.iterations, ref.converged, ref.final_residual), (st, ref)
+        assert np.array_equal(np.array(s.residual_history), ref.history) and np.array_equal(x, ref.x)
+
+    for side in (PCN.NoPc, PCN.Left, PCN.Right, PCN.LeftTextbook):
+        pcs = (None, None) if side == PCN.NoPc else (kpc, opc)
+        ref = O.solve("gmres", a, b, x0=x0, pc=pcs[1], tol=1e-8, max_iters=40, restart=restart, side=int(side), rs=rs)
+        s = K.GmresSolver(restart, 1e-8, 40).with_preconditioning(side)
+        x = x0.copy()
+        same(ref, s.solve(d, pcs[0], b, x), s, x)
+    ref = PR.as_written(a, b, pc=opc, side=int(PCN.Right), restart=restart, tol=1e-8, max_iters=40, rs=rs)
+    s = K.PcaGmresSolver(restart, 1, 1, 1e-8, 40).with_preconditioning(PCN.Right)
+    x = x0.copy()
+    same(ref, s.solve(d, kpc, b, x), s, x)
+    for sb in (1, 3, 16):
+        ref = PR.sstep(a, b, x=x0, pc=opc, side=2, restart=restart, block_size=sb, tol=1e-8, max_iters=40, rs=rs)
+        s = K.PcaGmresSolver(restart, 1, sb, 1e-8, 40).with_preconditioning(PCN.Right).with_textbook()
+        x = x0.copy()
+        same(ref, s.solve(d, kpc, b, x), s, x)
