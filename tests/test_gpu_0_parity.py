@@ -11,6 +11,7 @@ import pytest
 
 import kryst_amd as K
 from oracle import oracle as O
+from nonfinite_cases import box_operator as _box_operator
 
 pytestmark = pytest.mark.gpu
 
@@ -714,37 +715,6 @@ def test_structured_grid_triangular_solve_bit_exact(ctx, grid_path, monkeypatch)
             for _ in range(2):
                 r = rng.standard_normal(a.nrows)
                 assert np.array_equal(pc.apply(r), ref.apply(r)), (grid_path, a.nrows)
-
-
-def _box_operator(rng, Ni, Nj, Nk, keep, drop=0.0, unsym=True, zeros=0.0):
-    """A stencil operator inside the 3 x 3 x 3 cube on an Ni x Nj x Nk box, natural ordering: `keep(dk, dj, di)` selects the couplings (27-point: all),
-    a fraction `drop` of the couplings is removed at random, the values are random (unsymmetric), the diagonal dominates."""
-    import scipy.sparse as sp
-    n = Ni * Nj * Nk
-    idx = np.arange(n)
-    i, j, k = idx % Ni, (idx // Ni) % Nj, idx // (Ni * Nj)
-    rows, cols, vals = [], [], []
-    for dk in (-1, 0, 1):
-        for dj in (-1, 0, 1):
-            for di in (-1, 0, 1):
-                if (dk, dj, di) == (0, 0, 0) or not keep(dk, dj, di):
-                    continue
-                ok = (i + di >= 0) & (i + di < Ni) & (j + dj >= 0) & (j + dj < Nj) & (k + dk >= 0) & (k + dk < Nk)
-                if drop > 0.0:
-                    ok &= rng.random(n) >= drop
-                r = idx[ok]
-                rows.append(r); cols.append(r + di + Ni * dj + Ni * Nj * dk)
-                v = -rng.uniform(0.2, 1.0, len(r)) if unsym else -np.ones(len(r))
-                if zeros > 0.0:
-                    v[rng.random(len(v)) < zeros] = 0.0                    # stored zeros: part of the pattern, never kept in a factor
-                vals.append(v)
-    rows, cols, vals = np.concatenate(rows), np.concatenate(cols), np.concatenate(vals)
-    dsum = np.ones(n)
-    np.add.at(dsum, rows, np.abs(vals))
-    m = sp.coo_matrix((np.concatenate([vals, dsum]), (np.concatenate([rows, idx]), np.concatenate([cols, idx]))), shape=(n, n)).tocsr()
-    m.sort_indices()
-    assert zeros == 0.0 or (m.data == 0.0).any()                           # the zeros are stored
-    return O.Csr(n, n, m.indptr, m.indices, m.data)
 
 
 @pytest.mark.parametrize("form", ["wave", "box", "levels"])
