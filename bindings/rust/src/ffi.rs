@@ -118,6 +118,7 @@ extern "C" {
     pub fn kryst_bench_csr_skeleton(a: Csr, x: Vecd, y: Vecd, reps: i32, avg_ms: *mut f64) -> i32;
     pub fn kryst_bench_spmv_fused(a: Csr, x: Vecd, y: Vecd, reps: i32, avg_ms: *mut f64) -> i32;
     pub fn kryst_bench_poison_lds(ctx: Ctx) -> i32;
+    pub fn kryst_bench_vec_padding(v: Vecd, fill: *const f64, dirty: *mut i64) -> i32;
 
     pub fn kryst_dot(x: Vecd, y: Vecd, out: *mut f64) -> i32;
     pub fn kryst_norm(x: Vecd, out: *mut f64) -> i32;

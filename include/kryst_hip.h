@@ -122,7 +122,7 @@ int32_t kryst_vec_len(kryst_vec_t v, int64_t* n);
 int32_t kryst_vec_upload(kryst_vec_t v, const double* host, int64_t n);
 int32_t kryst_vec_download(kryst_vec_t v, double* host, int64_t n);
 int32_t kryst_vec_fill(kryst_vec_t v, double value);
-int32_t kryst_vec_copy(kryst_vec_t dst, kryst_vec_t src);
+int32_t kryst_vec_copy(kryst_vec_t dst, kryst_vec_t src);             /* dst == src: allowed, nothing is done */
 /* deterministic synthetic fill on device: v[i] = uniform[0,1) from splitmix64(seed, global index) */
 int32_t kryst_vec_fill_splitmix(kryst_vec_t v, uint64_t seed, int64_t global_offset);
 
@@ -167,7 +167,8 @@ int32_t kryst_csr_download(kryst_csr_t a, int64_t* row_ptr, int32_t* col_idx_loc
  * *tries homes tried, *chosen the one kept, skeleton_ms8[8] the skeleton's milliseconds per launch on each home tried. */
 int32_t kryst_csr_placement_info(kryst_csr_t a, int32_t* tries, int32_t* chosen, double* skeleton_ms8);
 
-/* MatVec::matvec (src/core/traits.rs:4-7) == SparseMatrix::spmv (sparse.rs:56-67): y <- A x, y overwritten */
+/* MatVec::matvec (src/core/traits.rs:4-7) == SparseMatrix::spmv (sparse.rs:56-67): y <- A x, y overwritten.  REFUSED: x and y the same
+ * vector (KRYST_ERR_ARG before any launch, y unchanged); the same holds for kryst_spmv_transpose. */
 int32_t kryst_spmv(kryst_csr_t a, kryst_vec_t x, kryst_vec_t y);
 /* MatTransVec::mattransvec (src/core/traits.rs; the reference's CsrMatrix has none): y <- A^T x, x of length nrows, y of length
  * ncols (rectangular operators allowed).  A^T is built on the device by the first call -- row j lists column j of A in ascending row
@@ -196,8 +197,18 @@ int32_t kryst_bench_spmv_fused(kryst_csr_t a, kryst_vec_t x, kryst_vec_t y, int3
 /* test hook: fills the LDS of every compute unit with NaNs.  LDS is not cleared between kernels, so whatever a kernel reads from LDS
  * before writing it is what an earlier kernel -- of any process -- left there; a round-4 kernel did, and was wrong on one GPU box in five */
 int32_t kryst_bench_poison_lds(kryst_ctx_t ctx);
+/* test hook (ABI 6): what lies behind a vector's end.  A vector of n elements is allocated as ceil(n / 512) * 512 + 512 doubles, zero at
+ * creation; kernels read past n (16-byte pair loads, shifted and clamped windows) and the pointwise kernels write the whole last tile.
+ * Results depend on the first n elements only and the padding after any operation is unspecified; this hook lets a
+ * test put something there.  *dirty (may be NULL) receives the number of allocated elements at index >= n whose 64 bits are not +0.0,
+ * counted BEFORE any fill; if fill is not NULL every allocated element at index >= n -- the rest of the last tile and the whole extra tile,
+ * ceil(n / 512) * 512 + 512 - n elements -- is then set to *fill.  Ordinary stores on the compute stream; elements < n are untouched. */
+int32_t kryst_bench_vec_padding(kryst_vec_t v, const double* fill, int64_t* dirty);
 
-/* ---- BLAS-1: InnerProduct for () (src/core/wrappers.rs:90-127) and the solvers' pointwise loops ---- */
+/* ---- BLAS-1: InnerProduct for () (src/core/wrappers.rs:90-127) and the solvers' pointwise loops ----
+ * Operands that share storage are ALLOWED here and defined element by element: kryst_dot(v, v), kryst_axpy(al, v, v) = v + al * v,
+ * kryst_aypx(be, v, v) = v + be * v, kryst_sub with out, a and b the same or different in any combination (every element is read
+ * before it is written, by the thread that writes it). */
 int32_t kryst_dot(kryst_vec_t x, kryst_vec_t y, double* out);       /* wrappers.rs:90-108 */
 int32_t kryst_norm(kryst_vec_t x, double* out);                     /* wrappers.rs:110-127 */
 int32_t kryst_axpy(double alpha, kryst_vec_t x, kryst_vec_t y);     /* y[i] = y[i] + alpha*x[i]   cg.rs:207-209 */
@@ -317,7 +328,10 @@ int32_t kryst_pc_amg_info(kryst_pc_t pc, int32_t* nlevels, int64_t* rows, int64_
  * P / R of the last level are empty (0 x 0).  row_ptr == NULL: the sizes only; else row_ptr (nrows + 1), col and val (*nnz each). */
 int32_t kryst_pc_amg_export(kryst_pc_t pc, int32_t level, int32_t which, int64_t* nrows, int64_t* ncols, int64_t* nnz, int64_t* row_ptr,
                             int32_t* col, double* val);
-int32_t kryst_pc_apply(kryst_pc_t pc, kryst_vec_t r, kryst_vec_t z);                /* Preconditioner::apply */
+/* Preconditioner::apply(&self, r: &V, z: &mut V).  REFUSED for every kind: r and z the same handle or the same device storage
+ * (KRYST_ERR_ARG before any launch, both vectors unchanged) -- the Rust signature cannot alias either, and most applies would race or
+ * overwrite their own input.  The same rule holds for kryst_bench_pc_apply and kryst_apply_chebyshev. */
+int32_t kryst_pc_apply(kryst_pc_t pc, kryst_vec_t r, kryst_vec_t z);
 int32_t kryst_pc_destroy(kryst_pc_t pc);
 /* measurement hooks (bench.py): average ms of `reps` back-to-back applies between two HIP events on the compute stream; and what
  * an ILU-family preconditioner's apply runs and streams -- info[0] form (0 level-ordered, 1 grid 8 x 8 lines per workgroup,
@@ -367,7 +381,8 @@ int32_t kryst_cg_solve      (const double* b, double* x, int64_t n, KRYST_SOLVE_
 int32_t kryst_pcg_solve     (const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS);  /* PcgSolver::solve      pcg.rs:114-222 */
 int32_t kryst_gmres_solve   (const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS);  /* GmresSolver::solve    gmres.rs:216-402 */
 int32_t kryst_bicgstab_solve(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS);  /* BiCgStabSolver::solve bicgstab.rs:69-293 */
-/* same with b, x resident in HBM (the performant drop-in; bench.py times these) */
+/* same with b, x resident in HBM (the performant drop-in; bench.py times these).  ALLOWED for every *_solve_dev and for a stepping
+ * session: b and x the same vector (x0 = b; every solver iterates on a copy and writes x once at the end: the vector holds x afterwards) */
 int32_t kryst_cg_solve_dev      (kryst_vec_t b, kryst_vec_t x, KRYST_SOLVE_ARGS);
 int32_t kryst_pcg_solve_dev     (kryst_vec_t b, kryst_vec_t x, KRYST_SOLVE_ARGS);
 int32_t kryst_gmres_solve_dev   (kryst_vec_t b, kryst_vec_t x, KRYST_SOLVE_ARGS);

@@ -171,6 +171,21 @@ class DeviceVec:
         check(lib().kryst_vec_copy(self.h, other.h))
         return self
 
+    QUIET_NAN_BITS = 0x7FF8000000000000
+
+    def poison_padding(self, value=None):
+        """Test hook (kryst_bench_vec_padding): every allocated element behind the n-th -- the rest of the last 512-element tile and the
+        whole extra tile -- becomes `value` (default: the quiet NaN 0x7FF8000000000000).  Results must not depend on it."""
+        fill = np.array([self.QUIET_NAN_BITS], dtype=np.uint64).view(np.float64) if value is None else np.array([value], dtype=np.float64)
+        check(lib().kryst_bench_vec_padding(self.h, _dp(fill), None))
+        return self
+
+    def padding_dirty(self):
+        """How many allocated elements behind the n-th are not +0.0 (kryst_bench_vec_padding)."""
+        dirty = C.c_int64(-1)
+        check(lib().kryst_bench_vec_padding(self.h, None, C.byref(dirty)))
+        return dirty.value
+
     def __del__(self):
         try:
             if self.h and self.ctx.h:

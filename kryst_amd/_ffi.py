@@ -84,6 +84,7 @@ SIGNATURES = {
     "kryst_bench_csr_skeleton": (C.c_int32, [Handle, Handle, Handle, C.c_int32, c_dp]),
     "kryst_bench_spmv_fused": (C.c_int32, [Handle, Handle, Handle, C.c_int32, c_dp]),
     "kryst_bench_poison_lds": (C.c_int32, [Handle]),
+    "kryst_bench_vec_padding": (C.c_int32, [Handle, c_dp, c_i64p]),
     "kryst_dot": (C.c_int32, [Handle, Handle, c_dp]),
     "kryst_norm": (C.c_int32, [Handle, c_dp]),
     "kryst_axpy": (C.c_int32, [C.c_double, Handle, Handle]),

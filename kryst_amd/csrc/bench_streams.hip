@@ -348,6 +348,40 @@ extern "C" int32_t kryst_bench_poison_lds(kryst_ctx_t ctx) {
     return KRYST_OK;
 }
 
+namespace kr {
+// one workgroup: the allocation behind a vector's n elements is the rest of its last tile and one more tile, 512 .. 1023 doubles
+__global__ __launch_bounds__(2 * KR_TILE) void vec_padding_kernel(double* d, int64_t n, int64_t cap, int do_fill, double fill, int64_t* dirty) {
+    __shared__ int count;
+    if (threadIdx.x == 0) count = 0;
+    __syncthreads();
+    const int64_t i = n + threadIdx.x;
+    if (i < cap) {
+        if (__double_as_longlong(d[i]) != 0ll) atomicAdd(&count, 1);     // counted before the fill: anything but +0.0
+        if (do_fill) d[i] = fill;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) *dirty = count;
+}
+}  // namespace kr
+
+extern "C" int32_t kryst_bench_vec_padding(kryst_vec_t v, const double* fill, int64_t* dirty) {
+    KR_ARG(v, "bench_vec_padding");
+    kryst_ctx_t ctx = v->ctx;
+    KR_HIP(hipSetDevice(ctx->device));
+    const int64_t cap = (v->n + KR_TILE - 1) / KR_TILE * KR_TILE + KR_TILE;     // kryst_vec_create
+    int64_t* d_count = nullptr;
+    KR_HIP(hipMalloc(&d_count, sizeof(int64_t)));
+    hipLaunchKernelGGL(kr::vec_padding_kernel, dim3(1), dim3(2 * KR_TILE), 0, ctx->s_main, v->d, v->n, cap, fill ? 1 : 0, fill ? *fill : 0.0, d_count);
+    int64_t count = 0;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->s_main);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->s_main);
+    (void)hipFree(d_count);
+    KR_HIP(e);
+    if (dirty) *dirty = count;
+    return KRYST_OK;
+}
+
 extern "C" int32_t kryst_bench_csr_skeleton(kryst_csr_t a, kryst_vec_t x, kryst_vec_t y, int32_t reps, double* avg_ms) {
     KR_ARG(a && x && y && avg_ms && reps >= 1, "bench_csr_skeleton");
     KR_ARG(x->n == a->xlen && y->n == a->nrows && a->nrows == a->xlen && !a->dist, "bench_csr_skeleton: a square single-rank operator and vectors of its size");

@@ -206,6 +206,7 @@ int32_t kryst_vec_fill(kryst_vec_t v, double value) {
 
 int32_t kryst_vec_copy(kryst_vec_t dst, kryst_vec_t src) {
     KR_TRY(vec_check2(dst, src));
+    if (dst == src || dst->d == src->d) return KRYST_OK;                    // a vector onto itself: nothing to do
     KR_HIP(hipSetDevice(dst->ctx->device));
     KR_HIP(hipMemcpyAsync(dst->d, src->d, sizeof(double) * (size_t)padded(src->n), hipMemcpyDeviceToDevice, dst->ctx->s_main));
     return KRYST_OK;

@@ -208,6 +208,7 @@ int32_t kryst_pc_apply(kryst_pc_t pc, kryst_vec_t r, kryst_vec_t z) {
     KR_ARG(pc && r && z, "pc_apply");
     KR_ARG(r->ctx == pc->ctx && z->ctx == pc->ctx, "pc_apply: context mismatch");
     KR_ARG(r->n == z->n, "pc_apply: length mismatch");
+    KR_ARG(r != z && r->d != z->d, "pc_apply: r and z alias");              // apply(&self, r: &V, z: &mut V): one rule for every kind
     KR_ARG(pc->n < 0 || pc->n == r->n, "pc_apply: vector length != operator size");
     KR_HIP(hipSetDevice(pc->ctx->device));
     KR_TRY(pc_apply_dev(pc, r->n, r->d, z->d, nullptr));
@@ -227,6 +228,7 @@ int32_t kryst_pc_apply(kryst_pc_t pc, kryst_vec_t r, kryst_vec_t z) {
 int32_t kryst_bench_pc_apply(kryst_pc_t pc, kryst_vec_t r, kryst_vec_t z, int32_t reps, double* avg_ms) {
     KR_ARG(pc && r && z && avg_ms && reps >= 1, "bench_pc_apply");
     KR_ARG(r->ctx == pc->ctx && z->ctx == pc->ctx && r->n == z->n && pc->n == r->n, "bench_pc_apply: size or context mismatch");
+    KR_ARG(r != z && r->d != z->d, "bench_pc_apply: r and z alias");
     kryst_ctx_t ctx = pc->ctx;
     KR_HIP(hipSetDevice(ctx->device));
     KR_TRY(pc_apply_dev(pc, r->n, r->d, z->d, nullptr));
@@ -254,6 +256,7 @@ int32_t kryst_pc_destroy(kryst_pc_t pc) {
 int32_t kryst_apply_chebyshev(kryst_csr_t a, kryst_vec_t r, kryst_vec_t z, double alpha, double beta, int64_t m) {
     KR_ARG(a && r && z && m >= 0, "apply_chebyshev");
     KR_ARG(r->n == a->nrows && z->n == a->nrows && a->nrows == a->xlen, "apply_chebyshev: size mismatch");
+    KR_ARG(r != z && r->d != z->d, "apply_chebyshev: r and z alias");
     KR_HIP(hipSetDevice(a->ctx->device));
     double *v0 = nullptr, *v1 = nullptr, *v2 = nullptr;
     int32_t rc = alloc_vec(a->ctx, &v0, a->nrows);
