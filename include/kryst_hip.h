@@ -160,6 +160,12 @@ int32_t kryst_csr_tile_order(kryst_csr_t a, int64_t* info);
  * offsets are the same in every pattern, info[2] first tile of a rank's contiguous interior range (-1: none), info[3] 1 if kryst_spmv
  * takes that kernel now */
 int32_t kryst_csr_pattern_info(kryst_csr_t a, int64_t* info);
+/* measurement hook: the marching mode of the fused direction + SpMV kernel of CG / PCG (a workgroup keeps a strip of 512 T rows of a grid
+ * plane and walks a segment of S planes, the operands one plane away come out of its own LDS windows; results are the same bits).  With the
+ * KRYST_SPMV_FUSE_* settings as they are now: info[0] 1 if the operator's shape allows it (far offsets of +- one plane, a plane that is a
+ * whole number of strips, a box that is a whole number of planes, lines of at most 512 points), info[1] 1 if a fused launch takes it now,
+ * info[2] T, info[3] strips per plane, info[4] S, info[5] segments (info[3 .. 5] 0 when not eligible) */
+int32_t kryst_csr_fuse_march_info(kryst_csr_t a, int64_t* info);
 int32_t kryst_csr_download(kryst_csr_t a, int64_t* row_ptr, int32_t* col_idx_local, double* vals);
 /* Measurement hook (ABI 5): where the CSR arrays live.  The same plain-CSR stream mix runs at 0.70 .. 0.76 of the HBM peak depending on where
  * the driver put the three arrays (round 4, 512^3), so a single-rank creation may try several homes for (row_ptr, col, val) -- K =

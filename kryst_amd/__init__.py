@@ -352,6 +352,13 @@ class CsrMatrix:
         check(lib().kryst_csr_pattern_info(self.h, info))
         return {"line": info[0], "uniform_far": bool(info[1]), "interior_first": info[2], "staged": bool(info[3])}
 
+    def fuse_march_info(self):
+        """Measurement hook (kryst_csr_fuse_march_info): the marching mode of the fused direction + SpMV kernel under the current
+        KRYST_SPMV_FUSE_* settings -- {"eligible", "on", "T", "strips", "S", "segments"}."""
+        info = (C.c_int64 * 6)()
+        check(lib().kryst_csr_fuse_march_info(self.h, info))
+        return {"eligible": bool(info[0]), "on": bool(info[1]), "T": info[2], "strips": info[3], "S": info[4], "segments": info[5]}
+
     def placement_info(self):
         """Where the CSR arrays live (kryst_csr_placement_info): {"tries", "chosen", "skeleton_ms": [...]} of the homes tried at creation."""
         t, c = C.c_int32(0), C.c_int32(0)

@@ -782,12 +782,195 @@ struct FuseArgs { const double* z; const double* p_old; double* p_new; double* x
 // XU: the deferred x update rides on this kernel (false: the solver updates x in batches, solvers.hip: XBatchOp -- no registers held for x)
 // (measured and not kept, round 5: runs of 8 tiles -- 166 registers, 3 waves per SIMD: 582-590 against 596 it/s; amdgpu_waves_per_eu(5): four
 // spilled registers, 565 against 596)
+//
+// MARCH (the marching mode; launch_spmv_fused_impl: fuse_march_plan decides).  The far operands of a row are the SAME (i, j) row one plane below and
+// above, so a workgroup that keeps its strip of R = 512 T consecutive rows of a plane and walks a segment of S planes along k holds them itself:
+// e[6] is read from the window of plane s + 1 at the LDS index of B, and e[0] is the lane's own B pair of plane s - 1, carried in registers (the
+// lane-to-row mapping is the same in every step).  Only the first and the last plane of a segment form a far operand from z and p_old in memory
+// (clamped at the ends of the box), as the un-marched kernel does for every tile: per own line 1 + (2 n + 4) / R + 2 / S lines of z and p_old are
+// requested instead of 3 + (2 n + 4) / R, and the halo lines are a neighbouring strip's own lines on the same XCD.
+//   LDS: TWO windows of R + 2 n + 4 doubles, W(s) and W(s + 1).  A step is
+//     a. request W(s + 2): z, p_old (and the owed x) of the whole window into REGISTERS, and the ids of plane s + 1 -- in flight under b.  (Not by
+//        LDS-DMA as the un-marched fill: beside a pending DMA the compiler drains vmcnt(0) before the first LDS read of b. and before every use of
+//        an ordinary load, which serialises the step; plain loads are counted exactly.  Both forms read at the same rate.)
+//     b. the tiles of plane s out of W(s) and W(s + 1), partials per wave into red;
+//     barrier 1: every wave has read W(s) for the last time;
+//     c. the cross-wave step of the partials (threads 0 .. T NQ - 1 out of red); p_new = z + beta p_old into the buffer that held W(s), own
+//        rows to p_new in memory, with the owed x update;
+//     barrier 2: W(s + 2) is complete; the buffers change roles.
+//   Every barrier against the loop: c. of step s overwrites W(s), whose last reads (A, B, C, M, P of b.) are before barrier 1 of step s, W(s + 1)
+//   is only read; b. of step s + 1 reads W(s + 2) after barrier 2 of step s; red is written in b. of step s + 1, after barrier 2 of step s, which
+//   its readers of c. reach only afterwards.  Both barriers are executed in every step by every wave: the branches around them depend on s and the
+//   segment's length alone (uniform over the workgroup).
+//   Grid: strips / 8 (rounded up) neighbouring strips per XCD, segment after segment: the workgroups resident on an XCD are neighbouring strips of
+//   the same planes (contiguous in memory at every step, halo lines shared in that XCD's L2), and a strip is on the same XCD in every segment.
+//   Which workgroup computes a tile changes and nothing else: per-element arithmetic, entry order, absent-entry selects and the per-tile partials
+//   (thread, wave butterfly, the four waves in turn, partials[tile]) are the un-marched kernel's -- the same bits.
+//   Registers: 164 at T = 4 without the x update (the un-marched instance: 98) -- a whole window of z and p_old is held across b. -- i.e. three waves per
+//   SIMD, one more than the two workgroups per CU the launch keeps resident need.  Measured at 512^3 (profiles/march/): HBM traffic 39.9 -> 35.4 bytes
+//   per row (model 34), the kernel 879 -> 843 us, CG 601 -> 628 it/s.
+//   a.group: strips per XCD; a.xcd_chunk: S; a.tpw: strips per plane; far_hi == -far_lo == the plane; every strip and every plane is whole.
 template <int NQ, int T, int NMAX, bool XU>
+__device__ __forceinline__ void fuse_march(const SpmvArgs& a, const FuseArgs& f, const int32_t n, const int32_t plane, unsigned char* smem, const bool ended, const bool owed) {
+    const int XS = T * KR_TILE + 2 * n + 4;                                  // elements of one window (even)
+    double* win = reinterpret_cast<double*>(smem);
+    uint2* meta = reinterpret_cast<uint2*>(win + 2 * XS);
+    double* pval = reinterpret_cast<double*>(meta + a.npat);
+    double* red = reinterpret_cast<double*>(smem + a.pat_red_off);
+    const int t = threadIdx.x;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int spx = a.group, S = a.xcd_chunk;
+    const int strip = xcd * spx + slot % spx, k0 = (slot / spx) * S;
+    const int nplanes = a.nrows / plane;
+    if (strip >= a.tpw || k0 >= nplanes) return;                             // (uniform over the workgroup)
+    const int ns = min(S, nplanes - k0);                                     // planes of this segment (the last one may be shorter)
+    const int32_t rbeg = k0 * plane + strip * (T * KR_TILE);                 // first row of the strip in the segment's first plane
+    const double al = *f.alpha, be = *f.beta;
+    if (ended) {                                                             // (uniform) only x += alpha p_old is still owed, on the segment's own rows
+        for (int s = 0; s < ns; ++s) {
+#pragma unroll
+            for (int k = 0; k < T; ++k) {
+                const int32_t row = rbeg + s * plane + k * KR_TILE + 2 * t;
+                const d2 pp = ld2(f.p_old, row), xx = ld2(f.xvec, row);
+                st2(f.xvec, row, xx.a + al * pp.a, xx.b + al * pp.b);
+            }
+        }
+        return;
+    }
+    constexpr int NP = (T * KR_TILE + 2 * NMAX + 4 + 2 * KR_T - 1) / (2 * KR_T);   // pairs per lane at most (n <= NMAX)
+    const int npairs = XS / 2;
+    const int32_t xsafe = (int32_t)a.xsafe;
+    const int own_lo = (n + 2) / 2, own_hi = own_lo + T * (KR_TILE / 2);    // window pairs that are rows of the strip
+    v2d zz[NP], po[NP], xo[XU ? NP : 1];
+    // a window's requests (r0: the strip's first row in that plane).  Every lane loads NP pairs: pairs past the window's end are clamped into it (and
+    // dropped by write_window) -- no branch around a load
+    auto request = [&](const int32_t r0) {
+        const int32_t e0 = r0 - n - 2;                                       // element at the window's [0] (even)
+        const bool inside = e0 >= 0 && e0 + XS <= xsafe;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int pi = min(t + i * KR_T, npairs - 1);
+            const int32_t e = inside ? e0 + 2 * pi : min(max(e0 + 2 * pi, 0), xsafe);     // outside x: any valid pair (those operands are absent entries)
+            po[i] = *reinterpret_cast<const v2d*>(f.p_old + e);
+            zz[i] = *reinterpret_cast<const v2d*>(f.z + e);
+            if constexpr (XU) { xo[i].x = 0.0; xo[i].y = 0.0; if (owed && pi >= own_lo && pi < own_hi) xo[i] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(f.xvec + e)); }     // (own rows are never clamped; read once)
+        }
+    };
+    // p_new = z + beta p_old (cg.rs:274-276 / pcg.rs:215-217, un-fused multiply and add) into the window; own rows also to memory, with their x update
+    auto write_window = [&](const int32_t r0, double* xs) {
+        const int32_t e0 = r0 - n - 2;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int pi = t + i * KR_T;
+            if (pi < npairs) {
+                v2d pn; pn.x = zz[i].x + be * po[i].x; pn.y = zz[i].y + be * po[i].y;
+                *reinterpret_cast<v2d*>(xs + 2 * pi) = pn;
+                if (pi >= own_lo && pi < own_hi) {
+                    const int32_t row = e0 + 2 * pi;
+                    st2(f.p_new, row, pn.x, pn.y);
+                    if constexpr (XU) { if (owed) st2(f.xvec, row, xo[i].x + al * po[i].x, xo[i].y + al * po[i].y); }
+                }
+            }
+        }
+    };
+    // a far operand the segment does not hold (below its first plane, above its last): formed the same way from z and p_old there
+    auto far_pair = [&](const int64_t row) {
+        const int64_t c = min(max(row, (int64_t)0), (int64_t)xsafe);
+        const v2d zf = *reinterpret_cast<const v2d*>(f.z + c), pf = *reinterpret_cast<const v2d*>(f.p_old + c);
+        v2d r; r.x = zf.x + be * pf.x; r.y = zf.y + be * pf.y;
+        return r;
+    };
+    unsigned ids[T], idn[T];
+    v2d prev[T], hi[T];
+    // ---- the segment's first two windows
+#pragma unroll
+    for (int k = 0; k < T; ++k) { ids[k] = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(a.pid + (size_t)rbeg + k * KR_TILE + 2 * t)); idn[k] = 0u; }
+    double* w0 = win; double* w1 = win + XS;                                 // W(s), W(s + 1)
+    request(rbeg);
+#pragma unroll
+    for (int k = 0; k < T; ++k) { prev[k] = far_pair((int64_t)rbeg + k * KR_TILE + 2 * t - plane); hi[k].x = 0.0; hi[k].y = 0.0; }
+    for (int i = t; i < a.npat; i += KR_T) meta[i] = reinterpret_cast<const uint2*>(a.pmeta)[i];
+    for (int i = t; i < a.ntab; i += KR_T) pval[i] = a.pval[i];
+    write_window(rbeg, w0);
+    if (ns > 1) {
+        request(rbeg + plane);
+        write_window(rbeg + plane, w1);
+    }
+    __syncthreads();
+    for (int s = 0; s < ns; ++s) {
+        const int32_t r0 = rbeg + s * plane;
+        const bool last = s + 1 == ns, fill = s + 2 < ns;                   // (uniform)
+        // a.
+        if (fill) request(r0 + 2 * plane);
+        if (!last) {
+#pragma unroll
+            for (int k = 0; k < T; ++k) idn[k] = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(a.pid + (size_t)(r0 + plane) + k * KR_TILE + 2 * t));
+        } else {
+#pragma unroll
+            for (int k = 0; k < T; ++k) hi[k] = far_pair((int64_t)r0 + k * KR_TILE + 2 * t + plane);
+        }
+        // b. tile after tile out of LDS (spmv_pattern_stage_kernel's arithmetic)
+#pragma unroll
+        for (int k = 0; k < T; ++k) {
+            const int32_t row = r0 + k * KR_TILE + 2 * t;
+            const uint2 ma = meta[ids[k] & 0xffffu], mb = meta[ids[k] >> 16];
+            const int j = k * KR_TILE + 2 * t + n + 2;                       // w0[j] = p_new[row], w1[j] = p_new[row + plane]
+            const v2d A = *reinterpret_cast<const v2d*>(w0 + j - 2), B = *reinterpret_cast<const v2d*>(w0 + j), C = *reinterpret_cast<const v2d*>(w0 + j + 2);
+            const v2d M = *reinterpret_cast<const v2d*>(w0 + j - n), P = *reinterpret_cast<const v2d*>(w0 + j + n);
+            const v2d U = *reinterpret_cast<const v2d*>(w1 + j);             // (the segment's last plane: not used)
+            v2d e[7];
+            e[0] = prev[k]; e[1] = M; e[2].x = A.y; e[2].y = B.x; e[3] = B; e[4].x = B.y; e[4].y = C.x; e[5] = P;
+            e[6].x = last ? hi[k].x : U.x; e[6].y = last ? hi[k].y : U.y;
+            prev[k] = B;
+            const double* tva = pval + (ma.x & 0xffffu); const double* tvb = pval + (mb.x & 0xffffu);
+            const unsigned ka = ma.y, kb = mb.y;
+            double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+            for (int u = 0; u < 7; ++u) {
+                const double ta = s0 + tva[u] * e[u].x, tb = s1 + tvb[u] * e[u].y;
+                s0 = ((ka >> u) & 1u) ? ta : s0;
+                s1 = ((kb >> u) & 1u) ? tb : s1;
+            }
+            st2(a.y, row, s0, s1);
+            double acc[NQ];
+            acc[0] = 0.0;
+            acc[0] = acc[0] + B.x * s0;
+            acc[0] = acc[0] + B.y * s1;
+            if constexpr (NQ > 1) {
+                acc[1] = 0.0;
+                acc[1] = acc[1] + s0 * s0;
+                acc[1] = acc[1] + s1 * s1;
+            }
+#pragma unroll
+            for (int kk = 0; kk < NQ; ++kk) {
+                const double wsum = wave_butterfly(acc[kk]);
+                if ((t & 63) == 0) red[(k * NQ + kk) * (KR_T / 64) + (t >> 6)] = wsum;
+            }
+        }
+        __syncthreads();                                                     // barrier 1
+        // c.
+        if (t < T * NQ) {                                                    // thread k * NQ + kk: tile r0 / 512 + k, quantity kk
+            const int k = t / NQ, kk = t % NQ;
+            double sum = red[t * (KR_T / 64)];
+#pragma unroll
+            for (int w = 1; w < KR_T / 64; ++w) sum = sum + red[t * (KR_T / 64) + w];
+            a.partials[kk * a.pstride + r0 / KR_TILE + k] = sum;
+        }
+        if (fill) write_window(r0 + 2 * plane, w0);
+        __syncthreads();                                                     // barrier 2
+#pragma unroll
+        for (int k = 0; k < T; ++k) ids[k] = idn[k];
+        double* w = w0; w0 = w1; w1 = w;
+    }
+}
+
+template <int NQ, int T, int NMAX, bool XU, bool MARCH = false>
 __global__ __launch_bounds__(KR_T) void spmv_pattern_fuse_kernel(const SpmvArgs a, const FuseArgs f, const int32_t n, const int32_t far_lo, const int32_t far_hi) {
     const bool ended = a.done && *a.done;
     const bool owed = XU && *f.xpend == f.it - 1;
     if (ended && !owed) return;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if constexpr (MARCH) { fuse_march<NQ, T, NMAX, XU>(a, f, n, far_hi, smem, ended, owed); return; }
     const int XS = T * KR_TILE + 2 * n + 4;                                  // staged elements (even)
     double* xs = reinterpret_cast<double*>(smem);                            // p_old's window, overwritten in place by p_new's
     uint2* meta = reinterpret_cast<uint2*>(xs + XS);
@@ -1037,7 +1220,9 @@ static int spmv_blocks_per_cu() { return env_int("KRYST_SPMV_BLOCKS_PER_CU", 0);
 // when a grid plane (far_hi rows) is a whole number of groups per XCD -- G = plane / (8 T tiles) -- the same (i, j) strip of every plane lands on
 // the same XCD, whose L2 then streams those rows itself: 512^3 fused CG, G = 16 against 4: 613 against 596 it/s (three interleaved rounds,
 // tools/cg_fuse_knobs.py).  (Walking SUB-strips of R runs plane by plane -- resident runs then neighbours in k -- was measured and loses: R = 1 / 2 / 4 /
-// 8 / 16: 563 / 578 / 590 / 603 / 616 it/s; a run that jumps a plane every few runs costs DRAM page locality more than the far operands' L2 hits give.)  The plain staged kernel does not care at 512^3 (0.500-0.508 ms for G = 1 .. 16, tools/stage_group_ab.py) and loses
+// 8 / 16: 563 / 578 / 590 / 603 / 616 it/s; a run that jumps a plane every few runs costs DRAM page locality more than the far operands' L2 hits give.
+// The marching mode, fuse_march_plan below, is the form of that idea that pays: the workgroup ITSELF walks the planes and keeps the far operands in its
+// LDS windows and registers, with whole planes' worth of neighbouring strips resident at every step -- 512^3: 631-636 against 611-620 it/s.)  The plain staged kernel does not care at 512^3 (0.500-0.508 ms for G = 1 .. 16, tools/stage_group_ab.py) and loses
 // with large groups at 384^3 (0.26 against 0.21 ms), so it keeps 4.
 static int stage_group_default(kryst_csr_t a, int64_t nruns, int T, bool fused) {
     if (nruns < 2048) return 1;
@@ -1547,6 +1732,42 @@ int32_t launch_spmv_fused(kryst_csr_t a, const double* z, const double* p_old, d
                           const double* alpha, const double* beta, const long long* xpend, long long it, const int* done) {
     return launch_spmv_fused_impl(a, z, p_old, p_new, xvec, y, nq, alpha, beta, xpend, it, done, false);
 }
+// The marching mode of the fused kernel (spmv_pattern_fuse_kernel<.., MARCH>): a workgroup keeps a strip of 512 T rows of a plane and walks a
+// segment of S planes.  Eligible: uniform far offsets of exactly +- one plane, a plane that is a whole number of strips, a box that is a whole
+// number of planes, lines of at most 512 points, and two windows + tables that leave room for two workgroups per CU; everything else (40^3:
+// a plane of 1 600 rows; 16^3: a tile spans two planes) takes the un-marched path untouched.  KRYST_SPMV_FUSE_MARCH (0 / 1), KRYST_SPMV_FUSE_SEG
+// (S) and KRYST_SPMV_FUSE_T are read per launch.
+struct FuseMarchPlan { bool eligible, on; int T, strips, S, segs; size_t red_off, lds; };
+static FuseMarchPlan fuse_march_plan(kryst_csr_t a, int nq) {
+    FuseMarchPlan m;
+    memset(&m, 0, sizeof m);
+    m.T = env_int("KRYST_SPMV_FUSE_T", 4) <= 2 ? 2 : 4;
+    const int64_t plane = a->pat_far_uniform ? (int64_t)a->pat_far_hi : 0, R = (int64_t)m.T * KR_TILE;
+    const int32_t n_ = a->pat_stage_n;
+    if (!(a->d_pid && n_ > 0 && n_ <= 512 && plane > 0 && (int64_t)a->pat_far_lo == -plane && plane % R == 0 && a->nrows % plane == 0 && a->nrows == a->xlen)) return m;
+    const size_t tab = 2 * sizeof(double) * (size_t)(R + 2 * n_ + 4) + (size_t)a->npat * 8 + (size_t)a->ntab * 8;
+    m.red_off = (tab + 15) & ~(size_t)15;
+    m.lds = m.red_off + sizeof(double) * (size_t)m.T * (size_t)nq * (KR_T / 64);
+    if (m.lds > ((size_t)80 << 10)) return m;
+    const int64_t nplanes = a->nrows / plane;
+    m.eligible = true;
+    m.strips = (int)(plane / R);
+    // S: KRYST_SPMV_FUSE_SEG, or (0, the default) the longest segments that still give two full rounds of the resident workgroups (two per CU, below):
+    // strips x segments <= 4 per CU -- 512^3: 128 strips x 8 segments of 64 planes = 1 024 workgroups; 384^3: 72 x 14 of 28; 256^3: 32 x 32 of 8.
+    // Fewer, longer segments leave CUs idle (256^3 with S = 64: 128 workgroups, 0.69 of the un-marched rate), shorter ones read more far operands.
+    int S = env_int("KRYST_SPMV_FUSE_SEG", 0);
+    if (S <= 0) {
+        const int64_t want = std::max<int64_t>(1, (int64_t)a->ctx->num_cu * 4 / m.strips);
+        S = (int)std::max<int64_t>((nplanes + want - 1) / want, std::min<int64_t>(4, nplanes));
+    }
+    m.S = (int)std::min<int64_t>(S, nplanes);
+    m.segs = (int)((nplanes + m.S - 1) / m.S);
+    // On by default where it was measured to pay and the fused form is the default itself (vectors beyond KRYST_CG_FUSE_MIN_BYTES: 512^3).  In-process
+    // A/B inside CG with the fused form forced (tools/cg_march_ab.py, profiles/march/): 512^3 +3.3 .. +3.5 %, 256^3 +4.6 %, 448^3 -0.2 %, 384^3 -2.6 .. -3.4 %.
+    m.on = env_int("KRYST_SPMV_FUSE_MARCH", a->nrows * 8 > env_ll("KRYST_CG_FUSE_MIN_BYTES", 768ll << 20) ? 1 : 0) != 0;
+    return m;
+}
+
 static int32_t launch_spmv_fused_impl(kryst_csr_t a, const double* z, const double* p_old, double* p_new, double* xvec, double* y, int nq,
                                       const double* alpha, const double* beta, const long long* xpend, long long it, const int* done, bool force) {
     kryst_ctx_t ctx = a->ctx;
@@ -1576,6 +1797,37 @@ static int32_t launch_spmv_fused_impl(kryst_csr_t a, const double* z, const doub
 #ifdef KR_TUNING
     args.abl = env_int("KRYST_FUSE_ABL", 0);          // timing-only ablations (tuning builds; wrong results)
 #endif
+    const FuseMarchPlan m = fuse_march_plan(a, 2);    // (sized for two quantities, like the query: one answer per operator)
+#ifdef KR_TUNING
+    if (m.eligible && m.on && !args.abl) {
+#else
+    if (m.eligible && m.on) {
+#endif
+        const int spx = (m.strips + 7) / 8;
+        args.group = spx; args.xcd_chunk = m.S; args.tpw = m.strips; args.pat_red_off = (int32_t)m.red_off;
+        size_t lds_m = m.lds;
+        // resident workgroups per CU: two unless KRYST_SPMV_FUSE_WG_PER_CU says otherwise (the three that fit at T = 4 are slower: 512^3 CG 620-624 against
+        // 636 it/s, profiles/march/sweep512.jsonl)
+        const int wgm = wgcu > 0 ? wgcu : 2;
+        lds_m = std::max(lds_m, std::min<size_t>((size_t)(160 << 10) / (size_t)wgm - 512, (size_t)80 << 10));
+        static bool raised_m = false;
+        if (!raised_m) {
+#define KR_MARCH_FNS(NQ_, T_) (const void*)spmv_pattern_fuse_kernel<NQ_, T_, 512, true, true>, (const void*)spmv_pattern_fuse_kernel<NQ_, T_, 512, false, true>
+            for (const void* fn : {KR_MARCH_FNS(1, 2), KR_MARCH_FNS(1, 4), KR_MARCH_FNS(2, 2), KR_MARCH_FNS(2, 4)})
+                (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 80 << 10);
+#undef KR_MARCH_FNS
+            raised_m = true;
+        }
+        const dim3 mgrid((unsigned)(8 * spx * m.segs));
+#define KR_MARCH_X(NQ_, T_) do { if (xvec) hipLaunchKernelGGL((spmv_pattern_fuse_kernel<NQ_, T_, 512, true, true>), mgrid, block, lds_m, ctx->s_main, args, f, n_, a->pat_far_lo, a->pat_far_hi); \
+                                 else hipLaunchKernelGGL((spmv_pattern_fuse_kernel<NQ_, T_, 512, false, true>), mgrid, block, lds_m, ctx->s_main, args, f, n_, a->pat_far_lo, a->pat_far_hi); } while (0)
+        if (nq == 1) { if (T == 2) KR_MARCH_X(1, 2); else KR_MARCH_X(1, 4); }
+        else { if (T == 2) KR_MARCH_X(2, 2); else KR_MARCH_X(2, 4); }
+#undef KR_MARCH_X
+        KR_HIP(hipGetLastError());
+        phase_mark(ctx, KR_PH_SPMV);
+        return KRYST_OK;
+    }
     if (lds_s > ((size_t)48 << 10)) {       // (more than the default dynamic LDS limit: once per instance)
         static bool raised = false;
         if (!raised) {
@@ -1726,6 +1978,16 @@ int32_t kryst_csr_tile_order(kryst_csr_t a, int64_t* info) {
 // info[0]: line length n of the staged-window form of the CSR-P16 kernel (0: the operator's bases are not (far, -n, -1, 0, +1, +n, far)),
 // info[1]: 1 when every base has the same far offsets (one round trip per run), info[2]: first tile of a rank's contiguous interior
 // range (-1: none), info[3]: 1 when kryst_spmv would take the staged-window kernel under the current settings
+int32_t kryst_csr_fuse_march_info(kryst_csr_t a, int64_t* info) {
+    KR_ARG(a && info, "csr_fuse_march_info");
+    const bool form = !a->dist && a->d_pid && a->pat_stage_n > 0 && a->pat_far_uniform && a->npat <= 512 && a->ntab <= 512 && a->nrows == a->xlen && takes_pattern_path(a, false);
+    FuseMarchPlan m;
+    memset(&m, 0, sizeof m);
+    if (form) m = fuse_march_plan(a, 2);
+    info[0] = m.eligible ? 1 : 0; info[1] = m.eligible && m.on ? 1 : 0; info[2] = m.T; info[3] = m.strips; info[4] = m.S; info[5] = m.segs;
+    return KRYST_OK;
+}
+
 int32_t kryst_csr_pattern_info(kryst_csr_t a, int64_t* info) {
     KR_ARG(a && info, "csr_pattern_info");
     info[0] = a->d_pid ? a->pat_stage_n : 0; info[1] = a->pat_far_uniform ? 1 : 0; info[2] = a->interior_first;
