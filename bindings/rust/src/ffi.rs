@@ -10,6 +10,8 @@ pub type Pc = *mut c_void;
 pub type Session = *mut c_void;
 pub type HostFactors = *mut c_void;
 pub type HostAmg = *mut c_void;
+pub type Dense = *mut c_void;
+pub type Lu = *mut c_void;
 
 pub const KRYST_OK: i32 = 0;
 pub const KRYST_FACTOR_ERROR: i32 = 1;
@@ -144,6 +146,25 @@ extern "C" {
     pub fn kryst_pc_asm_export(pc: Pc, sub_ptr: *mut i64, sub_idx: *mut i32, owner: *mut i32, tiles: *mut f64) -> i32;
     pub fn kryst_pc_sor(a: Csr, omega: f64, its: i64, lits: i64, sym_bits: u32, fshift: f64, colors: *const i32, out: *mut Pc) -> i32;
     pub fn kryst_pc_sor_info(pc: Pc, groups_forward: *mut i32, groups_backward: *mut i32, rows: *mut i64, grid_forward: *mut i32, grid_backward: *mut i32) -> i32;
+    // dense storage and the direct solvers (DenseMatrix src/matrix/dense.rs, LuSolver / QrSolver src/solver/direct_lu.rs)
+    pub fn kryst_dense_create(ctx: Ctx, nrows: i64, ncols: i64, data: *const f64, colmajor: i32, out: *mut Dense) -> i32;
+    pub fn kryst_dense_from_csr(a: Csr, out: *mut Dense) -> i32;
+    pub fn kryst_dense_shape(a: Dense, nrows: *mut i64, ncols: *mut i64) -> i32;
+    pub fn kryst_dense_download(a: Dense, colmajor: *mut f64) -> i32;
+    pub fn kryst_dense_destroy(a: Dense) -> i32;
+    pub fn kryst_dense_matvec(a: Dense, x: Vecd, y: Vecd) -> i32;
+    pub fn kryst_lu_create(ctx: Ctx, out: *mut Lu) -> i32;
+    pub fn kryst_lu_destroy(lu: Lu) -> i32;
+    pub fn kryst_lu_solve(lu: Lu, a: Dense, pc: Pc, b: *const f64, x: *mut f64, n: i64, stats: *mut Stats) -> i32;
+    pub fn kryst_lu_solve_dev(lu: Lu, a: Dense, pc: Pc, b: Vecd, x: Vecd, stats: *mut Stats) -> i32;
+    pub fn kryst_lu_solve_cached(lu: Lu, b: Vecd, x: Vecd) -> i32;
+    pub fn kryst_lu_export(lu: Lu, n: i64, row_perm: *mut i64, col_perm: *mut i64, factors_colmajor: *mut f64) -> i32;
+    pub fn kryst_lu_info(lu: Lu, info: *mut i64, count: i32) -> i32;
+    pub fn kryst_qr_solve(a: Dense, pc: Pc, b: *const f64, x: *mut f64, n: i64, stats: *mut Stats) -> i32;
+    pub fn kryst_qr_solve_dev(a: Dense, pc: Pc, b: Vecd, x: Vecd, stats: *mut Stats) -> i32;
+    pub fn kryst_host_dense_lu(nrows: i64, ncols: i64, a: *const f64, row_perm: *mut i64, col_perm: *mut i64, factors: *mut f64) -> i32;
+    pub fn kryst_host_dense_lu_solve(n: i64, row_perm: *const i64, col_perm: *const i64, factors: *const f64, b: *const f64, x: *mut f64) -> i32;
+    pub fn kryst_host_dense_qr_solve(nrows: i64, ncols: i64, a: *const f64, b: *const f64, x: *mut f64) -> i32;
     pub fn kryst_host_color_graph(n: i64, ptr: *const i64, col: *const i32, colors: *mut i32, ncolors: *mut i32) -> i32;
     pub fn kryst_pc_spai(a: Csr, pattern_kind: i32, pat_ptr: *const i64, pat_idx: *const i64, pat_n: i64, tol: f64, out: *mut Pc) -> i32;
     pub fn kryst_pc_spai_export(pc: Pc, nnz: *mut i64, row_ptr: *mut i64, col: *mut i32, val: *mut f64) -> i32;

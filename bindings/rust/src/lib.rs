@@ -846,3 +846,136 @@ mod tests {
         assert!(probe_device_pc(&Host).is_none());
     }
 }
+
+// ------------------------------------------------------------------------------------------------------------------ dense storage, direct solvers
+/// `DenseMatrix::from_raw` (src/matrix/dense.rs:16-25) resident in HBM, column-major.
+pub struct HipDenseMatrix {
+    ctx: HipContext,
+    h: ffi::Dense,
+    nrows: usize,
+    ncols: usize,
+}
+
+impl HipDenseMatrix {
+    /// `from_raw(nrows, ncols, data)`: `data[j * nrows + i]`.
+    pub fn from_raw(ctx: &HipContext, nrows: usize, ncols: usize, data: Vec<f64>) -> Result<Self, KError> {
+        if data.len() != nrows * ncols { return Err(KError::SolveError("from_raw: data length differs from nrows * ncols".into())); }
+        let mut h: ffi::Dense = std::ptr::null_mut();
+        check(unsafe { ffi::kryst_dense_create(ctx.raw(), nrows as i64, ncols as i64, data.as_ptr(), 1, &mut h) })?;
+        Ok(Self { ctx: ctx.clone(), h, nrows, ncols })
+    }
+    /// Extension: the operator densified on the device, absent entries +0.0.
+    pub fn from_csr(a: &HipCsrMatrix) -> Result<Self, KError> {
+        let mut h: ffi::Dense = std::ptr::null_mut();
+        check(unsafe { ffi::kryst_dense_from_csr(a.h, &mut h) })?;
+        Ok(Self { ctx: a.ctx.clone(), h, nrows: a.nrows, ncols: a.ncols })
+    }
+    pub fn to_raw(&self) -> Result<Vec<f64>, KError> {
+        let mut d = vec![0.0; self.nrows * self.ncols];
+        check(unsafe { ffi::kryst_dense_download(self.h, d.as_mut_ptr()) })?;
+        Ok(d)
+    }
+}
+
+impl Drop for HipDenseMatrix {
+    fn drop(&mut self) {
+        unsafe { ffi::kryst_dense_destroy(self.h) };
+    }
+}
+
+/// `MatVec` for the dense matrix (src/core/wrappers.rs:27-38): y[i] = sum over ascending j of a[i][j] * x[j], from +0.0.
+impl MatVec<Vec<f64>> for HipDenseMatrix {
+    fn matvec(&self, x: &Vec<f64>, y: &mut Vec<f64>) {
+        assert_eq!(x.len(), self.ncols);
+        assert_eq!(y.len(), self.nrows);
+        let (mut dx, mut dy): (ffi::Vecd, ffi::Vecd) = (std::ptr::null_mut(), std::ptr::null_mut());
+        unsafe {
+            let mut rc = ffi::kryst_vec_create(self.ctx.raw(), x.len() as i64, &mut dx);
+            if rc == 0 { rc = ffi::kryst_vec_create(self.ctx.raw(), y.len() as i64, &mut dy); }
+            if rc == 0 { rc = ffi::kryst_vec_upload(dx, x.as_ptr(), x.len() as i64); }
+            if rc == 0 { rc = ffi::kryst_dense_matvec(self.h, dx, dy); }
+            if rc == 0 { rc = ffi::kryst_vec_download(dy, y.as_mut_ptr(), y.len() as i64); }
+            if !dx.is_null() { ffi::kryst_vec_destroy(dx); }
+            if !dy.is_null() { ffi::kryst_vec_destroy(dy); }
+            assert_eq!(rc, 0, "kryst-hip dense matvec: {:?}", kerr(rc));
+        }
+    }
+}
+impl Indexing for HipDenseMatrix {
+    fn nrows(&self) -> usize {
+        self.nrows
+    }
+}
+impl MatShape for HipDenseMatrix {
+    fn nrows(&self) -> usize {
+        self.nrows
+    }
+    fn ncols(&self) -> usize {
+        self.ncols
+    }
+}
+
+fn direct_stats(st: &ffi::Stats) -> SolveStats<f64> {
+    SolveStats { iterations: st.iterations as usize, final_residual: st.final_residual, converged: st.converged != 0 }
+}
+
+/// `LuSolver<f64>` (src/solver/direct_lu.rs:14-90): LU with full pivoting in the operation order of DESIGN.md section 4.12 (a labelled
+/// deviation from faer's `FullPivLu`); `pc` is ignored (direct_lu.rs:70).
+pub struct HipLuSolver {
+    ctx: HipContext,
+    h: ffi::Lu,
+}
+impl HipLuSolver {
+    pub fn new(ctx: &HipContext) -> Result<Self, KError> {
+        let mut h: ffi::Lu = std::ptr::null_mut();
+        check(unsafe { ffi::kryst_lu_create(ctx.raw(), &mut h) })?;
+        Ok(Self { ctx: ctx.clone(), h })
+    }
+    /// `solve_cached` (direct_lu.rs:34-43); `Err(SolveError)` where the reference panics (nothing factored yet).
+    pub fn solve_cached(&self, b: &[f64], x: &mut [f64]) -> Result<(), KError> {
+        if b.len() != x.len() { return Err(KError::SolveError("solve_cached: length mismatch".into())); }
+        let mut v: ffi::Vecd = std::ptr::null_mut();
+        unsafe {
+            let mut rc = ffi::kryst_vec_create(self.ctx.raw(), b.len() as i64, &mut v);
+            if rc == 0 { rc = ffi::kryst_vec_upload(v, b.as_ptr(), b.len() as i64); }
+            if rc == 0 { rc = ffi::kryst_lu_solve_cached(self.h, v, v); }
+            if rc == 0 { rc = ffi::kryst_vec_download(v, x.as_mut_ptr(), x.len() as i64); }
+            if !v.is_null() { ffi::kryst_vec_destroy(v); }
+            check(rc)
+        }
+    }
+}
+impl Drop for HipLuSolver {
+    fn drop(&mut self) {
+        unsafe { ffi::kryst_lu_destroy(self.h) };
+    }
+}
+impl LinearSolver<HipDenseMatrix, Vec<f64>> for HipLuSolver {
+    type Error = KError;
+    type Scalar = f64;
+    fn solve(&mut self, a: &HipDenseMatrix, _pc: Option<&dyn Preconditioner<HipDenseMatrix, Vec<f64>>>, b: &Vec<f64>, x: &mut Vec<f64>)
+        -> Result<SolveStats<f64>, KError> {
+        if b.len() != x.len() { return Err(KError::SolveError("solve: b and x differ in length".into())); }
+        let mut st = ffi::Stats { iterations: 0, final_residual: 0.0, converged: 0 };
+        check(unsafe { ffi::kryst_lu_solve(self.h, a.h, std::ptr::null_mut(), b.as_ptr(), x.as_mut_ptr(), b.len() as i64, &mut st) })?;
+        Ok(direct_stats(&st))
+    }
+}
+
+/// `QrSolver` (src/solver/direct_lu.rs:96-146), square systems; `pc` is ignored (:123).
+#[derive(Default)]
+pub struct HipQrSolver;
+impl HipQrSolver {
+    pub fn new() -> Self { Self }
+}
+impl LinearSolver<HipDenseMatrix, Vec<f64>> for HipQrSolver {
+    type Error = KError;
+    type Scalar = f64;
+    fn solve(&mut self, a: &HipDenseMatrix, _pc: Option<&dyn Preconditioner<HipDenseMatrix, Vec<f64>>>, b: &Vec<f64>, x: &mut Vec<f64>)
+        -> Result<SolveStats<f64>, KError> {
+        if b.len() != x.len() { return Err(KError::SolveError("solve: b and x differ in length".into())); }
+        let mut st = ffi::Stats { iterations: 0, final_residual: 0.0, converged: 0 };
+        check(unsafe { ffi::kryst_qr_solve(a.h, std::ptr::null_mut(), b.as_ptr(), x.as_mut_ptr(), b.len() as i64, &mut st) })?;
+        Ok(direct_stats(&st))
+    }
+}

@@ -459,6 +459,48 @@ int32_t kryst_session_step(kryst_session_t s, int64_t k);
  * entry points repeat the solve themselves. */
 int32_t kryst_session_end(kryst_session_t s, kryst_stats_t* stats, double* hist, int64_t hist_cap, int64_t* hist_len);
 
+/* ---- dense storage and the direct solvers: DenseMatrix (src/matrix/dense.rs), LuSolver / QrSolver (src/solver/direct_lu.rs) ----
+ * Labelled deviation: the reference keeps faer's FullPivLu / Qr; these are the textbook factorizations -- LU with
+ * full pivoting (largest |w_ij| of the trailing block, the smaller row and then the smaller column on a tie), Householder QR -- in the
+ * operation order section 4.12 fixes: fp64, every operation rounded on its own, true divisions, column sweeps.  The host twins below and the
+ * device compute the same bits.  Square systems of at most KRYST_DENSE_MAX rows: more is KRYST_UNSUPPORTED, a non-square matrix
+ * KRYST_ERR_ARG, a context of several ranks KRYST_UNSUPPORTED.  KRYST_ZERO_PIVOT (kryst_hip_last_error_row() = the step) on a zero pivot /
+ * zero Householder column, KRYST_FACTOR_ERROR on a NaN or Inf in the matrix or in a pivot; x is untouched on every error.  Stats are
+ * direct_lu.rs:84-88 (iterations 1, final_residual 0.0, converged); pc is accepted and ignored (direct_lu.rs:70, :123).
+ * ALIASING: b and x may be the same vector (the reference copies b into x and solves in place); every other overlap of b, x and the
+ * matrix is refused with KRYST_ERR_ARG. */
+enum { KRYST_DENSE_MAX = 4096 };
+typedef struct kryst_dense_s* kryst_dense_t;
+typedef struct kryst_lu_s*    kryst_lu_t;
+/* DenseMatrix::from_raw(nrows, ncols, data) (dense.rs:16-25): data column-major, data[i + j * nrows]; colmajor == 0 (extension): row-major input */
+int32_t kryst_dense_create(kryst_ctx_t ctx, int64_t nrows, int64_t ncols, const double* data, int32_t colmajor, kryst_dense_t* out);
+/* extension: the operator densified on the device, absent entries +0.0 (a CSR operator holds no column twice in a row: kryst_csr_create checks
+ * new_checked's strictly ascending columns, so every entry has a place of its own) */
+int32_t kryst_dense_from_csr(kryst_csr_t a, kryst_dense_t* out);
+int32_t kryst_dense_shape(kryst_dense_t a, int64_t* nrows, int64_t* ncols);         /* nrows() / ncols() dense.rs:32-37 */
+int32_t kryst_dense_download(kryst_dense_t a, double* colmajor);
+int32_t kryst_dense_destroy(kryst_dense_t a);
+/* MatVec for DenseMatrix (core/wrappers.rs:27-38): y[i] = +0.0, then y[i] = y[i] + a[i][j] * x[j] for ascending j; rectangular allowed;
+ * x and y sharing storage: KRYST_ERR_ARG */
+int32_t kryst_dense_matvec(kryst_dense_t a, kryst_vec_t x, kryst_vec_t y);
+int32_t kryst_lu_create(kryst_ctx_t ctx, kryst_lu_t* out);                          /* LuSolver::new direct_lu.rs:24 */
+int32_t kryst_lu_destroy(kryst_lu_t lu);
+/* LuSolver::solve (direct_lu.rs:64-90): factor, cache the factors, solve */
+int32_t kryst_lu_solve(kryst_lu_t lu, kryst_dense_t a, kryst_pc_t pc, const double* b, double* x, int64_t n, kryst_stats_t* stats);
+int32_t kryst_lu_solve_dev(kryst_lu_t lu, kryst_dense_t a, kryst_pc_t pc, kryst_vec_t b, kryst_vec_t x, kryst_stats_t* stats);
+/* LuSolver::solve_cached (direct_lu.rs:34-43); KRYST_SOLVE_ERROR before any factorization or after a failed one (the reference panics) */
+int32_t kryst_lu_solve_cached(kryst_lu_t lu, kryst_vec_t b, kryst_vec_t x);
+/* the cached factorization: row_perm[i] / col_perm[j] = the row / column of A at position i / j, factors column-major in that frame
+ * (L below the diagonal, its unit diagonal implied, U on and above); any pointer may be NULL */
+int32_t kryst_lu_export(kryst_lu_t lu, int64_t n, int64_t* row_perm, int64_t* col_perm, double* factors_colmajor);
+/* info[0] KRYST_DENSE_MAX, info[1] rows of the trailing block that one workgroup finishes inside LDS (KRYST_DENSE_TAIL = 0 .. 128 sets it,
+ * 0: every step is a launch of its own; a test hook), info[2] rows of an update tile, info[3] rows of the cached factorization (-1: none);
+ * count >= 4 */
+int32_t kryst_lu_info(kryst_lu_t lu, int64_t* info, int32_t count);
+/* QrSolver::solve (direct_lu.rs:117-146), square systems */
+int32_t kryst_qr_solve(kryst_dense_t a, kryst_pc_t pc, const double* b, double* x, int64_t n, kryst_stats_t* stats);
+int32_t kryst_qr_solve_dev(kryst_dense_t a, kryst_pc_t pc, kryst_vec_t b, kryst_vec_t x, kryst_stats_t* stats);
+
 /* ---- host-only helpers (no GPU needed) ---- */
 /* 7-point stencil rows of planes [k_lo,k_hi) with global columns; returns nnz; pass NULL arrays to size */
 int64_t kryst_host_stencil7(int32_t N, int32_t kind, int32_t k_lo, int32_t k_hi,
@@ -512,6 +554,13 @@ int32_t kryst_host_amg_levels(kryst_host_amg_t h, int32_t* nlevels);
 int32_t kryst_host_amg_get(kryst_host_amg_t h, int32_t level, int32_t which, int64_t* nrows, int64_t* ncols, int64_t* nnz, int64_t* row_ptr,
                            int32_t* col, double* val);
 int32_t kryst_host_amg_destroy(kryst_host_amg_t h);
+
+/* The dense direct solvers of kryst_lu_solve / kryst_qr_solve (direct_lu.rs:64-90, :117-146) on host arrays, in the same operation order
+ * (kryst_amd/csrc/host_dense.cpp): the same bits as the device.  a column-major; no size cap; the same statuses;
+ * factors / row_perm / col_perm as kryst_lu_export gives them; b and x may be the same array, x is untouched on an error. */
+int32_t kryst_host_dense_lu(int64_t nrows, int64_t ncols, const double* a, int64_t* row_perm, int64_t* col_perm, double* factors);
+int32_t kryst_host_dense_lu_solve(int64_t n, const int64_t* row_perm, const int64_t* col_perm, const double* factors, const double* b, double* x);
+int32_t kryst_host_dense_qr_solve(int64_t nrows, int64_t ncols, const double* a, const double* b, double* x);
 
 /* Matrix Market coordinate file -> CSR (0-based, rows sorted, symmetric / skew-symmetric storage expanded, duplicates summed;
  * real, integer and pattern fields).  Returns nnz, or -1 (kryst_hip_last_error() says why).  Call with NULL arrays to size,

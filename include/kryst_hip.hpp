@@ -575,4 +575,82 @@ struct KspContext {
     }
 };
 
+// ---- dense storage and the direct solvers ---------------------------------------------------------------------------
+// DenseMatrix::from_raw (src/matrix/dense.rs:16-25) resident in HBM, column-major; MatVec (core/wrappers.rs:27-38).
+class HipDenseMatrix : public MatVec<Vec> {
+public:
+    static HipDenseMatrix from_raw(size_t nrows, size_t ncols, const Vec& data, std::shared_ptr<Context> ctx = Context::global()) {
+        if (data.size() != nrows * ncols) throw KError(KRYST_ERR_ARG);
+        kryst_dense_t h = nullptr;
+        check(kryst_dense_create(ctx->handle(), (int64_t)nrows, (int64_t)ncols, data.data(), 1, &h));
+        return HipDenseMatrix(std::move(ctx), h, nrows, ncols);
+    }
+    static HipDenseMatrix from_csr(const HipCsrMatrix& a) {      // extension: densified on the device, absent entries +0.0
+        kryst_dense_t h = nullptr;
+        check(kryst_dense_from_csr(a.handle(), &h));
+        return HipDenseMatrix(a.context(), h, a.nrows(), a.ncols());
+    }
+    HipDenseMatrix(HipDenseMatrix&& o) noexcept : ctx_(std::move(o.ctx_)), h_(o.h_), nrows_(o.nrows_), ncols_(o.ncols_) { o.h_ = nullptr; }
+    ~HipDenseMatrix() override { if (h_) kryst_dense_destroy(h_); }
+    size_t nrows() const { return nrows_; }
+    size_t ncols() const { return ncols_; }
+    Vec to_raw() const { Vec d(nrows_ * ncols_); check(kryst_dense_download(h_, d.data())); return d; }
+    void matvec(const Vec& x, Vec& y) const override {
+        if (x.size() != ncols_ || y.size() != nrows_) throw KError(KRYST_ERR_ARG);
+        kryst_vec_t xv = nullptr, yv = nullptr;
+        int32_t rc = kryst_vec_create(ctx_->handle(), (int64_t)x.size(), &xv);
+        if (rc == 0) rc = kryst_vec_create(ctx_->handle(), (int64_t)y.size(), &yv);
+        if (rc == 0) rc = kryst_vec_upload(xv, x.data(), (int64_t)x.size());
+        if (rc == 0) rc = kryst_dense_matvec(h_, xv, yv);
+        if (rc == 0) rc = kryst_vec_download(yv, y.data(), (int64_t)y.size());
+        if (xv) kryst_vec_destroy(xv);
+        if (yv) kryst_vec_destroy(yv);
+        check(rc);
+    }
+    kryst_dense_t handle() const { return h_; }
+    const std::shared_ptr<Context>& context() const { return ctx_; }
+private:
+    HipDenseMatrix(std::shared_ptr<Context> c, kryst_dense_t h, size_t nr, size_t nc) : ctx_(std::move(c)), h_(h), nrows_(nr), ncols_(nc) {}
+    std::shared_ptr<Context> ctx_; kryst_dense_t h_; size_t nrows_, ncols_;
+};
+
+// LuSolver (src/solver/direct_lu.rs:14-90): LU with full pivoting in the operation order of DESIGN.md section 4.12 (a labelled
+// deviation from faer's FullPivLu).  pc is accepted and ignored (direct_lu.rs:70).
+class LuSolver : public LinearSolver<HipDenseMatrix, Vec> {
+public:
+    explicit LuSolver(std::shared_ptr<Context> ctx = Context::global()) : ctx_(std::move(ctx)) { check(kryst_lu_create(ctx_->handle(), &h_)); }
+    ~LuSolver() override { if (h_) kryst_lu_destroy(h_); }
+    LuSolver(const LuSolver&) = delete; LuSolver& operator=(const LuSolver&) = delete;
+    SolveStats<double> solve(const HipDenseMatrix& a, const Preconditioner<HipDenseMatrix, Vec>*, const Vec& b, Vec& x) override {
+        if (b.size() != x.size()) throw KError(KRYST_ERR_ARG);
+        kryst_stats_t st{};
+        check(kryst_lu_solve(h_, a.handle(), nullptr, b.data(), x.data(), (int64_t)b.size(), &st));
+        return {(size_t)st.iterations, st.final_residual, st.converged != 0};
+    }
+    // solve_cached (direct_lu.rs:34-43): throws KError{SolveError} where the reference panics (nothing factored yet)
+    void solve_cached(const Vec& b, Vec& x) const {
+        if (b.size() != x.size()) throw KError(KRYST_ERR_ARG);
+        kryst_vec_t v = nullptr;
+        int32_t rc = kryst_vec_create(ctx_->handle(), (int64_t)b.size(), &v);
+        if (rc == 0) rc = kryst_vec_upload(v, b.data(), (int64_t)b.size());
+        if (rc == 0) rc = kryst_lu_solve_cached(h_, v, v);
+        if (rc == 0) rc = kryst_vec_download(v, x.data(), (int64_t)x.size());
+        if (v) kryst_vec_destroy(v);
+        check(rc);
+    }
+private:
+    std::shared_ptr<Context> ctx_; kryst_lu_t h_ = nullptr;
+};
+
+// QrSolver (src/solver/direct_lu.rs:96-146), square systems; pc is accepted and ignored (:123).
+class QrSolver : public LinearSolver<HipDenseMatrix, Vec> {
+public:
+    SolveStats<double> solve(const HipDenseMatrix& a, const Preconditioner<HipDenseMatrix, Vec>*, const Vec& b, Vec& x) override {
+        if (b.size() != x.size()) throw KError(KRYST_ERR_ARG);
+        kryst_stats_t st{};
+        check(kryst_qr_solve(a.handle(), nullptr, b.data(), x.data(), (int64_t)b.size(), &st));
+        return {(size_t)st.iterations, st.final_residual, st.converged != 0};
+    }
+};
+
 }  // namespace kryst

@@ -9,6 +9,8 @@ behaviour (paths relative to the kryst crate):
     Jacobi / Ilu0 / Ilup / Chebyshev  .setup(a) .apply(r, z)        src/preconditioner/*.rs
     apply_chebyshev(a, r, z, alpha, beta, m)                        src/preconditioner/chebyshev.rs:83-140
     CgSolver / PcgSolver / GmresSolver / BiCgStabSolver .solve(a, pc, b, x) -> SolveStats   src/solver/*.rs
+    DenseMatrix.from_raw(nrows, ncols, data) .matvec(x, y)          src/matrix/dense.rs:16-25, core/wrappers.rs:27-38
+    LuSolver / QrSolver .solve(a, pc, b, x), LuSolver.solve_cached  src/solver/direct_lu.rs
     Convergence, SolveStats, KError, CgNormType, Preconditioning    src/utils/convergence.rs, src/error.rs
 
 Everything executes in libkryst_hip.so (hand-written HIP for gfx950) through the C ABI of include/kryst_hip.h.
@@ -24,7 +26,8 @@ from ._ffi import KError, lib, check
 __all__ = ["Context", "DeviceVec", "CsrMatrix", "dot", "norm", "Jacobi", "Ilu0", "Ilup", "Ilut", "TrueIlu0", "Chebyshev",
            "ChebyshevPc", "IdentityPc", "ApproxInv", "BlockJacobi", "AdditiveSchwarz", "Sor", "MatSorType", "SparsityPattern", "Spai", "Amg", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
            "Preconditioning", "CgSolver", "PcgSolver", "GmresSolver", "FgmresSolver", "PcaGmresSolver", "Orthog", "CgsSolver", "TfqmrSolver", "MinresSolver", "QmrSolver", "CgnrSolver", "CgneSolver", "BiCgStabSolver", "BiCgStabRightPcSolver", "Session", "KspContext", "SolverKind", "PC", "KError", "reduce_spec",
-           "host_stencil7", "partition_rows", "halo_recv_plan", "read_matrix_market", "read_petsc_binary", "host_ilup", "host_ilut", "host_amg", "host_levels", "color_graph", "build_blocks_from_colors"]
+           "host_stencil7", "partition_rows", "halo_recv_plan", "read_matrix_market", "read_petsc_binary", "host_ilup", "host_ilut", "host_amg", "host_levels", "color_graph", "build_blocks_from_colors",
+           "DenseMatrix", "LuSolver", "QrSolver", "host_dense_lu", "host_dense_lu_solve", "host_dense_qr_solve"]
 
 
 def _dp(a):
@@ -1282,6 +1285,191 @@ class CgneSolver(CgnrSolver):
 class BiCgStabRightPcSolver(_Solver):
     """Extension: right-preconditioned BiCGStab (device vectors only)."""
     _HOST, _DEV = None, "kryst_bicgstab_rpc_solve_dev"
+
+
+class DenseMatrix:
+    """DenseMatrix<f64> (src/matrix/dense.rs) living on the GPU, column-major; implements MatVec (core/wrappers.rs:27-38)."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+        nr, nc = C.c_int64(), C.c_int64()
+        check(lib().kryst_dense_shape(self.h, C.byref(nr), C.byref(nc)))
+        self._nrows, self._ncols = nr.value, nc.value
+
+    @staticmethod
+    def from_raw(nrows, ncols, data, ctx=None):
+        """DenseMatrix::from_raw(nrows, ncols, data) (dense.rs:16-25): data column-major, data[i + j * nrows]."""
+        ctx = ctx or Context.default()
+        d = _f64(data).ravel()
+        if len(d) != nrows * ncols:
+            raise KError(102, "from_raw: data length differs from nrows * ncols")
+        h = _ffi.Handle()
+        check(lib().kryst_dense_create(ctx.h, nrows, ncols, _dp(d), 1, C.byref(h)))
+        return DenseMatrix(ctx, h)
+
+    @staticmethod
+    def from_numpy(a, ctx=None):
+        """A 2-D array a[i, j] (extension)."""
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim != 2:
+            raise KError(102, "from_numpy: a 2-D array is required")
+        return DenseMatrix.from_raw(a.shape[0], a.shape[1], np.asfortranarray(a).ravel(order="F"), ctx=ctx)
+
+    @staticmethod
+    def from_csr(a):
+        """The CsrMatrix densified on the device, absent entries +0.0 (extension)."""
+        h = _ffi.Handle()
+        check(lib().kryst_dense_from_csr(a.h, C.byref(h)))
+        return DenseMatrix(a.ctx, h)
+
+    def nrows(self):
+        return self._nrows
+
+    def ncols(self):
+        return self._ncols
+
+    @property
+    def shape(self):
+        return (self._nrows, self._ncols)
+
+    def to_numpy(self):
+        out = np.empty(self._nrows * self._ncols)
+        check(lib().kryst_dense_download(self.h, _dp(out)))
+        return out.reshape((self._nrows, self._ncols), order="F")
+
+    def matvec(self, x, y=None):
+        """MatVec::matvec(&self, x, y) (core/wrappers.rs:27-38): y = A x.  Host arrays in -> host array out; DeviceVec in -> DeviceVec."""
+        if isinstance(x, DeviceVec):
+            y = y if y is not None else DeviceVec(self.ctx, self._nrows)
+            check(lib().kryst_dense_matvec(self.h, x.h, y.h))
+            return y
+        xv, yv = DeviceVec(self.ctx, _f64(x)), DeviceVec(self.ctx, self._nrows)
+        check(lib().kryst_dense_matvec(self.h, xv.h, yv.h))
+        out = yv.to_host()
+        if y is not None:
+            y[:] = out
+            return y
+        return out
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                lib().kryst_dense_destroy(self.h)
+        except Exception:
+            pass
+
+
+def _direct_solve(host_fn, dev_fn, head, a, pc, b, x):
+    """The call shape shared by LuSolver::solve and QrSolver::solve: pc is accepted and ignored (direct_lu.rs:70, :123)."""
+    st = _ffi.Stats()
+    pch = pc.h if pc is not None else None
+    if isinstance(b, DeviceVec):
+        rc = dev_fn(*head, a.h, pch, b.h, x.h, C.byref(st))
+    else:
+        bb = _f64(b)
+        if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.flags.c_contiguous):
+            raise KError(102, "x must be a contiguous float64 numpy array (it is written in place)")
+        if len(bb) != len(x):
+            raise KError(102, "b and x differ in length")
+        rc = host_fn(*head, a.h, pch, _dp(bb), _dp(x), len(bb), C.byref(st))
+    stats = SolveStats(st.iterations, st.final_residual, bool(st.converged))
+    check(rc, stats)
+    return stats
+
+
+class LuSolver:
+    """LuSolver (src/solver/direct_lu.rs:14-90) on a DenseMatrix: LU with full pivoting in the operation order of DESIGN.md section 4.12
+    (a labelled deviation from faer's FullPivLu)."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx or Context.default()
+        self.h = _ffi.Handle()
+        check(lib().kryst_lu_create(self.ctx.h, C.byref(self.h)))
+
+    def solve(self, a, pc, b, x):
+        """LinearSolver::solve (direct_lu.rs:64-90): factor, cache, solve.  b is x is allowed for DeviceVec arguments."""
+        return _direct_solve(lib().kryst_lu_solve, lib().kryst_lu_solve_dev, (self.h,), a, pc, b, x)
+
+    def solve_cached(self, b, x=None):
+        """solve_cached (direct_lu.rs:34-43) with the cached factors; KError(SolveError) when there are none (the reference panics)."""
+        if isinstance(b, DeviceVec):
+            x = x if x is not None else DeviceVec(self.ctx, len(b))
+            check(lib().kryst_lu_solve_cached(self.h, b.h, x.h))
+            return x
+        bv = DeviceVec(self.ctx, _f64(b))
+        check(lib().kryst_lu_solve_cached(self.h, bv.h, bv.h))
+        out = bv.to_host()
+        if x is not None:
+            x[:] = out
+            return x
+        return out
+
+    def info(self):
+        v = (C.c_int64 * 4)()
+        check(lib().kryst_lu_info(self.h, v, 4))
+        return {"cap": v[0], "tail": v[1], "tile": v[2], "n": v[3]}
+
+    def factors(self):
+        """-> (row_perm, col_perm, factors): P A Q = L U with (P A Q)[i, j] = A[row_perm[i], col_perm[j]], L strictly below the diagonal of
+        `factors` (unit diagonal implied), U on and above it."""
+        n = self.info()["n"]
+        if n < 0:
+            raise KError(2, "factors: no factorization is cached")
+        rp = np.zeros(max(n, 1), dtype=np.int64); cp = np.zeros(max(n, 1), dtype=np.int64); f = np.zeros(max(n * n, 1))
+        check(lib().kryst_lu_export(self.h, n, rp.ctypes.data_as(_ffi.c_i64p), cp.ctypes.data_as(_ffi.c_i64p), _dp(f)))
+        return rp[:n], cp[:n], f[:n * n].reshape((n, n), order="F")
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                lib().kryst_lu_destroy(self.h)
+        except Exception:
+            pass
+
+
+class QrSolver:
+    """QrSolver (src/solver/direct_lu.rs:96-146) on a square DenseMatrix: Householder QR in the operation order of DESIGN.md section 4.12."""
+
+    def solve(self, a, pc, b, x):
+        return _direct_solve(lib().kryst_qr_solve, lib().kryst_qr_solve_dev, (), a, pc, b, x)
+
+
+def _colmajor(a):
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 2:
+        raise KError(102, "a 2-D array is required")
+    return a.shape[0], a.shape[1], np.asfortranarray(a).ravel(order="F")
+
+
+def host_dense_lu(a):
+    """LU with full pivoting on the host, no GPU (kryst_host_dense_lu): the bits of LuSolver.  -> (row_perm, col_perm, factors)."""
+    nr, nc, d = _colmajor(a)
+    rp = np.zeros(max(nr, 1), dtype=np.int64); cp = np.zeros(max(nr, 1), dtype=np.int64); f = np.zeros(max(nr * nr, 1))
+    check(lib().kryst_host_dense_lu(nr, nc, _dp(d), rp.ctypes.data_as(_ffi.c_i64p), cp.ctypes.data_as(_ffi.c_i64p), _dp(f)))
+    return rp[:nr], cp[:nr], f[:nr * nr].reshape((nr, nr), order="F")
+
+
+def host_dense_lu_solve(row_perm, col_perm, factors, b, x=None):
+    """The two column sweeps of LuSolver on the host (kryst_host_dense_lu_solve) -> x."""
+    rp = np.ascontiguousarray(row_perm, dtype=np.int64); cp = np.ascontiguousarray(col_perm, dtype=np.int64)
+    n, _, f = _colmajor(factors)
+    bb = _f64(b)
+    if len(bb) != n or len(rp) != n or len(cp) != n:
+        raise KError(102, "host_dense_lu_solve: lengths differ")
+    x = np.empty(n) if x is None else x
+    check(lib().kryst_host_dense_lu_solve(n, rp.ctypes.data_as(_ffi.c_i64p), cp.ctypes.data_as(_ffi.c_i64p), _dp(f), _dp(bb), _dp(x)))
+    return x
+
+
+def host_dense_qr_solve(a, b, x=None):
+    """Householder QR solve on the host (kryst_host_dense_qr_solve): the bits of QrSolver.  x (if given) is untouched on an error."""
+    nr, nc, d = _colmajor(a)
+    bb = _f64(b)
+    if len(bb) != nr:
+        raise KError(102, "host_dense_qr_solve: b has the wrong length")
+    x = np.empty(nr) if x is None else x
+    check(lib().kryst_host_dense_qr_solve(nr, nc, _dp(d), _dp(bb), _dp(x)))
+    return x
 
 
 class PC:

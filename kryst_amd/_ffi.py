@@ -147,6 +147,24 @@ SIGNATURES = {
     "kryst_session_begin": (C.c_int32, [C.c_int32, Handle, Handle, Handle, Handle, C.POINTER(Params), C.POINTER(Handle)]),
     "kryst_session_step": (C.c_int32, [Handle, C.c_int64]),
     "kryst_session_end": (C.c_int32, [Handle, C.POINTER(Stats), c_dp, C.c_int64, c_i64p]),
+    "kryst_dense_create": (C.c_int32, [Handle, C.c_int64, C.c_int64, c_dp, C.c_int32, C.POINTER(Handle)]),
+    "kryst_dense_from_csr": (C.c_int32, [Handle, C.POINTER(Handle)]),
+    "kryst_dense_shape": (C.c_int32, [Handle, c_i64p, c_i64p]),
+    "kryst_dense_download": (C.c_int32, [Handle, c_dp]),
+    "kryst_dense_destroy": (C.c_int32, [Handle]),
+    "kryst_dense_matvec": (C.c_int32, [Handle, Handle, Handle]),
+    "kryst_lu_create": (C.c_int32, [Handle, C.POINTER(Handle)]),
+    "kryst_lu_destroy": (C.c_int32, [Handle]),
+    "kryst_lu_solve": (C.c_int32, [Handle, Handle, Handle, c_dp, c_dp, C.c_int64, C.POINTER(Stats)]),
+    "kryst_lu_solve_dev": (C.c_int32, [Handle, Handle, Handle, Handle, Handle, C.POINTER(Stats)]),
+    "kryst_lu_solve_cached": (C.c_int32, [Handle, Handle, Handle]),
+    "kryst_lu_export": (C.c_int32, [Handle, C.c_int64, c_i64p, c_i64p, c_dp]),
+    "kryst_lu_info": (C.c_int32, [Handle, c_i64p, C.c_int32]),
+    "kryst_qr_solve": (C.c_int32, [Handle, Handle, c_dp, c_dp, C.c_int64, C.POINTER(Stats)]),
+    "kryst_qr_solve_dev": (C.c_int32, [Handle, Handle, Handle, Handle, C.POINTER(Stats)]),
+    "kryst_host_dense_lu": (C.c_int32, [C.c_int64, C.c_int64, c_dp, c_i64p, c_i64p, c_dp]),
+    "kryst_host_dense_lu_solve": (C.c_int32, [C.c_int64, c_i64p, c_i64p, c_dp, c_dp, c_dp]),
+    "kryst_host_dense_qr_solve": (C.c_int32, [C.c_int64, C.c_int64, c_dp, c_dp, c_dp]),
     "kryst_host_stencil7": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i64p, c_i64p, c_dp]),
     "kryst_host_partition_rows": (C.c_int32, [C.c_int64, C.c_int32, C.c_int64, c_i64p]),
     "kryst_host_read_petsc_binary": (C.c_int64, [C.c_char_p, c_i64p, c_i64p, c_i64p, c_i64p, c_dp]),
