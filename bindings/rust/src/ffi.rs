@@ -144,6 +144,11 @@ extern "C" {
     pub fn kryst_pc_asm_uniform(a: Csr, nparts: i64, overlap: i32, variant: i32, out: *mut Pc) -> i32;
     pub fn kryst_pc_asm_info(pc: Pc, nsub: *mut i64, ext_rows: *mut i64, max_rows: *mut i32) -> i32;
     pub fn kryst_pc_asm_export(pc: Pc, sub_ptr: *mut i64, sub_idx: *mut i32, owner: *mut i32, tiles: *mut f64) -> i32;
+    pub fn kryst_pc_asm_ilu(a: Csr, sub_ptr: *const i64, sub_idx: *const i64, nsub: i64, overlap: i32, variant: i32, sub_mode: i32, out: *mut Pc) -> i32;
+    pub fn kryst_pc_asm_ilu_uniform(a: Csr, nparts: i64, overlap: i32, variant: i32, sub_mode: i32, out: *mut Pc) -> i32;
+    pub fn kryst_pc_asm_ilu_info(pc: Pc, info: *mut i64, count: i32) -> i32;
+    pub fn kryst_pc_asm_ilu_export(pc: Pc, sub_ptr: *mut i64, sub_idx: *mut i32, owner: *mut i32, ent_ptr: *mut i64, row_ptr: *mut i32, col: *mut i32,
+                                   val: *mut f64, lev_l: *mut i32, lev_u: *mut i32) -> i32;
     pub fn kryst_pc_sor(a: Csr, omega: f64, its: i64, lits: i64, sym_bits: u32, fshift: f64, colors: *const i32, out: *mut Pc) -> i32;
     pub fn kryst_pc_sor_info(pc: Pc, groups_forward: *mut i32, groups_backward: *mut i32, rows: *mut i64, grid_forward: *mut i32, grid_backward: *mut i32) -> i32;
     // dense storage and the direct solvers (DenseMatrix src/matrix/dense.rs, LuSolver / QrSolver src/solver/direct_lu.rs)

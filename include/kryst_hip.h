@@ -277,6 +277,32 @@ int32_t kryst_pc_asm_info(kryst_pc_t pc, int64_t* nsub, int64_t* ext_rows, int32
  * (sum b_k^2) the inverses subdomain after subdomain, column-major inside a tile (tiles[off_k + j b_k + i] = Binv_k[i][j]). */
 int32_t kryst_pc_asm_export(kryst_pc_t pc, int64_t* sub_ptr, int32_t* sub_idx, int32_t* owner, double* tiles);
 
+/* Additive Schwarz with ILU(0) subdomain solves (labelled extension of AdditiveSchwarz::setup's `solver_factory`, asm.rs:38-40; DESIGN.md
+ * section 4.13).  Index sets, growth, owners, variants, the uniform partition and the combine are those of kryst_pc_asm; the inner solver of
+ * subdomain k is an incomplete factorisation of S_k = A[g_k, g_k] (sorted g_k; every stored entry kept, explicit zeros included; columns outside
+ * g_k dropped): sub_mode KRYST_ILU_ILUP0 is Ilup::new(0) as written (ilup.rs:77-167), KRYST_ILU_TRUE_ILU0 the textbook IKJ ILU(0) on S_k's
+ * pattern, both applied as ilup.rs:138-167 does (a factor entry equal to 0.0 takes no part; the division only by a stored non-zero diagonal);
+ * KRYST_ILU_KRYST_COMPAT is KRYST_UNSUPPORTED.  The apply solves every subdomain in one workgroup with its vector in LDS.  Errors: those of
+ * kryst_pc_asm for the sets; those of kryst_pc_ilu0 for the factors (KRYST_ZERO_PIVOT / KRYST_SOLVE_ERROR, the row a row of A in the message
+ * and in kryst_hip_last_error_row(), the lowest-numbered failing subdomain); KRYST_UNSUPPORTED for a subdomain of more than
+ * KRYST_ASM_ILU_MAX_ROWS rows before or after growth (the message names the cap), a context of several ranks, a distributed operator;
+ * KRYST_ERR_HIP with byte counts when the device memory does not suffice.  a is borrowed (must outlive the preconditioner). */
+enum { KRYST_ASM_ILU_MAX_ROWS = 16384, KRYST_ASM_ILU_INFO_COUNT = 10 };
+int32_t kryst_pc_asm_ilu(kryst_csr_t a, const int64_t* sub_ptr, const int64_t* sub_idx, int64_t nsub, int32_t overlap, int32_t variant,
+                         int32_t sub_mode, kryst_pc_t* out);
+int32_t kryst_pc_asm_ilu_uniform(kryst_csr_t a, int64_t nparts, int32_t overlap, int32_t variant, int32_t sub_mode, kryst_pc_t* out);
+/* the first min(count, KRYST_ASM_ILU_INFO_COUNT) of: nsub, ext_rows (the sum of the grown subdomain rows), max_rows, nnz_L and nnz_U (the kept,
+ * i.e. non-zero, entries strictly below / strictly above the diagonal), the largest level count of a sweep, the LDS bytes per workgroup of
+ * the apply, the cap KRYST_ASM_ILU_MAX_ROWS, nnz_S (the stored entries of all submatrices), the entries of the padded level layouts */
+int32_t kryst_pc_asm_ilu_info(kryst_pc_t pc, int64_t* info, int32_t count);
+/* the set-up, downloaded; any pointer may be NULL: sub_ptr (nsub + 1), sub_idx (ext_rows) and owner (n) as kryst_pc_asm_export gives them;
+ * the factors on the submatrices' patterns, subdomain after subdomain: ent_ptr (nsub + 1) the first entry of every subdomain, row_ptr
+ * (ext_rows + nsub: b_k + 1 row pointers per subdomain, relative to ent_ptr[k]), col (nnz_S, local columns = positions in g_k, ascending
+ * within a row), val (nnz_S: l_ij below the diagonal, u_ij on and above it); lev_l and lev_u (ext_rows): every row's level (from 1) in the
+ * forward and in the backward sweep */
+int32_t kryst_pc_asm_ilu_export(kryst_pc_t pc, int64_t* sub_ptr, int32_t* sub_idx, int32_t* owner, int64_t* ent_ptr, int32_t* row_ptr, int32_t* col,
+                                double* val, int32_t* lev_l, int32_t* lev_u);
+
 /* Sor::new(omega, its, lits, sym, fshift) + setup + apply (src/preconditioner/sor.rs:71-170) as a device preconditioner on the CSR operator
  * (DESIGN.md section 4.11).  sym_bits: the MatSorType bits below.  Set-up: inv_diag[i] = 1 / (a_ii + fshift), a row without a stored
  * diagonal counts as a_ii = 0; a sum of exactly zero is KRYST_ZERO_PIVOT with the lowest such row in kryst_hip_last_error_row().  apply:

@@ -221,14 +221,21 @@ struct AdditiveSchwarz : DevicePc {
     AdditiveSchwarz(size_t overlap = 0, std::vector<std::vector<size_t>> subdomains = {}, size_t nparts = 0, Variant variant = AsWritten)
         : overlap(overlap), subdomains(std::move(subdomains)), nparts(nparts), variant(variant) {}
     size_t overlap; std::vector<std::vector<size_t>> subdomains; size_t nparts; Variant variant;
+    // labelled extension (kryst_pc_asm_ilu): ILU(0) subdomain solves in place of the dense inverses, subdomains of up to
+    // KRYST_ASM_ILU_MAX_ROWS rows; sub_mode KRYST_ILU_TRUE_ILU0 or KRYST_ILU_ILUP0.  Negative (the default): the direct solve.
+    int32_t sub_mode = -1;
+    AdditiveSchwarz& with_sub_ilu(int32_t mode = KRYST_ILU_TRUE_ILU0) { sub_mode = mode; return *this; }
     void setup(const HipCsrMatrix& a) override {
         kryst_pc_t h = nullptr;
         const int32_t ov = (int32_t)std::min<size_t>(overlap, INT32_MAX);
+        std::vector<int64_t> ptr(1, 0), idx;
+        for (auto& g : subdomains) { for (size_t i : g) idx.push_back((int64_t)i); ptr.push_back((int64_t)idx.size()); }
         if (subdomains.empty()) {
-            check(kryst_pc_asm_uniform(a.handle(), (int64_t)nparts, ov, (int32_t)variant, &h));
+            if (sub_mode >= 0) check(kryst_pc_asm_ilu_uniform(a.handle(), (int64_t)nparts, ov, (int32_t)variant, sub_mode, &h));
+            else check(kryst_pc_asm_uniform(a.handle(), (int64_t)nparts, ov, (int32_t)variant, &h));
+        } else if (sub_mode >= 0) {
+            check(kryst_pc_asm_ilu(a.handle(), ptr.data(), idx.data(), (int64_t)subdomains.size(), ov, (int32_t)variant, sub_mode, &h));
         } else {
-            std::vector<int64_t> ptr(1, 0), idx;
-            for (auto& g : subdomains) { for (size_t i : g) idx.push_back((int64_t)i); ptr.push_back((int64_t)idx.size()); }
             check(kryst_pc_asm(a.handle(), ptr.data(), idx.data(), (int64_t)subdomains.size(), ov, (int32_t)variant, &h));
         }
         reset(h, a.context()->handle());

@@ -669,15 +669,21 @@ class AdditiveSchwarz(_Pc):
     of the symmetrised graph of A; `.restricted()` grows them and keeps, per row, only the product of the last un-grown subdomain that
     contains it (RAS: not symmetric, for GMRES, FGMRES and BiCGStab, not PCG).  Labelled deviations, those of BlockJacobi: explicit
     Gauss-Jordan inverses, sorted index sets, errors (ZeroPivot with `.row`, FactorError, ArgumentError, Unsupported for a subdomain of
-    more than 128 rows before or after growth) where the reference gives non-finite z or panics."""
+    more than 128 rows before or after growth) where the reference gives non-finite z or panics.  `.with_sub_ilu(mode)` (labelled
+    extension) replaces the dense inverses by ILU(0) subdomain solves, each solved by one workgroup with its vector
+    in LDS: subdomains of up to SUB_ILU_MAX_ROWS rows; with overlap, RAS keeps global ILU(0)'s iteration counts while the plain sum of
+    inexact overlapping solves needs more iterations than no overlap at all."""
     AS_WRITTEN, GROWN, RESTRICTED = 0, 1, 2
     MAX_ROWS = 128
+    SUB_ILU_MAX_ROWS = 16384
+    _SUB_MODES = {"ilup0": 1, "ilu0": 2}
 
     def __init__(self, overlap=0, subdomains=None, nparts=None):
         super().__init__()
         self.overlap = int(overlap)
         self.nparts = 0 if nparts is None else int(nparts)
         self.variant = self.AS_WRITTEN
+        self.sub_mode = None
         self.ptr = self.idx = None
         if subdomains is not None and len(subdomains) > 0:
             if isinstance(subdomains, tuple) and len(subdomains) == 2 and all(isinstance(v, np.ndarray) for v in subdomains):
@@ -690,6 +696,16 @@ class AdditiveSchwarz(_Pc):
                 self.idx = np.concatenate(sets) if sets else np.zeros(0, dtype=np.int64)
             if len(self.ptr) < 1 or int(self.ptr[-1]) != len(self.idx):
                 raise KError(102, "AdditiveSchwarz: inconsistent (ptr, idx)")
+
+    def with_sub_ilu(self, mode="ilu0"):
+        """Labelled extension: every subdomain is solved with an incomplete factorisation of its submatrix instead of its dense inverse.
+        mode "ilu0": textbook ILU(0) on the submatrix's pattern (TrueIlu0); "ilup0": Ilup::new(0) as written (Ilu0).  An integer is passed
+        through as the library's sub_mode."""
+        self.sub_mode = self._SUB_MODES[mode] if isinstance(mode, str) and mode in self._SUB_MODES else mode
+        if isinstance(self.sub_mode, str) or self.sub_mode is None:
+            raise KError(102, f"AdditiveSchwarz.with_sub_ilu: unknown mode {mode!r} (\"ilu0\" or \"ilup0\")")
+        self.sub_mode = int(self.sub_mode)
+        return self
 
     def with_overlap(self):
         """Labelled extension: grow every subdomain by `overlap` layers before it is inverted."""
@@ -717,7 +733,12 @@ class AdditiveSchwarz(_Pc):
 
     def setup(self, a):
         h = _ffi.Handle()
-        if self.ptr is None:
+        if self.sub_mode is not None and self.ptr is None:
+            check(lib().kryst_pc_asm_ilu_uniform(a.h, self.nparts, self.overlap, self.variant, self.sub_mode, C.byref(h)))
+        elif self.sub_mode is not None:
+            check(lib().kryst_pc_asm_ilu(a.h, self.ptr.ctypes.data_as(_ffi.c_i64p), self.idx.ctypes.data_as(_ffi.c_i64p), len(self.ptr) - 1,
+                                         self.overlap, self.variant, self.sub_mode, C.byref(h)))
+        elif self.ptr is None:
             check(lib().kryst_pc_asm_uniform(a.h, self.nparts, self.overlap, self.variant, C.byref(h)))
         else:
             check(lib().kryst_pc_asm(a.h, self.ptr.ctypes.data_as(_ffi.c_i64p), self.idx.ctypes.data_as(_ffi.c_i64p), len(self.ptr) - 1,
@@ -727,17 +748,42 @@ class AdditiveSchwarz(_Pc):
         return self
 
     def info(self):
-        """-> dict(nsub, ext_rows = the sum of the (grown) subdomain rows, max_rows)"""
+        """-> dict(nsub, ext_rows = the sum of the (grown) subdomain rows, max_rows); with ILU sub-solves also nnz_l, nnz_u (the kept
+        entries strictly below / above the diagonal), max_levels, lds_bytes (per workgroup of the apply), cap, nnz_s (the stored entries of
+        the submatrices), layout_entries (the padded level layouts)"""
         if self.h is None:
             raise KError(2, "preconditioner used before setup")
+        if self.sub_mode is not None:
+            v = np.zeros(10, dtype=np.int64)
+            check(lib().kryst_pc_asm_ilu_info(self.h, v.ctypes.data_as(_ffi.c_i64p), len(v)))
+            keys = ("nsub", "ext_rows", "max_rows", "nnz_l", "nnz_u", "max_levels", "lds_bytes", "cap", "nnz_s", "layout_entries")
+            return {k: int(x) for k, x in zip(keys, v)}
         ns, ext, mx = C.c_int64(), C.c_int64(), C.c_int32()
         check(lib().kryst_pc_asm_info(self.h, C.byref(ns), C.byref(ext), C.byref(mx)))
         return {"nsub": ns.value, "ext_rows": ext.value, "max_rows": mx.value}
 
     def export(self):
         """-> (ptr int64, idx int32, owner int32, tiles float64): the (grown) subdomains sorted ascending, the last un-grown subdomain of
-        every row (-1: none), the inverses subdomain after subdomain, column-major inside a tile (tiles[off_k + j b + i] = Binv_k[i][j])."""
+        every row (-1: none), the inverses subdomain after subdomain, column-major inside a tile (tiles[off_k + j b + i] = Binv_k[i][j]).
+        With ILU sub-solves -> (ptr, idx, owner, factors): factors[k] = dict(row_ptr int32 (b_k + 1), col int32 (local columns, ascending
+        within a row), val float64 (l_ij below the diagonal, u_ij on and above it), lev_l, lev_u int32 (b_k: every row's level, from 1, in
+        the forward and in the backward sweep))."""
         inf = self.info()
+        if self.sub_mode is not None:
+            ns, ext = inf["nsub"], inf["ext_rows"]
+            ptr, ent = np.zeros(ns + 1, dtype=np.int64), np.zeros(ns + 1, dtype=np.int64)
+            idx, owner = np.zeros(ext, dtype=np.int32), np.zeros(self._a.nrows(), dtype=np.int32)
+            rp, col, val = np.zeros(ext + ns, dtype=np.int32), np.zeros(inf["nnz_s"], dtype=np.int32), np.zeros(inf["nnz_s"], dtype=np.float64)
+            ll, lu = np.zeros(ext, dtype=np.int32), np.zeros(ext, dtype=np.int32)
+            i32 = lambda v: v.ctypes.data_as(_ffi.c_i32p)
+            check(lib().kryst_pc_asm_ilu_export(self.h, ptr.ctypes.data_as(_ffi.c_i64p), i32(idx), i32(owner), ent.ctypes.data_as(_ffi.c_i64p),
+                                                i32(rp), i32(col), _dp(val), i32(ll), i32(lu)))
+            factors = []
+            for k in range(ns):
+                lo, hi = int(ptr[k]), int(ptr[k + 1])
+                factors.append({"row_ptr": rp[lo + k:hi + k + 1].copy() if hi > lo else np.zeros(1, dtype=np.int32),
+                                "col": col[ent[k]:ent[k + 1]], "val": val[ent[k]:ent[k + 1]], "lev_l": ll[lo:hi], "lev_u": lu[lo:hi]})
+            return ptr, idx, owner, factors
         ptr = np.zeros(inf["nsub"] + 1, dtype=np.int64)
         check(lib().kryst_pc_asm_export(self.h, ptr.ctypes.data_as(_ffi.c_i64p), None, None, None))
         b = np.diff(ptr)
@@ -1520,8 +1566,8 @@ class PC:
         return PC("AMG", max_levels=max_levels, threshold=threshold)
 
     @staticmethod
-    def AdditiveSchwarz(overlap=0, subdomains=None, nparts=None):   # pc_context.rs:75 AdditiveSchwarz (no parameters there); asm.rs:34 new(overlap, subdomains)
-        return PC("AdditiveSchwarz", overlap=overlap, subdomains=subdomains, nparts=nparts)
+    def AdditiveSchwarz(overlap=0, subdomains=None, nparts=None, sub=None):   # pc_context.rs:75 AdditiveSchwarz (no parameters there); asm.rs:34 new(overlap, subdomains)
+        return PC("AdditiveSchwarz", overlap=overlap, subdomains=subdomains, nparts=nparts, sub=sub)   # sub: None (direct), "ilu0" or "ilup0" (labelled extension)
 
     @staticmethod
     def Ssor(omega=1.0, its=1):                      # pc_context.rs:45 Ssor (no parameters there)
@@ -1550,7 +1596,8 @@ class PC:
         if k == "AMG" and "max_levels" in q:          # PC.AMG(...); the bare PC("AMG") keeps raising Unsupported, as before
             return Amg(q["max_levels"], q["threshold"]).setup(a)
         if k == "AdditiveSchwarz" and "overlap" in q:  # PC.AdditiveSchwarz(...); the bare PC("AdditiveSchwarz") keeps raising Unsupported
-            return AdditiveSchwarz(q["overlap"], q["subdomains"], q["nparts"]).setup(a)
+            pc = AdditiveSchwarz(q["overlap"], q["subdomains"], q["nparts"])
+            return (pc if q.get("sub") is None else pc.with_sub_ilu(q["sub"])).setup(a)
         if k == "Ssor" and "omega" in q:              # PC.Ssor(...); the bare PC("Ssor") keeps raising Unsupported
             return Sor(q["omega"], q["its"], 1, MatSorType.SYMMETRIC_SWEEP, 0.0).setup(a)
         if k == "Multicolor" and "omega" in q:        # PC.Multicolor(colors); the bare PC("Multicolor") keeps raising Unsupported

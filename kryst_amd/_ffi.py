@@ -106,6 +106,10 @@ SIGNATURES = {
     "kryst_pc_asm_uniform": (C.c_int32, [Handle, C.c_int64, C.c_int32, C.c_int32, C.POINTER(Handle)]),
     "kryst_pc_asm_info": (C.c_int32, [Handle, c_i64p, c_i64p, c_i32p]),
     "kryst_pc_asm_export": (C.c_int32, [Handle, c_i64p, c_i32p, c_i32p, c_dp]),
+    "kryst_pc_asm_ilu": (C.c_int32, [Handle, c_i64p, c_i64p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Handle)]),
+    "kryst_pc_asm_ilu_uniform": (C.c_int32, [Handle, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Handle)]),
+    "kryst_pc_asm_ilu_info": (C.c_int32, [Handle, c_i64p, C.c_int32]),
+    "kryst_pc_asm_ilu_export": (C.c_int32, [Handle, c_i64p, c_i32p, c_i32p, c_i64p, c_i32p, c_i32p, c_dp, c_i32p, c_i32p]),
     "kryst_pc_sor": (C.c_int32, [Handle, C.c_double, C.c_int64, C.c_int64, C.c_uint32, C.c_double, c_i32p, C.POINTER(Handle)]),
     "kryst_pc_sor_info": (C.c_int32, [Handle, c_i32p, c_i32p, c_i64p, c_i32p, c_i32p]),
     "kryst_pc_spai": (C.c_int32, [Handle, C.c_int32, c_i64p, c_i64p, C.c_int64, C.c_double, C.POINTER(Handle)]),

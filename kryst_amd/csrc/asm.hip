@@ -10,7 +10,7 @@
 // duplicates removed); tiles by one workgroup per subdomain, one row per lane (one wave up to 64 rows, two waves up to 128), the tile in LDS.
 // Apply: a products kernel X[off_k + i] = sum_j Binv_k[i][j] r[g_k[j]] (one position per lane, r|_g staged in LDS, tiles column-major) and a
 // combine kernel z[row] = ((+0.0 + X[p1]) + X[p2]) + ... over a row -> positions map built at set-up.
-#include "pc.h"
+#include "asm.h"
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -288,22 +288,14 @@ int32_t AsmPc::apply(int64_t, const double* r, double* z, const int* done) {
                            (const int32_t*)d_idx, total, r, d_x, done);
         KR_HIP(hipGetLastError());
     }
-    if (n > 0) {
-        hipLaunchKernelGGL(asm_combine_kernel, dim3(asm_grid(n, KR_ASM_T)), dim3(KR_ASM_T), 0, ctx->s_main, (const int32_t*)d_mptr,
-                           (const int32_t*)d_mpos, (const double*)d_x, n, z, done);
-        KR_HIP(hipGetLastError());
-    }
-    return KRYST_OK;
+    return asm_combine_launch(ctx, d_mptr, d_mpos, d_x, n, z, done);
 }
 
-template <class T> static int32_t asm_upload(kryst_ctx_t ctx, T** d, const std::vector<T>& h, const char* what) {
-    if (pool_malloc(d, sizeof(T) * std::max<size_t>(h.size(), 1)) != hipSuccess) {
-        (void)hipGetLastError();
-        *d = nullptr;
-        set_error("additive Schwarz: out of device memory (%s)", what);
-        return KRYST_ERR_HIP;
+int32_t asm_combine_launch(kryst_ctx_t ctx, const int32_t* mptr, const int32_t* mpos, const double* X, int64_t n, double* z, const int* done) {
+    if (n > 0) {
+        hipLaunchKernelGGL(asm_combine_kernel, dim3(asm_grid(n, KR_ASM_T)), dim3(KR_ASM_T), 0, ctx->s_main, mptr, mpos, X, n, z, done);
+        KR_HIP(hipGetLastError());
     }
-    if (!h.empty()) KR_HIP(hipMemcpyAsync(*d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, ctx->s_main));
     return KRYST_OK;
 }
 
@@ -311,7 +303,7 @@ template <class T> static int32_t asm_upload(kryst_ctx_t ctx, T** d, const std::
 // an earlier preconditioner's tiles, the growth's own scratch) as used, so when the figure falls short the pool is given back to the driver
 // and the figure taken again.  Test hook: KRYST_ASM_MEM_LIMIT_MB caps the free figure at that many MiB less what the pool holds, as if
 // the device had that much free with the pool empty.
-static int32_t asm_check_memory(int device, unsigned long long need) {
+int32_t asm_check_memory(int device, unsigned long long need) {
     unsigned long long avail = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
         size_t fr = 0, tot = 0;
@@ -334,11 +326,141 @@ static unsigned long long asm_bytes(int64_t n, int64_t nsub, unsigned long long 
     return 8ull * sb2 + (4ull + 4ull + 8ull) * sb + 12ull * (unsigned long long)(nsub + 1) + 4ull * (unsigned long long)(n + 1) + 4ull * m;
 }
 
+// ---------------------------------------------------------------- growth of sets past 128 rows: a bitmap over the rows per workgroup
+// Workgroup w owns bm[w W .. (w + 1) W) (W = ceil(n / 32) words, all zero between subdomains) and cur[w cap .. (w + 1) cap).  Per layer the
+// neighbours of the rows of cur are marked; the marked rows of the words [wlo, whi] (the span of everything marked so far), taken in
+// ascending order, are the new cur.  More than cap rows: sizes[k] = -1 and err = min(err, k).  out == nullptr: sizes only (the first of
+// two passes; the host turns the sizes into the offsets ooff of the second).  The bitmap is read and cleared with device-scope atomics:
+// the marks are atomics, which a cached load need not see.
+__global__ __launch_bounds__(KR_ASM_T) void asm_grow_wide_kernel(const int32_t* a_ptr, const int32_t* a_col, const int32_t* t_ptr, const int32_t* t_col,
+                                                                const int64_t* ptr, const int32_t* idx, int64_t nsub, int overlap, int cap, int64_t W,
+                                                                unsigned int* bm_all, int32_t* cur_all, const int64_t* ooff, int32_t* out,
+                                                                int32_t* sizes, unsigned long long* err) {
+    __shared__ int part[KR_ASM_T];
+    __shared__ int s_lo, s_hi;
+    const int t = threadIdx.x;
+    unsigned int* bm = bm_all + (int64_t)blockIdx.x * W;
+    int32_t* cur = cur_all + (int64_t)blockIdx.x * cap;
+    for (int64_t k = blockIdx.x; k < nsub; k += gridDim.x) {                // uniform over the workgroup
+        const int64_t lo = ptr[k];
+        int nu = (int)(ptr[k + 1] - lo);
+        bool fail = false;
+        if (nu > 0) {
+            if (t == 0) { s_lo = idx[lo] >> 5; s_hi = idx[lo + nu - 1] >> 5; }
+            for (int i = t; i < nu; i += KR_ASM_T) { const int r = idx[lo + i]; cur[i] = r; atomicOr(&bm[r >> 5], 1u << (r & 31)); }
+            __syncthreads();
+            for (int layer = 0; layer < overlap && !fail; ++layer) {
+                int mylo = INT_MAX, myhi = -1;
+                for (int i = t; i < nu; i += KR_ASM_T) {
+                    const int r = cur[i];
+                    for (int32_t e = a_ptr[r]; e < a_ptr[r + 1]; ++e) { const int c = a_col[e]; atomicOr(&bm[c >> 5], 1u << (c & 31)); mylo = min(mylo, c >> 5); myhi = max(myhi, c >> 5); }
+                    for (int32_t e = t_ptr[r]; e < t_ptr[r + 1]; ++e) { const int c = t_col[e]; atomicOr(&bm[c >> 5], 1u << (c & 31)); mylo = min(mylo, c >> 5); myhi = max(myhi, c >> 5); }
+                }
+                if (myhi >= 0) { atomicMin(&s_lo, mylo); atomicMax(&s_hi, myhi); }
+                __syncthreads();
+                const int wlo = s_lo, whi = s_hi;
+                int base = 0;
+                for (int w0 = wlo; w0 <= whi; w0 += KR_ASM_T) {             // uniform
+                    const int w = w0 + t;
+                    const unsigned int bits = w <= whi ? __hip_atomic_load(&bm[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+                    const int cnt = __popc(bits);
+                    part[t] = cnt;
+                    __syncthreads();
+                    for (int o = 1; o < KR_ASM_T; o <<= 1) {
+                        const int x = (t >= o) ? part[t - o] : 0;
+                        __syncthreads();
+                        part[t] += x;
+                        __syncthreads();
+                    }
+                    int q = base + part[t] - cnt;
+                    unsigned int rest = bits;
+                    while (rest) {
+                        const int bit = __ffs(rest) - 1;
+                        rest &= rest - 1;
+                        if (q < cap) cur[q] = (w << 5) | bit;
+                        ++q;
+                    }
+                    base += part[KR_ASM_T - 1];
+                    __syncthreads();
+                }
+                if (base > cap) fail = true; else nu = base;
+            }
+            const int wlo = s_lo, whi = s_hi;
+            __syncthreads();
+            for (int w = wlo + t; w <= whi; w += KR_ASM_T) __hip_atomic_store(&bm[w], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (fail) {
+            if (t == 0) { sizes[k] = -1; atomicMin(err, (unsigned long long)k); }
+        } else {
+            if (out) for (int i = t; i < nu; i += KR_ASM_T) out[ooff[k] + i] = cur[i];
+            if (t == 0) sizes[k] = nu;
+        }
+        __syncthreads();                                                    // the next subdomain reuses cur, the bitmap and the LDS
+    }
+}
+
+static int32_t asm_grow_wide(kryst_csr_t a, int overlap, std::vector<int64_t>& ptr, std::vector<int32_t>& idx, int cap) {
+    kryst_ctx_t ctx = a->ctx;
+    const int64_t nsub = (int64_t)ptr.size() - 1, n = a->nrows, W = (n + 31) / 32;
+    const unsigned grid = (unsigned)std::min<int64_t>(nsub, 128);
+    DevCsr at;
+    int64_t* d_ptr = nullptr; int32_t* d_idx = nullptr; int32_t* d_out = nullptr; int32_t* d_sizes = nullptr; unsigned long long* d_err = nullptr;
+    unsigned int* d_bm = nullptr; int32_t* d_cur = nullptr; int64_t* d_ooff = nullptr;
+    std::vector<int32_t> sizes((size_t)nsub);
+    std::vector<int64_t> ooff((size_t)nsub + 1, 0);
+    int32_t rc = csr_transpose(ctx, "additive Schwarz", a->d_row_ptr, a->d_col, a->d_val, a->nrows, a->ncols, false, 0.0, at);
+    do {
+        if (rc != KRYST_OK) break;
+        if ((rc = asm_upload(ctx, &d_ptr, ptr, "index sets")) != KRYST_OK) break;
+        if ((rc = asm_upload(ctx, &d_idx, idx, "index sets")) != KRYST_OK) break;
+        if (pool_malloc(&d_bm, sizeof(unsigned int) * (size_t)grid * (size_t)std::max<int64_t>(W, 1)) != hipSuccess ||
+            pool_malloc(&d_cur, sizeof(int32_t) * (size_t)grid * (size_t)cap) != hipSuccess ||
+            pool_malloc(&d_sizes, sizeof(int32_t) * (size_t)nsub) != hipSuccess || pool_malloc(&d_err, sizeof(unsigned long long)) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("additive Schwarz: out of device memory (growth of %lld subdomains)", (long long)nsub); rc = KRYST_ERR_HIP; break;
+        }
+        if (hipMemsetAsync(d_bm, 0, sizeof(unsigned int) * (size_t)grid * (size_t)std::max<int64_t>(W, 1), ctx->s_main) != hipSuccess ||
+            hipMemsetAsync(d_err, 0xFF, sizeof(unsigned long long), ctx->s_main) != hipSuccess) { rc = KRYST_ERR_HIP; break; }
+        for (int pass = 0; pass < 2 && rc == KRYST_OK; ++pass) {
+            if (pass == 1) {
+                for (int64_t k = 0; k < nsub; ++k) ooff[(size_t)k + 1] = ooff[(size_t)k] + sizes[(size_t)k];
+                if (ooff.back() >= INT32_MAX) { set_error("bad argument: pc_asm: more than 2^31 - 1 subdomain rows after growth"); rc = KRYST_ERR_ARG; break; }
+                if ((rc = asm_upload(ctx, &d_ooff, ooff, "grown index sets")) != KRYST_OK) break;
+                if (pool_malloc(&d_out, sizeof(int32_t) * (size_t)std::max<int64_t>(ooff.back(), 1)) != hipSuccess) {
+                    (void)hipGetLastError(); d_out = nullptr;
+                    set_error("additive Schwarz: out of device memory (%lld grown subdomain rows)", (long long)ooff.back()); rc = KRYST_ERR_HIP; break;
+                }
+            }
+            hipLaunchKernelGGL(asm_grow_wide_kernel, dim3(grid), dim3(KR_ASM_T), 0, ctx->s_main, a->d_row_ptr, a->d_col, (const int32_t*)at.ptr,
+                               (const int32_t*)at.idx, (const int64_t*)d_ptr, (const int32_t*)d_idx, nsub, overlap, cap, W, d_bm, d_cur,
+                               (const int64_t*)d_ooff, d_out, d_sizes, d_err);
+            if (hipGetLastError() != hipSuccess) { set_error("additive Schwarz: growth launch failed"); rc = KRYST_ERR_HIP; break; }
+            unsigned long long e = KR_ASM_NOERR;
+            if (hipMemcpyAsync(&e, d_err, sizeof e, hipMemcpyDeviceToHost, ctx->s_main) != hipSuccess ||
+                hipMemcpyAsync(sizes.data(), d_sizes, sizeof(int32_t) * sizes.size(), hipMemcpyDeviceToHost, ctx->s_main) != hipSuccess ||
+                hipStreamSynchronize(ctx->s_main) != hipSuccess) { set_error("additive Schwarz: growth failed on the device"); rc = KRYST_ERR_HIP; break; }
+            if (e != KR_ASM_NOERR) {
+                set_error("additive Schwarz: subdomain %lld grows past %d rows with overlap %d", (long long)e, cap, overlap);
+                rc = KRYST_UNSUPPORTED; break;
+            }
+        }
+        if (rc != KRYST_OK) break;
+        idx.resize((size_t)ooff.back());
+        if ((!idx.empty() && hipMemcpyAsync(idx.data(), d_out, sizeof(int32_t) * idx.size(), hipMemcpyDeviceToHost, ctx->s_main) != hipSuccess) ||
+            hipStreamSynchronize(ctx->s_main) != hipSuccess) { set_error("additive Schwarz: growth failed on the device"); rc = KRYST_ERR_HIP; break; }
+        ptr = ooff;
+    } while (0);
+    dev_csr_free(at);
+    for (void* p : {(void*)d_ptr, (void*)d_idx, (void*)d_out, (void*)d_sizes, (void*)d_err, (void*)d_bm, (void*)d_cur, (void*)d_ooff}) (void)pool_free(p);
+    return rc;
+}
+
 // grows the sorted sets (ptr, idx) by `overlap` layers on the device; on success (ptr, idx) hold the grown sets
-static int32_t asm_grow(kryst_csr_t a, int overlap, std::vector<int64_t>& ptr, std::vector<int32_t>& idx) {
+int32_t asm_grow(kryst_csr_t a, int overlap, std::vector<int64_t>& ptr, std::vector<int32_t>& idx, int cap) {
     kryst_ctx_t ctx = a->ctx;
     const int64_t nsub = (int64_t)ptr.size() - 1;
     if (nsub == 0 || overlap <= 0) return KRYST_OK;
+    if (cap > KR_ASM_MAX) return asm_grow_wide(a, overlap, ptr, idx, cap);
     DevCsr at;
     int64_t* d_ptr = nullptr; int32_t* d_idx = nullptr; int32_t* d_out = nullptr; int32_t* d_sizes = nullptr; unsigned long long* d_err = nullptr;
     std::vector<int32_t> sizes((size_t)nsub), out;
@@ -440,28 +562,26 @@ static int32_t asm_tiles_run(AsmPc* pc) {
     return KRYST_ZERO_PIVOT;
 }
 
-// the common set-up over index sets packed like CSR rows (unsorted, possibly overlapping, possibly leaving rows uncovered)
-static int32_t asm_setup(kryst_csr_t a, const int64_t* sub_ptr, const int64_t* sub_idx, int64_t nsub, int32_t overlap, int32_t variant,
-                         kryst_pc_t* out) {
+// ---------------------------------------------------------------- the host bookkeeping shared with the ILU sub-solves (asm.h)
+int32_t asm_sort_sets(kryst_csr_t a, const int64_t* sub_ptr, const int64_t* sub_idx, int64_t nsub, int cap, AsmSets& s) {
     const int64_t n = a->nrows;
     KR_ARG(nsub == 0 || sub_ptr[0] == 0, "pc_asm: sub_ptr[0] != 0");
-    std::vector<int64_t> ptr((size_t)nsub + 1, 0);
-    unsigned long long sb = 0, sb2 = 0;
+    std::vector<int64_t>& ptr = s.ptr;
+    ptr.assign((size_t)nsub + 1, 0);
     for (int64_t k = 0; k < nsub; ++k) {
         const int64_t len = sub_ptr[k + 1] - sub_ptr[k];
         KR_ARG(len >= 0, "pc_asm: sub_ptr is not ascending");
-        if (len > KR_ASM_MAX) {
-            set_error("additive Schwarz: subdomain %lld has %lld rows; at most %d are supported", (long long)k, (long long)len, KR_ASM_MAX);
+        if (len > cap) {
+            set_error("additive Schwarz: subdomain %lld has %lld rows; at most %d are supported", (long long)k, (long long)len, cap);
             return KRYST_UNSUPPORTED;
         }
         ptr[(size_t)k + 1] = ptr[(size_t)k] + len;
-        sb += (unsigned long long)len; sb2 += (unsigned long long)(len * len);
     }
     KR_ARG(nsub == 0 || sub_idx || ptr.back() == 0, "pc_asm: sub_idx is NULL");
     KR_ARG(ptr.back() < INT32_MAX, "pc_asm: more than 2^31 - 1 subdomain rows");
     // sort each index set (deviation 2), check it, and find the owner of every row: the last un-grown set that contains it
-    std::vector<int32_t> idx((size_t)ptr.back());
-    std::vector<int32_t> owner((size_t)n, -1);
+    s.idx.assign((size_t)ptr.back(), 0);
+    s.owner.assign((size_t)n, -1);
     for (int64_t k = 0; k < nsub; ++k) {
         const int64_t lo = ptr[(size_t)k], len = ptr[(size_t)k + 1] - lo;
         std::vector<int64_t> g(sub_idx + sub_ptr[k], sub_idx + sub_ptr[k] + len);
@@ -469,25 +589,21 @@ static int32_t asm_setup(kryst_csr_t a, const int64_t* sub_ptr, const int64_t* s
         for (int64_t i = 0; i < len; ++i) {
             KR_ARG(g[(size_t)i] >= 0 && g[(size_t)i] < n, "pc_asm: index out of range");
             KR_ARG(i == 0 || g[(size_t)i] != g[(size_t)i - 1], "pc_asm: index repeated within a subdomain");
-            idx[(size_t)(lo + i)] = (int32_t)g[(size_t)i];
-            owner[(size_t)g[(size_t)i]] = (int32_t)k;
+            s.idx[(size_t)(lo + i)] = (int32_t)g[(size_t)i];
+            s.owner[(size_t)g[(size_t)i]] = (int32_t)k;
         }
     }
-    KR_HIP(hipSetDevice(a->ctx->device));
-    // the un-grown sets bound the grown ones from below: a request that cannot fit fails before anything is allocated
-    KR_TRY(asm_check_memory(a->ctx->device, asm_bytes(n, nsub, sb, sb2, sb)));
-    if (variant != KRYST_ASM_AS_WRITTEN) KR_TRY(asm_grow(a, overlap, ptr, idx));
-    sb = 0; sb2 = 0;
-    int bmax = 0;
-    for (int64_t k = 0; k < nsub; ++k) {
-        const unsigned long long b = (unsigned long long)(ptr[(size_t)k + 1] - ptr[(size_t)k]);
-        sb += b; sb2 += b * b; bmax = std::max(bmax, (int)b);
-    }
-    // row -> positions in X: every subdomain that contains the row, ascending (RAS: the owner's position only)
-    std::vector<int32_t> mptr((size_t)n + 1, 0), mpos;
+    return KRYST_OK;
+}
+
+void asm_row_map(int64_t n, int32_t variant, const AsmSets& s, std::vector<int32_t>& mptr, std::vector<int32_t>& mpos) {
+    const std::vector<int64_t>& ptr = s.ptr;
+    const std::vector<int32_t>& idx = s.idx;
+    mptr.assign((size_t)n + 1, 0);
+    mpos.clear();
     if (variant == KRYST_ASM_RESTRICTED) {
         for (int64_t row = 0; row < n; ++row) {
-            const int32_t o = owner[(size_t)row];
+            const int32_t o = s.owner[(size_t)row];
             if (o >= 0) {
                 const auto b = idx.begin() + ptr[(size_t)o], e = idx.begin() + ptr[(size_t)o + 1];
                 mpos.push_back((int32_t)(std::lower_bound(b, e, (int32_t)row) - idx.begin()));
@@ -501,6 +617,45 @@ static int32_t asm_setup(kryst_csr_t a, const int64_t* sub_ptr, const int64_t* s
         std::vector<int32_t> fill(mptr.begin(), mptr.end() - 1);
         for (size_t p = 0; p < idx.size(); ++p) mpos[(size_t)fill[(size_t)idx[p]]++] = (int32_t)p;   // ascending p = ascending subdomain
     }
+}
+
+void asm_uniform_sets(int64_t n, int64_t nparts, std::vector<int64_t>& ptr, std::vector<int64_t>& idx) {
+    const int64_t p = std::max<int64_t>(nparts, 1), chunk = (n + p - 1) / p;
+    ptr.assign((size_t)p + 1, 0);
+    idx.clear();
+    idx.reserve((size_t)n);
+    for (int64_t i = 0; i < p; ++i) {
+        const int64_t s = i * chunk, e = std::min((i + 1) * chunk, n);
+        for (int64_t r = s; r < e; ++r) idx.push_back(r);
+        ptr[(size_t)i + 1] = (int64_t)idx.size();
+    }
+}
+
+// the common set-up over index sets packed like CSR rows (unsorted, possibly overlapping, possibly leaving rows uncovered)
+static int32_t asm_setup(kryst_csr_t a, const int64_t* sub_ptr, const int64_t* sub_idx, int64_t nsub, int32_t overlap, int32_t variant,
+                         kryst_pc_t* out) {
+    const int64_t n = a->nrows;
+    AsmSets sets;
+    KR_TRY(asm_sort_sets(a, sub_ptr, sub_idx, nsub, KR_ASM_MAX, sets));
+    std::vector<int64_t>& ptr = sets.ptr;
+    std::vector<int32_t>& idx = sets.idx;
+    unsigned long long sb = 0, sb2 = 0;
+    for (int64_t k = 0; k < nsub; ++k) {
+        const unsigned long long b = (unsigned long long)(ptr[(size_t)k + 1] - ptr[(size_t)k]);
+        sb += b; sb2 += b * b;
+    }
+    KR_HIP(hipSetDevice(a->ctx->device));
+    // the un-grown sets bound the grown ones from below: a request that cannot fit fails before anything is allocated
+    KR_TRY(asm_check_memory(a->ctx->device, asm_bytes(n, nsub, sb, sb2, sb)));
+    if (variant != KRYST_ASM_AS_WRITTEN) KR_TRY(asm_grow(a, overlap, ptr, idx, KR_ASM_MAX));
+    sb = 0; sb2 = 0;
+    int bmax = 0;
+    for (int64_t k = 0; k < nsub; ++k) {
+        const unsigned long long b = (unsigned long long)(ptr[(size_t)k + 1] - ptr[(size_t)k]);
+        sb += b; sb2 += b * b; bmax = std::max(bmax, (int)b);
+    }
+    std::vector<int32_t> mptr, mpos;
+    asm_row_map(n, variant, sets, mptr, mpos);
     KR_TRY(asm_check_memory(a->ctx->device, asm_bytes(n, nsub, sb, sb2, mpos.size())));
     std::vector<int32_t> xoff((size_t)nsub + 1), posk(idx.size());
     std::vector<int64_t> toff((size_t)nsub + 1, 0);
@@ -527,14 +682,14 @@ static int32_t asm_setup(kryst_csr_t a, const int64_t* sub_ptr, const int64_t* s
         (void)hipGetLastError(); pc->d_tile = nullptr;
         set_error("additive Schwarz: out of device memory for %lld tile entries", (long long)toff.back()); rc = KRYST_ERR_HIP;
     }
-    pc->ptr_h = std::move(ptr); pc->idx_h = std::move(idx); pc->owner_h = std::move(owner);
+    pc->ptr_h = std::move(sets.ptr); pc->idx_h = std::move(sets.idx); pc->owner_h = std::move(sets.owner);
     if (rc == KRYST_OK) rc = asm_tiles_run(pc);
     if (rc != KRYST_OK) { kryst_pc_destroy(pc); return rc; }
     *out = pc;
     return KRYST_OK;
 }
 
-static int32_t asm_check(kryst_csr_t a, int32_t overlap, int32_t variant) {
+int32_t asm_check(kryst_csr_t a, int32_t overlap, int32_t variant) {
     if (a->dist) { set_error("additive Schwarz: distributed operators are not supported"); return KRYST_UNSUPPORTED; }
     KR_ARG(a->nrows == a->ncols && a->nrows == a->xlen, "pc_asm: square operator required");
     KR_ARG(a->nrows < INT32_MAX, "pc_asm: more than 2^31 - 1 rows");
@@ -559,15 +714,9 @@ int32_t kryst_pc_asm(kryst_csr_t a, const int64_t* sub_ptr, const int64_t* sub_i
 int32_t kryst_pc_asm_uniform(kryst_csr_t a, int64_t nparts, int32_t overlap, int32_t variant, kryst_pc_t* out) {
     KR_ARG(a && out && nparts >= 0, "pc_asm_uniform");
     KR_TRY(asm_check(a, overlap, variant));
-    const int64_t n = a->nrows, p = std::max<int64_t>(nparts, 1), chunk = (n + p - 1) / p;
-    std::vector<int64_t> ptr((size_t)p + 1, 0), idx;
-    idx.reserve((size_t)n);
-    for (int64_t i = 0; i < p; ++i) {
-        const int64_t s = i * chunk, e = std::min((i + 1) * chunk, n);
-        for (int64_t r = s; r < e; ++r) idx.push_back(r);
-        ptr[(size_t)i + 1] = (int64_t)idx.size();
-    }
-    return asm_setup(a, ptr.data(), idx.data(), p, overlap, variant, out);
+    std::vector<int64_t> ptr, idx;
+    asm_uniform_sets(a->nrows, nparts, ptr, idx);
+    return asm_setup(a, ptr.data(), idx.data(), (int64_t)ptr.size() - 1, overlap, variant, out);
 }
 
 int32_t kryst_pc_asm_info(kryst_pc_t h, int64_t* nsub, int64_t* ext_rows, int32_t* max_rows) {

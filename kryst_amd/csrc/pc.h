@@ -3,7 +3,7 @@
 #pragma once
 #include "csr.h"
 
-enum { KR_PC_IDENTITY = 1, KR_PC_JACOBI = 2, KR_PC_ILU = 3, KR_PC_CHEB_STUB = 6, KR_PC_CHEB = 7, KR_PC_SPAI = 9, KR_PC_BLOCK_JACOBI = 10, KR_PC_AMG = 11, KR_PC_ASM = 12, KR_PC_SOR = 13 };
+enum { KR_PC_IDENTITY = 1, KR_PC_JACOBI = 2, KR_PC_ILU = 3, KR_PC_CHEB_STUB = 6, KR_PC_CHEB = 7, KR_PC_SPAI = 9, KR_PC_BLOCK_JACOBI = 10, KR_PC_AMG = 11, KR_PC_ASM = 12, KR_PC_SOR = 13, KR_PC_ASM_ILU = 14 };
 
 struct kryst_pc_s {
     const kryst_ctx_t ctx;
