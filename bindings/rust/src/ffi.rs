@@ -12,6 +12,7 @@ pub type HostFactors = *mut c_void;
 pub type HostAmg = *mut c_void;
 pub type Dense = *mut c_void;
 pub type Lu = *mut c_void;
+pub type MVec = *mut c_void;
 
 pub const KRYST_OK: i32 = 0;
 pub const KRYST_FACTOR_ERROR: i32 = 1;
@@ -240,4 +241,25 @@ extern "C" {
                                          vals: *mut f64) -> i64;
     pub fn kryst_host_read_petsc_binary(path: *const c_char, nrows: *mut i64, ncols: *mut i64, row_ptr: *mut i64, col_idx: *mut i64,
                                         vals: *mut f64) -> i64;
+}
+
+// several right-hand sides at once (kryst_mvec_t: n x k, k in {2, 4, 8}; column j of a batched call = the single-vector call on column j)
+extern "C" {
+    pub fn kryst_mvec_create(ctx: Ctx, n: i64, k: i32, out: *mut MVec) -> i32;
+    pub fn kryst_mvec_destroy(mv: MVec) -> i32;
+    pub fn kryst_mvec_shape(mv: MVec, n: *mut i64, k: *mut i32) -> i32;
+    pub fn kryst_mvec_upload(mv: MVec, host: *const f64, ld: i64) -> i32;
+    pub fn kryst_mvec_download(mv: MVec, host: *mut f64, ld: i64) -> i32;
+    pub fn kryst_mvec_set_column(mv: MVec, j: i32, v: Vecd) -> i32;
+    pub fn kryst_mvec_get_column(mv: MVec, j: i32, v: Vecd) -> i32;
+    pub fn kryst_bench_mvec_padding(mv: MVec, fill: *const f64, dirty: *mut i64) -> i32;
+    pub fn kryst_spmm(a: Csr, x: MVec, y: MVec) -> i32;
+    pub fn kryst_cg_solve_multi_dev(b: MVec, x: MVec, a: Csr, pc: Pc, params: *const Params, stats: *mut Stats, status: *mut i32,
+                                    hist: *mut f64, hist_cap: i64, hist_len: *mut i64) -> i32;
+    pub fn kryst_pcg_solve_multi_dev(b: MVec, x: MVec, a: Csr, pc: Pc, params: *const Params, stats: *mut Stats, status: *mut i32,
+                                     hist: *mut f64, hist_cap: i64, hist_len: *mut i64) -> i32;
+    pub fn kryst_cg_solve_multi(b: *const f64, x: *mut f64, n: i64, k: i32, ld: i64, a: Csr, pc: Pc, params: *const Params,
+                                stats: *mut Stats, status: *mut i32, hist: *mut f64, hist_cap: i64, hist_len: *mut i64) -> i32;
+    pub fn kryst_pcg_solve_multi(b: *const f64, x: *mut f64, n: i64, k: i32, ld: i64, a: Csr, pc: Pc, params: *const Params,
+                                 stats: *mut Stats, status: *mut i32, hist: *mut f64, hist_cap: i64, hist_len: *mut i64) -> i32;
 }

@@ -598,6 +598,51 @@ int64_t kryst_host_read_matrix_market(const char* path, int64_t* nrows, int64_t*
 int64_t kryst_host_read_petsc_binary(const char* path, int64_t* nrows, int64_t* ncols, int64_t* row_ptr,
                                      int64_t* col_idx, double* vals);
 
+/* ---- several right-hand sides at once (an extension: the reference solves one b per call, src/solver/mod.rs:43-49) ----
+ * THE RULE: column j of a batched call is, bit for bit, what the single-vector call returns for column j -- y, x, iterations, every
+ * residual-history entry, final_residual, converged and the status.  The matrix is read once for all columns.
+ * fp64, one rank; k is 2, 4 or 8 (anything else: KRYST_ERR_ARG).
+ *
+ * kryst_mvec_t widens V = Vec<f64> (the `b` / `x` of src/solver/mod.rs:43-49) to n x k: element (i, j) lives at i * k + j on the device (a
+ * row's k values are contiguous), allocated as (ceil(n / 512) * 512 + 512) * k doubles, zero at creation -- kryst_vec_t's padding, per column. */
+typedef struct kryst_mvec_s* kryst_mvec_t;
+int32_t kryst_mvec_create(kryst_ctx_t ctx, int64_t n, int32_t k, kryst_mvec_t* out);
+int32_t kryst_mvec_destroy(kryst_mvec_t mv);
+int32_t kryst_mvec_shape(kryst_mvec_t mv, int64_t* n, int32_t* k);                    /* either pointer may be NULL */
+/* the host side is column-major: column j starts at host + j * ld, ld >= n (kryst_vec_upload / _download, wrappers.rs' Vec<f64>, per column);
+ * the (de)interleave runs on the device */
+int32_t kryst_mvec_upload(kryst_mvec_t mv, const double* host, int64_t ld);
+int32_t kryst_mvec_download(kryst_mvec_t mv, double* host, int64_t ld);
+/* column j <- v / v <- column j (kryst_vec_copy per column); lengths must agree, 0 <= j < k */
+int32_t kryst_mvec_set_column(kryst_mvec_t mv, int32_t j, kryst_vec_t v);
+int32_t kryst_mvec_get_column(kryst_mvec_t mv, int32_t j, kryst_vec_t v);
+/* test hook, kryst_bench_vec_padding for a multivector: *dirty (may be NULL) counts the allocated elements of ROW index >= n whose 64 bits
+ * are not +0.0, before any fill; fill != NULL then sets every one of them -- (ceil(n / 512) * 512 + 512 - n) * k elements -- to *fill */
+int32_t kryst_bench_mvec_padding(kryst_mvec_t mv, const double* fill, int64_t* dirty);
+/* SparseMatrix::spmv (sparse.rs:56-67) on k columns: Y <- A X, Y overwritten; column j is kryst_spmv on column j, whatever storage form
+ * kryst_spmv streams for the operator (this kernel reads the plain CSR arrays).  REFUSED like kryst_spmv: X and Y the same multivector
+ * (KRYST_ERR_ARG before any launch, Y unchanged); a row count or k that does not match: KRYST_ERR_ARG; distributed operators: KRYST_UNSUPPORTED. */
+int32_t kryst_spmm(kryst_csr_t a, kryst_mvec_t x, kryst_mvec_t y);
+/* CgSolver::solve (cg.rs:114-288) / PcgSolver::solve (pcg.rs:114-222) on every column of B with the initial guesses in X: one SpMM per
+ * iteration, every column's scalars on the device in a state of its own; a column that has ended -- converged, the cap (converged = true
+ * at max_iters like the reference), IndefiniteMatrix, IndefinitePreconditioner, max_iters <= 0 -- is frozen while the others go on.
+ * stats[k], status[k] (the column's KError code, KRYST_OK = 0), hist_len[k] and hist (k slices of hist_cap entries, slice j at
+ * hist + j * hist_cap) may each be NULL.  The call returns KRYST_OK whenever it ran, whatever the columns' codes; X(:, j) is written only
+ * when status[j] == KRYST_OK.  B and X may be the same multivector (x0 = b).  kryst_cg_solve_multi* ignores pc (cg.rs:115); for
+ * kryst_pcg_solve_multi* pc may be NULL, Identity or Jacobi, any other kind is KRYST_UNSUPPORTED, as are norm_type outside {0, 1},
+ * has_radius, has_obj_target and distributed operators; nothing is written then.  There is no monitor and no stepping session. */
+int32_t kryst_cg_solve_multi_dev(kryst_mvec_t b, kryst_mvec_t x, kryst_csr_t a, kryst_pc_t pc, const kryst_params_t* params,
+                                 kryst_stats_t* stats, int32_t* status, double* hist, int64_t hist_cap, int64_t* hist_len);
+int32_t kryst_pcg_solve_multi_dev(kryst_mvec_t b, kryst_mvec_t x, kryst_csr_t a, kryst_pc_t pc, const kryst_params_t* params,
+                                  kryst_stats_t* stats, int32_t* status, double* hist, int64_t hist_cap, int64_t* hist_len);
+/* the same with B and X on the host, column-major with leading dimension ld (column j at b + j * ld; x in/out) */
+int32_t kryst_cg_solve_multi(const double* b, double* x, int64_t n, int32_t k, int64_t ld, kryst_csr_t a, kryst_pc_t pc,
+                             const kryst_params_t* params, kryst_stats_t* stats, int32_t* status, double* hist, int64_t hist_cap,
+                             int64_t* hist_len);
+int32_t kryst_pcg_solve_multi(const double* b, double* x, int64_t n, int32_t k, int64_t ld, kryst_csr_t a, kryst_pc_t pc,
+                              const kryst_params_t* params, kryst_stats_t* stats, int32_t* status, double* hist, int64_t hist_cap,
+                              int64_t* hist_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,42 @@ private:
     kryst_ctx_t h_ = nullptr;
 };
 
+// n x k device multivector, k in {2, 4, 8} (kryst_mvec_t): several right-hand sides at once; host data column-major, column j at j * ld
+class MultiVec {
+public:
+    MultiVec(size_t n, size_t k, std::shared_ptr<Context> ctx = Context::global()) : ctx_(std::move(ctx)), n_(n), k_(k) {
+        check(kryst_mvec_create(ctx_->handle(), (int64_t)n, (int32_t)k, &h_));
+    }
+    static MultiVec from_columns(const std::vector<Vec>& cols, std::shared_ptr<Context> ctx = Context::global()) {
+        const size_t n = cols.empty() ? 0 : cols[0].size();
+        MultiVec mv(n, cols.size(), std::move(ctx));
+        Vec host(n * cols.size());
+        for (size_t j = 0; j < cols.size(); ++j) {
+            if (cols[j].size() != n) throw KError(KRYST_ERR_ARG);
+            std::copy(cols[j].begin(), cols[j].end(), host.begin() + (long)(j * n));
+        }
+        mv.upload(host, n);
+        return mv;
+    }
+    MultiVec(MultiVec&& o) noexcept : ctx_(std::move(o.ctx_)), h_(o.h_), n_(o.n_), k_(o.k_) { o.h_ = nullptr; }
+    MultiVec(const MultiVec&) = delete; MultiVec& operator=(const MultiVec&) = delete;
+    ~MultiVec() { if (h_) kryst_mvec_destroy(h_); }
+    size_t nrows() const { return n_; }
+    size_t ncols() const { return k_; }
+    void upload(const Vec& host, size_t ld) { if (host.size() < (k_ ? (k_ - 1) * ld + n_ : 0)) throw KError(KRYST_ERR_ARG); check(kryst_mvec_upload(h_, host.data(), (int64_t)ld)); }
+    void download(Vec& host, size_t ld) const { if (host.size() < (k_ ? (k_ - 1) * ld + n_ : 0)) throw KError(KRYST_ERR_ARG); check(kryst_mvec_download(h_, host.data(), (int64_t)ld)); }
+    Vec column(size_t j) const {
+        if (j >= k_) throw KError(KRYST_ERR_ARG);
+        Vec host(n_ * k_), out(n_);
+        download(host, n_);
+        std::copy(host.begin() + (long)(j * n_), host.begin() + (long)((j + 1) * n_), out.begin());
+        return out;
+    }
+    kryst_mvec_t handle() const { return h_; }
+private:
+    std::shared_ptr<Context> ctx_; kryst_mvec_t h_ = nullptr; size_t n_ = 0, k_ = 0;
+};
+
 // CsrMatrix<f64> resident in HBM; SparseMatrix::{nrows,ncols,spmv} (sparse.rs:4-11,49-68) and MatVec.
 class HipCsrMatrix : public MatVec<Vec> {
 public:
@@ -105,6 +141,7 @@ public:
         check(kryst_spmv_host(h_, x.data(), (int64_t)x.size(), y.data(), (int64_t)y.size()));
     }
     void matvec(const Vec& x, Vec& y) const override { spmv(x, y); }
+    void spmm(const MultiVec& x, MultiVec& y) const { check(kryst_spmm(h_, x.handle(), y.handle())); }      // column j = spmv on column j
     // MatTransVec::mattransvec: y <- A^T x through kryst_spmv_transpose (A^T built on the first call, cached on the operator)
     void mattransvec(const Vec& x, Vec& y) const {
         if (x.size() != nrows_ || y.size() != ncols_) throw KError(KRYST_ERR_ARG);
@@ -370,9 +407,37 @@ public:
         check(rc);
         return SolveStats<double>{(size_t)st.iterations, st.final_residual, st.converged != 0};
     }
+    // several right-hand sides at once (CG and PCG): column j gets what solve() gives for column j, bit for bit.  Returns the columns'
+    // KError codes (KRYST_OK = 0); stats and residual_histories are per column; X(:, j) is written only where the code is KRYST_OK.
+    std::vector<std::vector<double>> residual_histories;
+    std::vector<int32_t> solve_many(const HipCsrMatrix& a, const Preconditioner<HipCsrMatrix, Vec>* pc, const MultiVec& b, MultiVec& x,
+                                    std::vector<SolveStats<double>>& stats) {
+        const size_t k = b.ncols();
+        kryst_params_t p{};
+        p.tol = conv.tol; p.max_iters = (int64_t)conv.max_iters; p.norm_type = (int)norm_type; p.single_reduction = single_reduction;
+        p.has_radius = radius.has_value(); p.radius = radius.value_or(0.0);
+        p.has_obj_target = obj_target.has_value(); p.obj_target = obj_target.value_or(0.0);
+        p.check_every = check_every;
+        std::vector<kryst_stats_t> st(k);
+        std::vector<int32_t> code(k, 0);
+        const size_t cap = std::min<size_t>(conv.max_iters + 8, ((size_t)1 << 19) + 8);
+        std::vector<double> hist(k * cap);
+        std::vector<int64_t> len(k, 0);
+        check(call_many(b.handle(), x.handle(), a.handle(), pc ? pc->device_handle() : nullptr, &p, st.data(), code.data(), hist.data(), (int64_t)cap,
+                        len.data()));
+        stats.clear(); residual_histories.clear();
+        for (size_t j = 0; j < k; ++j) {
+            stats.push_back(SolveStats<double>{(size_t)st[j].iterations, st[j].final_residual, st[j].converged != 0});
+            const size_t m = (size_t)std::min<int64_t>(len[j], (int64_t)cap);
+            residual_histories.emplace_back(hist.begin() + (long)(j * cap), hist.begin() + (long)(j * cap + m));
+        }
+        return code;
+    }
 protected:
     SolverBase(double tol, size_t max_iters) : conv{tol, max_iters} {}
     virtual int32_t call(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS) = 0;
+    virtual int32_t call_many(kryst_mvec_t, kryst_mvec_t, kryst_csr_t, kryst_pc_t, const kryst_params_t*, kryst_stats_t*, int32_t*, double*, int64_t,
+                              int64_t*) { return KRYST_UNSUPPORTED; }       // CG and PCG override it
     int restart_ = 0, side_ = 1, hist_per_iter_ = 1;
 private:
     static void trampoline(int64_t it, double res, void* user) { static_cast<SolverBase*>(user)->monitor((size_t)it, res); }
@@ -389,6 +454,10 @@ struct CgSolver : SolverBase {                               // cg.rs:40-93
     CgSolver& with_monitor(std::function<void(size_t, double)> f) { monitor = std::move(f); return *this; }
 protected:
     int32_t call(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS) override { return kryst_cg_solve(b, x, n, KRYST_FWD); }
+    int32_t call_many(kryst_mvec_t b, kryst_mvec_t x, kryst_csr_t a, kryst_pc_t pc, const kryst_params_t* params, kryst_stats_t* stats, int32_t* status,
+                      double* hist, int64_t hist_cap, int64_t* hist_len) override {
+        return kryst_cg_solve_multi_dev(b, x, a, pc, params, stats, status, hist, hist_cap, hist_len);
+    }
 };
 struct PcgSolver : SolverBase {                              // pcg.rs:31-91
     PcgSolver(double tol, size_t max_iters) : SolverBase(tol, max_iters) {}
@@ -397,6 +466,10 @@ struct PcgSolver : SolverBase {                              // pcg.rs:31-91
     PcgSolver& with_monitor(std::function<void(size_t, double)> f) { monitor = std::move(f); return *this; }
 protected:
     int32_t call(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS) override { return kryst_pcg_solve(b, x, n, KRYST_FWD); }
+    int32_t call_many(kryst_mvec_t b, kryst_mvec_t x, kryst_csr_t a, kryst_pc_t pc, const kryst_params_t* params, kryst_stats_t* stats, int32_t* status,
+                      double* hist, int64_t hist_cap, int64_t* hist_len) override {
+        return kryst_pcg_solve_multi_dev(b, x, a, pc, params, stats, status, hist, hist_cap, hist_len);
+    }
 };
 struct GmresSolver : SolverBase {                            // gmres.rs:38-60
     size_t restart; Preconditioning preconditioning = Preconditioning::Left;

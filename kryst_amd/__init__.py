@@ -9,6 +9,7 @@ behaviour (paths relative to the kryst crate):
     Jacobi / Ilu0 / Ilup / Chebyshev  .setup(a) .apply(r, z)        src/preconditioner/*.rs
     apply_chebyshev(a, r, z, alpha, beta, m)                        src/preconditioner/chebyshev.rs:83-140
     CgSolver / PcgSolver / GmresSolver / BiCgStabSolver .solve(a, pc, b, x) -> SolveStats   src/solver/*.rs
+    MultiVec, CsrMatrix.spmm(X, Y), CgSolver / PcgSolver .solve_many(a, pc, B, X)           several right-hand sides at once (extension)
     DenseMatrix.from_raw(nrows, ncols, data) .matvec(x, y)          src/matrix/dense.rs:16-25, core/wrappers.rs:27-38
     LuSolver / QrSolver .solve(a, pc, b, x), LuSolver.solve_cached  src/solver/direct_lu.rs
     Convergence, SolveStats, KError, CgNormType, Preconditioning    src/utils/convergence.rs, src/error.rs
@@ -27,7 +28,8 @@ __all__ = ["Context", "DeviceVec", "CsrMatrix", "dot", "norm", "Jacobi", "Ilu0",
            "ChebyshevPc", "IdentityPc", "ApproxInv", "BlockJacobi", "AdditiveSchwarz", "Sor", "MatSorType", "SparsityPattern", "Spai", "Amg", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
            "Preconditioning", "CgSolver", "PcgSolver", "GmresSolver", "FgmresSolver", "PcaGmresSolver", "Orthog", "CgsSolver", "TfqmrSolver", "MinresSolver", "QmrSolver", "CgnrSolver", "CgneSolver", "BiCgStabSolver", "BiCgStabRightPcSolver", "Session", "KspContext", "SolverKind", "PC", "KError", "reduce_spec",
            "host_stencil7", "partition_rows", "halo_recv_plan", "read_matrix_market", "read_petsc_binary", "host_ilup", "host_ilut", "host_amg", "host_levels", "color_graph", "build_blocks_from_colors",
-           "DenseMatrix", "LuSolver", "QrSolver", "host_dense_lu", "host_dense_lu_solve", "host_dense_qr_solve"]
+           "DenseMatrix", "LuSolver", "QrSolver", "host_dense_lu", "host_dense_lu_solve", "host_dense_qr_solve",
+           "MultiVec", "split_widths"]
 
 
 def _dp(a):
@@ -197,6 +199,89 @@ class DeviceVec:
             pass
 
 
+MVEC_WIDTHS = (8, 4, 2)
+
+
+def split_widths(m):
+    """How m right-hand sides are cut into multivectors: greedily into groups of 8, 4 and 2 columns; a leftover single column goes through
+    the single-vector call (width 1).  15 -> [8, 4, 2, 1].  No padding columns are invented."""
+    m = int(m)
+    if m < 0:
+        raise ValueError("split_widths: m < 0")
+    out = []
+    for w in MVEC_WIDTHS:
+        while m >= w:
+            out.append(w)
+            m -= w
+    if m:
+        out.append(1)
+    return out
+
+
+class MultiVec:
+    """n x k device multivector, k in {2, 4, 8} (kryst_mvec_t): the k values of a row are contiguous in HBM."""
+
+    def __init__(self, ctx, n, k):
+        self.ctx, self.n, self.k = ctx, int(n), int(k)
+        self.h = _ffi.Handle()
+        check(lib().kryst_mvec_create(ctx.h, self.n, self.k, C.byref(self.h)))
+
+    @staticmethod
+    def from_numpy(a, ctx=None):
+        """a: array of shape (n, k) in either memory order."""
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim != 2:
+            raise KError(102, "MultiVec.from_numpy: a two-dimensional array is required")
+        mv = MultiVec(ctx or Context.default(), a.shape[0], a.shape[1])
+        return mv.upload(a)
+
+    @property
+    def shape(self):
+        return (self.n, self.k)
+
+    def upload(self, a):
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape != (self.n, self.k):
+            raise KError(102, "MultiVec.upload: shape mismatch")
+        cm = np.asfortranarray(a)                       # column j at cm.ravel('K')[j * n:], ld = n
+        check(lib().kryst_mvec_upload(self.h, _dp(cm), max(self.n, 1)))
+        return self
+
+    def to_numpy(self):
+        out = np.empty((self.n, self.k), order="F")
+        check(lib().kryst_mvec_download(self.h, _dp(out), max(self.n, 1)))
+        return out
+
+    def column(self, j):
+        v = DeviceVec(self.ctx, self.n)
+        check(lib().kryst_mvec_get_column(self.h, int(j), v.h))
+        return v
+
+    def set_column(self, j, v):
+        if not isinstance(v, DeviceVec):
+            v = DeviceVec(self.ctx, v)
+        check(lib().kryst_mvec_set_column(self.h, int(j), v.h))
+        return self
+
+    def poison_padding(self, value=None):
+        """Test hook (kryst_bench_mvec_padding): every allocated element of row index >= n becomes `value` (default: a quiet NaN)."""
+        fill = np.array([DeviceVec.QUIET_NAN_BITS], dtype=np.uint64).view(np.float64) if value is None else np.array([value], dtype=np.float64)
+        check(lib().kryst_bench_mvec_padding(self.h, _dp(fill), None))
+        return self
+
+    def padding_dirty(self):
+        dirty = C.c_int64(-1)
+        check(lib().kryst_bench_mvec_padding(self.h, None, C.byref(dirty)))
+        return dirty.value
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                lib().kryst_mvec_destroy(self.h)
+        except Exception:
+            pass
+
+
 def dot(x, y):
     """InnerProduct::dot (wrappers.rs:90-108) on device vectors."""
     out = C.c_double()
@@ -334,6 +419,29 @@ class CsrMatrix:
             raise KError(102, "spmv_transpose: y.len() != ncols")
         y[:] = yv.to_host()
         return y
+
+    def spmm(self, X, Y=None):
+        """Y <- A X for several columns at once: column j is spmv on column j, bit for bit.  X: MultiVec, or an array of shape (ncols, m)
+        with any m (cut by split_widths; a leftover single column takes spmv); returns a MultiVec or an (nrows, m) array."""
+        if isinstance(X, MultiVec):
+            if Y is None:
+                Y = MultiVec(self.ctx, self._nrows, X.k)
+            check(lib().kryst_spmm(self.h, X.h, Y.h))
+            return Y
+        xa = np.asarray(X, dtype=np.float64)
+        if xa.ndim != 2 or xa.shape[0] != self._ncols:
+            raise KError(102, "spmm: X must have shape (ncols, m)")
+        out = np.empty((self._nrows, xa.shape[1]), order="F") if Y is None else Y
+        if out.shape != (self._nrows, xa.shape[1]):
+            raise KError(102, "spmm: Y must have shape (nrows, m)")
+        at = 0
+        for w in split_widths(xa.shape[1]):
+            if w == 1:
+                out[:, at] = self.spmv(np.ascontiguousarray(xa[:, at]))
+            else:
+                out[:, at:at + w] = self.spmm(MultiVec.from_numpy(xa[:, at:at + w], ctx=self.ctx)).to_numpy()
+            at += w
+        return out
 
     ENCODINGS = ("csr", "csr-d8", "csr-d16", "csr-p16", "csr-dia")
 
@@ -1109,6 +1217,7 @@ class _Solver:
         self.obj_target = None
         self.monitor = None
         self.residual_history = []
+        self.residual_histories = []                 # solve_many: one history per column
         self.restart = 0
         self.preconditioning = Preconditioning.Left
         self.check_every = 0
@@ -1152,6 +1261,68 @@ class _Solver:
         check(rc, stats)
         return stats
 
+    _MULTI_DEV = None
+
+    def _solve_group(self, a, pch, bm, xm):
+        """one multivector of 2, 4 or 8 columns through the batched entry point -> per column (code, SolveStats, history)"""
+        k = bm.k
+        prm = self._params()
+        st = (_ffi.Stats * k)()
+        code = (C.c_int32 * k)()
+        cap = min(self.conv.max_iters + 8, (1 << 19) + 8)          # the library records at most 2^19 entries per column
+        hist = np.zeros((k, cap))
+        hlen = (C.c_int64 * k)()
+        check(getattr(lib(), self._MULTI_DEV)(bm.h, xm.h, a.h, pch, C.byref(prm), st, code, _dp(hist), cap, hlen))
+        return [(code[j], SolveStats(st[j].iterations, st[j].final_residual, bool(st[j].converged)), hist[j, :min(hlen[j], cap)].tolist())
+                for j in range(k)]
+
+    def solve_many(self, a, pc, B, X):
+        """solve(a, pc, B[:, j], X[:, j]) for every column j, the matrix read once per group of columns: bit for bit the results of the
+        single calls.  B, X: MultiVec (2, 4 or 8 columns, X in/out on the device) or arrays of shape (n, m) with any m -- the columns are
+        cut by split_widths into groups of 8, 4 and 2, a leftover single column goes through solve(); X must then be a float64 array and
+        is written in place, column by column, where the column's solve succeeded.  Returns a list with a SolveStats or, for a column
+        that ended in an error, the KError (carrying .stats) in its place; self.residual_histories holds one history per column."""
+        if self._MULTI_DEV is None:
+            raise KError(6, "solve_many: CG and PCG only")
+        pch = pc.h if pc is not None else None
+        if pc is not None and pch is None:
+            raise KError(2, "preconditioner used before setup")
+        if isinstance(B, MultiVec) or isinstance(X, MultiVec):
+            if not (isinstance(B, MultiVec) and isinstance(X, MultiVec)):
+                raise KError(102, "solve_many: B and X must both be MultiVec or both be arrays")
+            res = self._solve_group(a, pch, B, X)
+        else:
+            ba = np.asarray(B, dtype=np.float64)
+            if ba.ndim != 2 or not isinstance(X, np.ndarray) or X.dtype != np.float64 or X.shape != ba.shape:
+                raise KError(102, "solve_many: B and X must be float64 arrays of the same shape (n, m)")
+            res, at = [], 0
+            for w in split_widths(ba.shape[1]):
+                if w == 1:
+                    saved, self.residual_history = self.residual_history, []
+                    xj = np.ascontiguousarray(X[:, at])
+                    try:
+                        stats = self.solve(a, pc, np.ascontiguousarray(ba[:, at]), xj)
+                        res.append((0, stats, self.residual_history))
+                        X[:, at] = xj
+                    except KError as e:
+                        if e.stats is None:
+                            raise
+                        res.append((e.code, e.stats, self.residual_history))
+                    finally:
+                        self.residual_history = saved
+                else:
+                    bm = MultiVec.from_numpy(ba[:, at:at + w], ctx=a.ctx)
+                    xm = MultiVec.from_numpy(X[:, at:at + w], ctx=a.ctx)
+                    group = self._solve_group(a, pch, bm, xm)
+                    xs = xm.to_numpy()
+                    for j, (code, _, _) in enumerate(group):
+                        if code == 0:
+                            X[:, at + j] = xs[:, j]
+                    res.extend(group)
+                at += w
+        self.residual_histories = [h for _, _, h in res]
+        return [stats if code == 0 else KError(code, "", stats) for code, stats, _ in res]
+
     def _extra(self):
         return ()
 
@@ -1183,11 +1354,13 @@ class _Solver:
 class CgSolver(_Solver):
     """CgSolver::new(tol, max_iters)  src/solver/cg.rs:40-93,114-288 (pc is ignored, cg.rs:115)."""
     _HOST, _DEV = "kryst_cg_solve", "kryst_cg_solve_dev"
+    _MULTI_DEV = "kryst_cg_solve_multi_dev"
 
 
 class PcgSolver(_Solver):
     """PcgSolver::new(tol, max_iters)  src/solver/pcg.rs:31-91,114-222."""
     _HOST, _DEV = "kryst_pcg_solve", "kryst_pcg_solve_dev"
+    _MULTI_DEV = "kryst_pcg_solve_multi_dev"
 
 
 class GmresSolver(_Solver):

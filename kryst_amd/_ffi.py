@@ -32,6 +32,8 @@ class Stats(C.Structure):
 
 
 _SOLVE_TAIL = [Handle, Handle, C.POINTER(Params), C.POINTER(Stats), c_dp, C.c_int64, c_i64p, MONITOR, C.c_void_p]
+# the batched solves: operator, pc, params, stats[k], status[k], hist (k slices of hist_cap), hist_cap, hist_len[k]
+_MULTI_TAIL = [Handle, Handle, C.POINTER(Params), C.POINTER(Stats), c_i32p, c_dp, C.c_int64, c_i64p]
 
 # name -> (restype, argtypes): every symbol include/kryst_hip.h declares
 SIGNATURES = {
@@ -185,6 +187,19 @@ SIGNATURES = {
     "kryst_host_factors_destroy": (C.c_int32, [Handle]),
     "kryst_host_levels": (C.c_int32, [C.c_int64, c_i64p, c_i32p, C.c_int32, c_i32p, c_i32p]),
     "kryst_host_color_graph": (C.c_int32, [C.c_int64, c_i64p, c_i32p, c_i32p, c_i32p]),
+    "kryst_mvec_create": (C.c_int32, [Handle, C.c_int64, C.c_int32, C.POINTER(Handle)]),
+    "kryst_mvec_destroy": (C.c_int32, [Handle]),
+    "kryst_mvec_shape": (C.c_int32, [Handle, c_i64p, c_i32p]),
+    "kryst_mvec_upload": (C.c_int32, [Handle, c_dp, C.c_int64]),
+    "kryst_mvec_download": (C.c_int32, [Handle, c_dp, C.c_int64]),
+    "kryst_mvec_set_column": (C.c_int32, [Handle, C.c_int32, Handle]),
+    "kryst_mvec_get_column": (C.c_int32, [Handle, C.c_int32, Handle]),
+    "kryst_bench_mvec_padding": (C.c_int32, [Handle, c_dp, c_i64p]),
+    "kryst_spmm": (C.c_int32, [Handle, Handle, Handle]),
+    "kryst_cg_solve_multi_dev": (C.c_int32, [Handle, Handle] + _MULTI_TAIL),
+    "kryst_pcg_solve_multi_dev": (C.c_int32, [Handle, Handle] + _MULTI_TAIL),
+    "kryst_cg_solve_multi": (C.c_int32, [c_dp, c_dp, C.c_int64, C.c_int32, C.c_int64] + _MULTI_TAIL),
+    "kryst_pcg_solve_multi": (C.c_int32, [c_dp, c_dp, C.c_int64, C.c_int32, C.c_int64] + _MULTI_TAIL),
 }
 
 _lib = None
