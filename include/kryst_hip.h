@@ -164,7 +164,8 @@ int32_t kryst_csr_pattern_info(kryst_csr_t a, int64_t* info);
  * plane and walks a segment of S planes, the operands one plane away come out of its own LDS windows; results are the same bits).  With the
  * KRYST_SPMV_FUSE_* settings as they are now: info[0] 1 if the operator's shape allows it (far offsets of +- one plane, a plane that is a
  * whole number of strips, a box that is a whole number of planes, lines of at most 512 points), info[1] 1 if a fused launch takes it now,
- * info[2] T, info[3] strips per plane, info[4] S, info[5] segments (info[3 .. 5] 0 when not eligible) */
+ * info[2] T, info[3] strips per plane, info[4] S, info[5] segments (info[3 .. 5] 0 when not eligible), info[6] 1 if a fused CG iteration would
+ * now store no A p and form it again in its residual pass (KRYST_CG_RECOMPUTE_AP; the marching mode on, x updated in batches).  info: 7 values */
 int32_t kryst_csr_fuse_march_info(kryst_csr_t a, int64_t* info);
 int32_t kryst_csr_download(kryst_csr_t a, int64_t* row_ptr, int32_t* col_idx_local, double* vals);
 /* Measurement hook (ABI 5): where the CSR arrays live.  The same plain-CSR stream mix runs at 0.70 .. 0.76 of the HBM peak depending on where

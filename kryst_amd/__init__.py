@@ -465,10 +465,12 @@ class CsrMatrix:
 
     def fuse_march_info(self):
         """Measurement hook (kryst_csr_fuse_march_info): the marching mode of the fused direction + SpMV kernel under the current
-        KRYST_SPMV_FUSE_* settings -- {"eligible", "on", "T", "strips", "S", "segments"}."""
-        info = (C.c_int64 * 6)()
+        KRYST_SPMV_FUSE_* settings -- {"eligible", "on", "T", "strips", "S", "segments"} -- and "recompute_ap": whether a fused CG iteration would
+        now store no Ap and form it again in its residual pass (KRYST_CG_RECOMPUTE_AP, x in batches)."""
+        info = (C.c_int64 * 7)()
         check(lib().kryst_csr_fuse_march_info(self.h, info))
-        return {"eligible": bool(info[0]), "on": bool(info[1]), "T": info[2], "strips": info[3], "S": info[4], "segments": info[5]}
+        return {"eligible": bool(info[0]), "on": bool(info[1]), "T": info[2], "strips": info[3], "S": info[4], "segments": info[5],
+                "recompute_ap": bool(info[6])}
 
     def placement_info(self):
         """Where the CSR arrays live (kryst_csr_placement_info): {"tries", "chosen", "skeleton_ms": [...]} of the homes tried at creation."""

@@ -74,6 +74,11 @@ int32_t launch_spmv(kryst_csr_t a, const double* x, double* y, int nq, const dou
 bool spmv_can_fuse_direction(kryst_csr_t a);
 int32_t launch_spmv_fused(kryst_csr_t a, const double* z, const double* p_old, double* p_new, double* xvec, double* y, int nq,
                           const double* alpha, const double* beta, const long long* xpend, long long it, const int* done);
+// CG without a stored A p (spmv.hip: cg_recompute_residual_kernel): whether the fused launch of an iteration may drop its y store (launch_spmv_fused
+// with y == nullptr: the marching kernel, nq == 1, no xvec) -- read ONCE per iteration and handed to both launches -- and the residual pass that goes
+// with it: r -= alpha A p with the tile partials of (r, r), A p formed again from p.  keep: r is stored temporal (keep_in_cache)
+bool spmv_can_recompute_ap(kryst_csr_t a);
+int32_t launch_cg_residual_recompute(kryst_csr_t a, const double* p, double* r, const double* alpha, bool keep, const int* done);
 // Distributed operators: start the halo exchange of x NOW (everything enqueued on the compute stream so far is waited for, nothing
 // later) and remember it, so that the next launch_spmv(a, x, ...) does not start it again.  A solver calls it after the launch that
 // wrote the rows the neighbours need and before the launches that write the rest (send_contiguous operators only).

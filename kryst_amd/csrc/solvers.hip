@@ -360,10 +360,13 @@ struct CgRun : SolverRun {
     int32_t iterate(int64_t it) override {
         if (fuse) {
             // iteration it: [x += alpha p_old owed by iteration it - 1 (xb == 1); p = r + beta p_old; Ap; (p, Ap)] in ONE pass, alpha, the residual pass, beta
+            // recompute: the fused launch stores no Ap and the residual pass forms it again from p_new (spmv.hip: cg_recompute_residual_kernel) -- decided
+            // ONCE per iteration, here, for both launches (KRYST_CG_RECOMPUTE_AP may change between session steps); every other iteration keeps ap
+            const bool recompute = fused_upto == it - 1 && it > 1 && xb > 1 && spmv_can_recompute_ap(a);
             if (fused_upto == it - 1 && it > 1) {
                 if (xb > 1) {
                     double* p_old = ring[(size_t)((it - 1) % (xb + 1))]; double* p_new = ring[(size_t)(it % (xb + 1))];
-                    KR_TRY(launch_spmv_fused(a, r, p_old, p_new, nullptr, ap, 1, &ws.st->alpha, &ws.st->beta, &ws.st->xpend, (long long)it, done));
+                    KR_TRY(launch_spmv_fused(a, r, p_old, p_new, nullptr, recompute ? nullptr : ap, 1, &ws.st->alpha, &ws.st->beta, &ws.st->xpend, (long long)it, done));
                     pp = p_new;
                 } else {
                     KR_TRY(launch_spmv_fused(a, r, pp, p2, xw, ap, 1, &ws.st->alpha, &ws.st->beta, &ws.st->xpend, (long long)it, done));
@@ -373,7 +376,8 @@ struct CgRun : SolverRun {
                 KR_TRY(launch_spmv(a, pp, ap, 1, pp, done));                                      // the first iteration: p = r already
             }
             KR_TRY((reduce_then<1>(ctx, nt, ws.red, CgAlphaLogic{lc})));
-            if (keep_in_cache(n)) KR_TRY(launch_ew(ctx, CgResidualOp<true>{&ws.st->alpha, ap, r}, n, done));
+            if (recompute) KR_TRY(launch_cg_residual_recompute(a, pp, r, &ws.st->alpha, keep_in_cache(n), done));
+            else if (keep_in_cache(n)) KR_TRY(launch_ew(ctx, CgResidualOp<true>{&ws.st->alpha, ap, r}, n, done));
             else KR_TRY(launch_ew(ctx, CgResidualOp<false>{&ws.st->alpha, ap, r}, n, done));
             KR_TRY((reduce_then<1>(ctx, nt, ws.red, CgBetaLogic{lc})));
             fused_upto = it;

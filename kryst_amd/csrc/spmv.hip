@@ -775,6 +775,8 @@ __global__ __launch_bounds__(KR_T) void spmv_pattern_stage_kernel(const SpmvArgs
 // far_lo / far_hi away) are formed the same way from z and p_old there: a row's p_new is computed by up to three workgroups, from the same
 // operands in the same order.  p_old and p_new are DIFFERENT arrays (the solver ping-pongs): nobody reads what another workgroup writes.
 // Per row: z, p_old, x read, p_new, x, y written + the pattern id -- 50 bytes instead of 40 (direction) + 18 (SpMV), and one launch fewer.
+// (With x in batches, XU = false: z, p_old read, p_new, y written + the id -- 34; and the marching instance with YS = false, which CG takes when its
+// residual pass forms A p again (cg_recompute_residual_kernel below), writes p_new alone -- 26.)
 //   xpend == it - 1: the x update of the previous iteration is owed (always, unless the solve ended earlier and it has been paid);
 //   done: the solve has ended -- only the owed x update happens, nothing else is touched.
 struct FuseArgs { const double* z; const double* p_old; double* p_new; double* xvec; const double* alpha; const double* beta; const long long* xpend; long long it; };
@@ -793,7 +795,7 @@ struct FuseArgs { const double* z; const double* p_old; double* p_new; double* x
 //     a. request W(s + 2): z, p_old (and the owed x) of the whole window into REGISTERS, and the ids of plane s + 1 -- in flight under b.  (Not by
 //        LDS-DMA as the un-marched fill: beside a pending DMA the compiler drains vmcnt(0) before the first LDS read of b. and before every use of
 //        an ordinary load, which serialises the step; plain loads are counted exactly.  Both forms read at the same rate.)
-//     b. the tiles of plane s out of W(s) and W(s + 1), partials per wave into red;
+//     b. the tiles of plane s out of W(s) and W(s + 1), y stored (YS; not when the residual pass recomputes it), partials per wave into red;
 //     barrier 1: every wave has read W(s) for the last time;
 //     c. the cross-wave step of the partials (threads 0 .. T NQ - 1 out of red); p_new = z + beta p_old into the buffer that held W(s), own
 //        rows to p_new in memory, with the owed x update;
@@ -810,7 +812,7 @@ struct FuseArgs { const double* z; const double* p_old; double* p_new; double* x
 //   SIMD, one more than the two workgroups per CU the launch keeps resident need.  Measured at 512^3 (profiles/march/): HBM traffic 39.9 -> 35.4 bytes
 //   per row (model 34), the kernel 879 -> 843 us, CG 601 -> 628 it/s.
 //   a.group: strips per XCD; a.xcd_chunk: S; a.tpw: strips per plane; far_hi == -far_lo == the plane; every strip and every plane is whole.
-template <int NQ, int T, int NMAX, bool XU>
+template <int NQ, int T, int NMAX, bool XU, bool YS>
 __device__ __forceinline__ void fuse_march(const SpmvArgs& a, const FuseArgs& f, const int32_t n, const int32_t plane, unsigned char* smem, const bool ended, const bool owed) {
     const int XS = T * KR_TILE + 2 * n + 4;                                  // elements of one window (even)
     double* win = reinterpret_cast<double*>(smem);
@@ -931,7 +933,7 @@ __device__ __forceinline__ void fuse_march(const SpmvArgs& a, const FuseArgs& f,
                 s0 = ((ka >> u) & 1u) ? ta : s0;
                 s1 = ((kb >> u) & 1u) ? tb : s1;
             }
-            st2(a.y, row, s0, s1);
+            if constexpr (YS) st2(a.y, row, s0, s1);                         // (!YS: the residual pass forms A p again, cg_recompute_residual_kernel)
             double acc[NQ];
             acc[0] = 0.0;
             acc[0] = acc[0] + B.x * s0;
@@ -964,13 +966,14 @@ __device__ __forceinline__ void fuse_march(const SpmvArgs& a, const FuseArgs& f,
     }
 }
 
-template <int NQ, int T, int NMAX, bool XU, bool MARCH = false>
+// YS (marching instances only): y is stored; false when the residual pass recomputes A p from p_new (launch_spmv_fused with y == nullptr)
+template <int NQ, int T, int NMAX, bool XU, bool MARCH = false, bool YS = true>
 __global__ __launch_bounds__(KR_T) void spmv_pattern_fuse_kernel(const SpmvArgs a, const FuseArgs f, const int32_t n, const int32_t far_lo, const int32_t far_hi) {
     const bool ended = a.done && *a.done;
     const bool owed = XU && *f.xpend == f.it - 1;
     if (ended && !owed) return;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    if constexpr (MARCH) { fuse_march<NQ, T, NMAX, XU>(a, f, n, far_hi, smem, ended, owed); return; }
+    if constexpr (MARCH) { fuse_march<NQ, T, NMAX, XU, YS>(a, f, n, far_hi, smem, ended, owed); return; }
     const int XS = T * KR_TILE + 2 * n + 4;                                  // staged elements (even)
     double* xs = reinterpret_cast<double*>(smem);                            // p_old's window, overwritten in place by p_new's
     uint2* meta = reinterpret_cast<uint2*>(xs + XS);
@@ -1120,6 +1123,163 @@ __global__ __launch_bounds__(KR_T) void spmv_pattern_fuse_kernel(const SpmvArgs 
             for (int w2 = 1; w2 < KR_T / 64; ++w2) sum = sum + red[t * (KR_T / 64) + w2];
             a.partials[kk * a.pstride + q0 + k] = sum;
         }
+    }
+}
+
+// CG's residual pass WITHOUT a stored A p (KRYST_CG_RECOMPUTE_AP; solvers.hip: CgRun::iterate).  The marching fused kernel above writes A p only to
+// carry it across the point where alpha is folded: 8 bytes per row written and 8 read back by CgResidualOp.  This kernel forms A p AGAIN from the
+// direction vector that kernel has just stored -- the very doubles it had in its windows, the same e[0 .. 6], table values, absent-entry selects and
+// un-fused multiply and add from 0.0, so the same bits -- and goes on as CgResidualOp does: r -= alpha Ap (cg.rs:210-212), the tile partial of (r, r)
+// (:223) in ew_kernel's order (thread: 0 + r0 r0 + r1 r1; wave butterfly; the four waves in turn; partials[tile]).  Per row: p (own rows once, the
+// window's halo (2 n + 4) / R and 2 / S far lines besides), r and the pattern id read, r written: 26 + halo instead of 24, and the fused kernel
+// writes 8 bytes per row less (p_new and nothing else).
+//   Mapping: fuse_march's -- the same T, S, strips per XCD and grid (fuse_march_plan), so a strip is on the same XCD in both kernels of an iteration and
+//   the halo lines are a neighbouring strip's own lines in that L2.  The window holds plain p: no z / p_old staging, e[0] is the lane's own B pair of
+//   the plane below carried in registers, e[6] comes out of the next plane's window, and only a segment's first and last plane load a far pair of p
+//   from memory (clamped at the ends of the box: only absent entries point there).
+//   LDS: THREE windows of R + 2 n + 4 doubles, W(s), W(s + 1) and the one being filled, and two copies of red.  A step is
+//     a. request W(s + 2) of p into registers, and r's own rows and the ids of plane s + 1 (nontemporal: read once) -- in flight under b.  (Plain loads,
+//        not LDS-DMA, for fuse_march's reason: r and the ids are in flight beside the window, and beside a pending DMA the compiler drains vmcnt(0)
+//        before every use of an ordinary load.)
+//     b. the tiles of plane s out of W(s) and W(s + 1): A p, r of plane s (requested one step ago) updated and stored, partials per wave into red[s & 1];
+//     c. W(s + 2) from the registers into the third buffer;
+//     barrier: W(s + 2) and red[s & 1] are complete;
+//     d. the cross-wave step of the partials (threads 0 .. T - 1 out of red[s & 1]); the buffers change roles.
+//   ONE barrier per step is enough: c. of step s overwrites the buffer that held W(s - 1), whose last reads (b. of step s - 1) are before the barrier of
+//   step s - 1; W(s) and W(s + 1) are only read in step s; b. of step s + 1 reads W(s + 2) after the barrier of step s; red[s & 1] is read in d. of step s
+//   and written again in b. of step s + 2, which its writers reach only through the barrier of step s + 1, behind d. of step s in every wave.  The
+//   barrier is executed in every step by every wave (the branches around the fills depend on s and the segment's length alone).
+//   Resources (gfx950, T = 4, n = 512): 165 VGPRs, no scratch (the compiler keeps a tile's LDS reads and the window in flight side by side: three waves
+//   per SIMD would fit, two are resident); LDS 3 x 24 608 B of windows + 8 B per pattern and table entry + 256 B of red, padded to 81 408 B (half a CU's LDS less 512).  Measured at
+//   512^3 (profiles/recompute/): the fused kernel 810 -> 632 us (35.3 -> 27.2 bytes per row), the residual pass 507 -> 620 us (24.1 -> 26.5), CG 628 ->
+//   674 it/s.
+//   a.group: strips per XCD; a.xcd_chunk: S; a.tpw: strips per plane; every strip and every plane is whole, so every row of a strip is a row of the box.
+// KEEP: r is stored temporal (keep_in_cache: the next launch reads it again out of the Infinity Cache), as CgResidualOp<KEEP> does.
+template <int T, bool KEEP>
+__global__ __launch_bounds__(KR_T) void cg_recompute_residual_kernel(const SpmvArgs a, const double* p, double* r, const double* alpha, const int32_t n, const int32_t plane) {
+    if (a.done && *a.done) return;                                           // (GateDone: alpha's logic may have ended the solve)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int XS = T * KR_TILE + 2 * n + 4;                                  // elements of one window (even)
+    double* win = reinterpret_cast<double*>(smem);
+    uint2* meta = reinterpret_cast<uint2*>(win + 3 * XS);
+    double* pval = reinterpret_cast<double*>(meta + a.npat);
+    double* red = reinterpret_cast<double*>(smem + a.pat_red_off);           // 2 x T x (KR_T / 64)
+    const int t = threadIdx.x;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int spx = a.group, S = a.xcd_chunk;
+    const int strip = xcd * spx + slot % spx, k0 = (slot / spx) * S;
+    const int nplanes = a.nrows / plane;
+    if (strip >= a.tpw || k0 >= nplanes) return;                             // (uniform over the workgroup)
+    const int ns = min(S, nplanes - k0);                                     // planes of this segment (the last one may be shorter)
+    const int32_t rbeg = k0 * plane + strip * (T * KR_TILE);                 // first row of the strip in the segment's first plane
+    const double al = *alpha;
+    constexpr int NP = (T * KR_TILE + 2 * 512 + 4 + 2 * KR_T - 1) / (2 * KR_T);     // pairs per lane at most (n <= 512)
+    const int npairs = XS / 2;
+    const int32_t xsafe = (int32_t)a.xsafe;
+    v2d wp[NP];
+    // a window's requests (r0: the strip's first row in that plane).  Every lane loads NP pairs: pairs past the window's end are clamped into it (and
+    // dropped by write_window) -- no branch around a load
+    auto request = [&](const int32_t r0) {
+        const int32_t e0 = r0 - n - 2;                                       // element at the window's [0] (even)
+        const bool inside = e0 >= 0 && e0 + XS <= xsafe;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int pi = min(t + i * KR_T, npairs - 1);
+            const int32_t e = inside ? e0 + 2 * pi : min(max(e0 + 2 * pi, 0), xsafe);     // outside p: any valid pair (those operands are absent entries)
+            wp[i] = *reinterpret_cast<const v2d*>(p + e);
+        }
+    };
+    auto write_window = [&](double* xs) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int pi = t + i * KR_T;
+            if (pi < npairs) *reinterpret_cast<v2d*>(xs + 2 * pi) = wp[i];
+        }
+    };
+    // a far operand the segment does not hold (below its first plane, above its last)
+    auto far_pair = [&](const int64_t row) {
+        return *reinterpret_cast<const v2d*>(p + min(max(row, (int64_t)0), (int64_t)xsafe));
+    };
+    unsigned ids[T], idn[T];
+    d2 rr[T], rn[T];
+    v2d prev[T], hi[T];
+    // ---- the segment's first two windows, r and the ids of its first plane
+#pragma unroll
+    for (int k = 0; k < T; ++k) {
+        ids[k] = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(a.pid + (size_t)rbeg + k * KR_TILE + 2 * t)); idn[k] = 0u;
+        rr[k] = ld2(r, (int64_t)rbeg + k * KR_TILE + 2 * t); rn[k] = rr[k];
+    }
+    double* w0 = win; double* w1 = win + XS; double* w2 = win + 2 * XS;    // W(s), W(s + 1), the one being filled
+    request(rbeg);
+#pragma unroll
+    for (int k = 0; k < T; ++k) { prev[k] = far_pair((int64_t)rbeg + k * KR_TILE + 2 * t - plane); hi[k].x = 0.0; hi[k].y = 0.0; }
+    for (int i = t; i < a.npat; i += KR_T) meta[i] = reinterpret_cast<const uint2*>(a.pmeta)[i];
+    for (int i = t; i < a.ntab; i += KR_T) pval[i] = a.pval[i];
+    write_window(w0);
+    if (ns > 1) {
+        request(rbeg + plane);
+        write_window(w1);
+    }
+    __syncthreads();
+    for (int s = 0; s < ns; ++s) {
+        const int32_t r0 = rbeg + s * plane;
+        const bool last = s + 1 == ns, fill = s + 2 < ns;                   // (uniform)
+        double* redb = red + (s & 1) * (T * (KR_T / 64));
+        // a.
+        if (fill) request(r0 + 2 * plane);
+        if (!last) {
+#pragma unroll
+            for (int k = 0; k < T; ++k) {
+                idn[k] = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(a.pid + (size_t)(r0 + plane) + k * KR_TILE + 2 * t));
+                rn[k] = ld2(r, (int64_t)(r0 + plane) + k * KR_TILE + 2 * t);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < T; ++k) hi[k] = far_pair((int64_t)r0 + k * KR_TILE + 2 * t + plane);
+        }
+        // b. tile after tile out of LDS (fuse_march's arithmetic, operand for operand), then CgResidualOp's
+#pragma unroll
+        for (int k = 0; k < T; ++k) {
+            const int32_t row = r0 + k * KR_TILE + 2 * t;
+            const uint2 ma = meta[ids[k] & 0xffffu], mb = meta[ids[k] >> 16];
+            const int j = k * KR_TILE + 2 * t + n + 2;                       // w0[j] = p[row], w1[j] = p[row + plane]
+            const v2d A = *reinterpret_cast<const v2d*>(w0 + j - 2), B = *reinterpret_cast<const v2d*>(w0 + j), C = *reinterpret_cast<const v2d*>(w0 + j + 2);
+            const v2d M = *reinterpret_cast<const v2d*>(w0 + j - n), P = *reinterpret_cast<const v2d*>(w0 + j + n);
+            const v2d U = *reinterpret_cast<const v2d*>(w1 + j);             // (the segment's last plane: not used)
+            v2d e[7];
+            e[0] = prev[k]; e[1] = M; e[2].x = A.y; e[2].y = B.x; e[3] = B; e[4].x = B.y; e[4].y = C.x; e[5] = P;
+            e[6].x = last ? hi[k].x : U.x; e[6].y = last ? hi[k].y : U.y;
+            prev[k] = B;
+            const double* tva = pval + (ma.x & 0xffffu); const double* tvb = pval + (mb.x & 0xffffu);
+            const unsigned ka = ma.y, kb = mb.y;
+            double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+            for (int u = 0; u < 7; ++u) {
+                const double ta = s0 + tva[u] * e[u].x, tb = s1 + tvb[u] * e[u].y;
+                s0 = ((ka >> u) & 1u) ? ta : s0;
+                s1 = ((kb >> u) & 1u) ? tb : s1;
+            }
+            const double q0 = rr[k].a - al * s0, q1 = rr[k].b - al * s1;    // cg.rs:210-212
+            st2_sel<KEEP>(r, row, q0, q1);
+            double acc = 0.0;
+            acc = acc + q0 * q0;
+            acc = acc + q1 * q1;
+            const double wsum = wave_butterfly(acc);
+            if ((t & 63) == 0) redb[k * (KR_T / 64) + (t >> 6)] = wsum;
+        }
+        // c.
+        if (fill) write_window(w2);
+        __syncthreads();
+        // d.
+        if (t < T) {                                                         // thread k: tile r0 / 512 + k
+            double sum = redb[t * (KR_T / 64)];
+#pragma unroll
+            for (int w = 1; w < KR_T / 64; ++w) sum = sum + redb[t * (KR_T / 64) + w];
+            a.partials[r0 / KR_TILE + t] = sum;
+        }
+#pragma unroll
+        for (int k = 0; k < T; ++k) { ids[k] = idn[k]; rr[k] = rn[k]; }
+        double* w = w0; w0 = w1; w1 = w2; w2 = w;
     }
 }
 
@@ -1767,6 +1927,60 @@ static FuseMarchPlan fuse_march_plan(kryst_csr_t a, int nq) {
     m.on = env_int("KRYST_SPMV_FUSE_MARCH", a->nrows * 8 > env_ll("KRYST_CG_FUSE_MIN_BYTES", 768ll << 20) ? 1 : 0) != 0;
     return m;
 }
+// CG without a stored A p (cg_recompute_residual_kernel): the marching fused kernel stores p_new only and the residual pass forms A p again.  Taken
+// where the marching plan is eligible and on, three windows + tables + two copies of red leave room for two workgroups per CU, CG updates x in
+// batches (KRYST_CG_X_BATCH > 1: the fused kernel's instance without the x update) and KRYST_CG_RECOMPUTE_AP (0 / 1, read per iteration) allows it.
+// The knob's default follows KRYST_SPMV_FUSE_MARCH's size rule (vectors beyond KRYST_CG_FUSE_MIN_BYTES: 512^3).  Measured (profiles/recompute/): the
+// benchmark's command alternating with the parent commit 637 / 624 / 624 -> 677 / 672 / 672 it/s (+7.2 %); in-process A/B with the fused form forced
+// (tools/cg_recompute_ab.py): 512^3 +6.2 %, 384^3 +4.0 %, 256^3 +2.0 %, 448^3 -6.0 %.
+struct RecomputePlan { bool on; FuseMarchPlan m; size_t red_off, lds; };
+static RecomputePlan recompute_plan(kryst_csr_t a) {
+    RecomputePlan q;
+    memset(&q, 0, sizeof q);
+    q.m = fuse_march_plan(a, 2);
+    if (!(q.m.eligible && q.m.on)) return q;
+    const size_t tab = 3 * sizeof(double) * (size_t)((int64_t)q.m.T * KR_TILE + 2 * a->pat_stage_n + 4) + (size_t)a->npat * 8 + (size_t)a->ntab * 8;
+    q.red_off = (tab + 15) & ~(size_t)15;
+    q.lds = q.red_off + sizeof(double) * 2 * (size_t)q.m.T * (KR_T / 64);
+    if (q.lds > ((size_t)(160 << 10) / 2 - 512)) return q;
+    // (8: CG's default batch length in the fused form, solvers.hip: cg_x_batch; the solver also checks the length it really took)
+    q.on = env_int("KRYST_CG_X_BATCH", 8) > 1 && env_int("KRYST_CG_RECOMPUTE_AP", a->nrows * 8 > env_ll("KRYST_CG_FUSE_MIN_BYTES", 768ll << 20) ? 1 : 0) != 0;
+    return q;
+}
+bool spmv_can_recompute_ap(kryst_csr_t a) { return spmv_can_fuse_direction(a) && recompute_plan(a).on; }
+// r -= alpha A p with the tile partials of (r, r), A p formed from p on the way (the launch after launch_spmv_fused(.., y = nullptr, ..) and alpha's fold)
+int32_t launch_cg_residual_recompute(kryst_csr_t a, const double* p, double* r, const double* alpha, bool keep, const int* done) {
+    kryst_ctx_t ctx = a->ctx;
+    const RecomputePlan q = recompute_plan(a);
+    KR_ARG(q.on, "launch_cg_residual_recompute: the operator's marching plan cannot take it");
+    KR_TRY(ensure_partials(ctx, a->ntiles));
+    SpmvArgs args;
+    memset(&args, 0, sizeof args);
+    args.x = p; args.ntiles = (int32_t)a->ntiles; args.nrows = (int32_t)a->nrows; args.nloc = (int32_t)a->nrows;
+    args.partials = ctx->d_partials; args.pstride = ctx->partials_cap; args.done = done;
+    args.pid = a->d_pid; args.pmeta = a->d_pmeta; args.poff = a->d_poff; args.pval = a->d_pval; args.npat = a->npat; args.ntab = a->ntab;
+    args.xsafe = (a->xlen + KR_TILE - 1) / KR_TILE * KR_TILE + KR_TILE - 2;
+    const int spx = (q.m.strips + 7) / 8;
+    args.group = spx; args.xcd_chunk = q.m.S; args.tpw = q.m.strips; args.pat_red_off = (int32_t)q.red_off;
+    // two resident workgroups per CU, like the fused kernel: the dynamic LDS request is padded so that no third one fits (T = 2)
+    const size_t lds = std::max(q.lds, (size_t)(160 << 10) / 2 - 512);
+    static bool raised = false;
+    if (!raised) {
+        for (const void* fn : {(const void*)cg_recompute_residual_kernel<2, false>, (const void*)cg_recompute_residual_kernel<2, true>,
+                               (const void*)cg_recompute_residual_kernel<4, false>, (const void*)cg_recompute_residual_kernel<4, true>})
+            (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 80 << 10);
+        raised = true;
+    }
+    const dim3 grid((unsigned)(8 * spx * q.m.segs)), block(KR_T);
+    const int32_t n_ = a->pat_stage_n, plane = a->pat_far_hi;
+#define KR_RECOMPUTE(T_) do { if (keep) hipLaunchKernelGGL((cg_recompute_residual_kernel<T_, true>), grid, block, lds, ctx->s_main, args, p, r, alpha, n_, plane); \
+                              else hipLaunchKernelGGL((cg_recompute_residual_kernel<T_, false>), grid, block, lds, ctx->s_main, args, p, r, alpha, n_, plane); } while (0)
+    if (q.m.T == 2) KR_RECOMPUTE(2); else KR_RECOMPUTE(4);
+#undef KR_RECOMPUTE
+    KR_HIP(hipGetLastError());
+    phase_mark(ctx, KR_PH_BLAS1_RESIDUAL);
+    return KRYST_OK;
+}
 
 static int32_t launch_spmv_fused_impl(kryst_csr_t a, const double* z, const double* p_old, double* p_new, double* xvec, double* y, int nq,
                                       const double* alpha, const double* beta, const long long* xpend, long long it, const int* done, bool force) {
@@ -1813,12 +2027,21 @@ static int32_t launch_spmv_fused_impl(kryst_csr_t a, const double* z, const doub
         static bool raised_m = false;
         if (!raised_m) {
 #define KR_MARCH_FNS(NQ_, T_) (const void*)spmv_pattern_fuse_kernel<NQ_, T_, 512, true, true>, (const void*)spmv_pattern_fuse_kernel<NQ_, T_, 512, false, true>
-            for (const void* fn : {KR_MARCH_FNS(1, 2), KR_MARCH_FNS(1, 4), KR_MARCH_FNS(2, 2), KR_MARCH_FNS(2, 4)})
+            for (const void* fn : {KR_MARCH_FNS(1, 2), KR_MARCH_FNS(1, 4), KR_MARCH_FNS(2, 2), KR_MARCH_FNS(2, 4),
+                                   (const void*)spmv_pattern_fuse_kernel<1, 2, 512, false, true, false>, (const void*)spmv_pattern_fuse_kernel<1, 4, 512, false, true, false>})
                 (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 80 << 10);
 #undef KR_MARCH_FNS
             raised_m = true;
         }
         const dim3 mgrid((unsigned)(8 * spx * m.segs));
+        if (!y) {                                      // no y store: the residual pass forms A p again (launch_cg_residual_recompute)
+            KR_ARG(nq == 1 && !xvec, "launch_spmv_fused: the form without y is CG's with x in batches");
+            if (T == 2) hipLaunchKernelGGL((spmv_pattern_fuse_kernel<1, 2, 512, false, true, false>), mgrid, block, lds_m, ctx->s_main, args, f, n_, a->pat_far_lo, a->pat_far_hi);
+            else hipLaunchKernelGGL((spmv_pattern_fuse_kernel<1, 4, 512, false, true, false>), mgrid, block, lds_m, ctx->s_main, args, f, n_, a->pat_far_lo, a->pat_far_hi);
+            KR_HIP(hipGetLastError());
+            phase_mark(ctx, KR_PH_SPMV);
+            return KRYST_OK;
+        }
 #define KR_MARCH_X(NQ_, T_) do { if (xvec) hipLaunchKernelGGL((spmv_pattern_fuse_kernel<NQ_, T_, 512, true, true>), mgrid, block, lds_m, ctx->s_main, args, f, n_, a->pat_far_lo, a->pat_far_hi); \
                                  else hipLaunchKernelGGL((spmv_pattern_fuse_kernel<NQ_, T_, 512, false, true>), mgrid, block, lds_m, ctx->s_main, args, f, n_, a->pat_far_lo, a->pat_far_hi); } while (0)
         if (nq == 1) { if (T == 2) KR_MARCH_X(1, 2); else KR_MARCH_X(1, 4); }
@@ -1828,6 +2051,7 @@ static int32_t launch_spmv_fused_impl(kryst_csr_t a, const double* z, const doub
         phase_mark(ctx, KR_PH_SPMV);
         return KRYST_OK;
     }
+    KR_ARG(y, "launch_spmv_fused: only the marching kernel has a form without y");
     if (lds_s > ((size_t)48 << 10)) {       // (more than the default dynamic LDS limit: once per instance)
         static bool raised = false;
         if (!raised) {
@@ -1985,6 +2209,7 @@ int32_t kryst_csr_fuse_march_info(kryst_csr_t a, int64_t* info) {
     memset(&m, 0, sizeof m);
     if (form) m = fuse_march_plan(a, 2);
     info[0] = m.eligible ? 1 : 0; info[1] = m.eligible && m.on ? 1 : 0; info[2] = m.T; info[3] = m.strips; info[4] = m.S; info[5] = m.segs;
+    info[6] = form && recompute_plan(a).on ? 1 : 0;
     return KRYST_OK;
 }
 
