@@ -30,6 +30,8 @@ pub const KRYST_ERR_BUSY: i32 = 104;
 pub const KRYST_ILU_KRYST_COMPAT: i32 = 0;
 pub const KRYST_ILU_ILUP0: i32 = 1;
 pub const KRYST_ILU_TRUE_ILU0: i32 = 2;
+pub const KRYST_CHEB_SCALE_NONE: i32 = 0;
+pub const KRYST_CHEB_SCALE_JACOBI: i32 = 1;
 pub const KRYST_AMG_AS_WRITTEN: i32 = 0;
 pub const KRYST_AMG_SMOOTHED: i32 = 1;
 pub const KRYST_AMG_DIRECT_MAX: i32 = 4096;
@@ -137,6 +139,11 @@ extern "C" {
     pub fn kryst_pc_ilut(a: Csr, fill: i32, droptol: f64, out: *mut Pc) -> i32;
     pub fn kryst_pc_chebyshev_stub(ctx: Ctx, degree: i32, out: *mut Pc) -> i32;
     pub fn kryst_pc_chebyshev(a: Csr, alpha: f64, beta: f64, degree: i32, out: *mut Pc) -> i32;
+    pub fn kryst_pc_chebyshev_poly(a: Csr, degree: i32, scaling: i32, lo: f64, hi: f64, out: *mut Pc) -> i32;
+    pub fn kryst_pc_chebyshev_poly_info(pc: Pc, degree: *mut i32, scaling: *mut i32, lo: *mut f64, hi: *mut f64, fused: *mut i32) -> i32;
+    pub fn kryst_spectrum_estimate(a: Csr, scaling: i32, steps: i32, seed: u64, alpha_out: *mut f64, beta_out: *mut f64, steps_done: *mut i32,
+                                   theta_min: *mut f64, theta_max: *mut f64, gershgorin: *mut f64) -> i32;
+    pub fn kryst_host_tridiag_extreme_eigs(alpha: *const f64, beta: *const f64, k: i32, lo: *mut f64, hi: *mut f64) -> i32;
     pub fn kryst_pc_approx_inverse(m: Csr, out: *mut Pc) -> i32;
     pub fn kryst_pc_block_jacobi(a: Csr, blk_ptr: *const i64, blk_idx: *const i64, nblocks: i64, out: *mut Pc) -> i32;
     pub fn kryst_pc_block_jacobi_uniform(a: Csr, bsize: i32, out: *mut Pc) -> i32;

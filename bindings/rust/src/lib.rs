@@ -311,6 +311,39 @@ impl HipChebyshev {
     pub fn new(degree: usize, lambda_min: Option<f64>, lambda_max: Option<f64>) -> Self { Self::empty(degree, lambda_min, lambda_max) }
 }
 
+/// Extension (`kryst_spectrum_estimate`): the Lanczos coefficients, the extreme Ritz values and the Gershgorin bound of `W A`.
+pub struct SpectrumEstimate { pub alpha: Vec<f64>, pub beta: Vec<f64>, pub theta_min: f64, pub theta_max: f64, pub gershgorin: f64 }
+
+/// Up to `steps` (1..=64) Lanczos steps on `W^1/2 A W^1/2` (`jacobi`: `W` = Jacobi's inverse diagonal, else nothing).  Single-rank operators.
+pub fn estimate_spectrum(a: &HipCsrMatrix, jacobi: bool, steps: usize, seed: u64) -> Result<SpectrumEstimate, KError> {
+    let mut alpha = vec![0.0f64; steps.max(1)];
+    let mut beta = vec![0.0f64; steps.max(1)];
+    let (mut done, mut tmin, mut tmax, mut g) = (0i32, 0.0f64, 0.0f64, 0.0f64);
+    let scaling = if jacobi { ffi::KRYST_CHEB_SCALE_JACOBI } else { ffi::KRYST_CHEB_SCALE_NONE };
+    check(unsafe { ffi::kryst_spectrum_estimate(a.h, scaling, steps as i32, seed, alpha.as_mut_ptr(), beta.as_mut_ptr(), &mut done, &mut tmin, &mut tmax, &mut g) })?;
+    alpha.truncate(done as usize);
+    beta.truncate(done as usize);
+    Ok(SpectrumEstimate { alpha, beta, theta_min: tmin, theta_max: tmax, gershgorin: g })
+}
+
+device_pc! {
+    /// Extension (`kryst_pc_chebyshev_poly`; nothing in the reference corresponds -- `HipChebyshev` above is its stub and its filter): the
+    /// Chebyshev polynomial preconditioner `z = p_degree(W A) W r`, `degree` SpMVs per apply.  Both bounds must be set before `setup`:
+    /// `with_estimated_bounds` fills them from `estimate_spectrum` (`lambda_max = min(safety * theta_max, gershgorin)`, `lambda_min = lambda_max / ratio`).
+    HipChebyshevPoly { degree: usize = 0, lambda_min: f64 = 0.0, lambda_max: f64 = 0.0, jacobi: bool = true } setup(s, a, out) {
+        ffi::kryst_pc_chebyshev_poly(a.h, s.degree as i32, if s.jacobi { ffi::KRYST_CHEB_SCALE_JACOBI } else { ffi::KRYST_CHEB_SCALE_NONE },
+                                     s.lambda_min, s.lambda_max, &mut out)
+    }
+}
+impl HipChebyshevPoly {
+    pub fn new(degree: usize, lambda_min: f64, lambda_max: f64, jacobi: bool) -> Self { Self::empty(degree, lambda_min, lambda_max, jacobi) }
+    pub fn with_estimated_bounds(degree: usize, a: &HipCsrMatrix, jacobi: bool, steps: usize, ratio: f64, safety: f64, seed: u64) -> Result<Self, KError> {
+        let e = estimate_spectrum(a, jacobi, steps, seed)?;
+        let hi = (safety * e.theta_max).min(e.gershgorin);
+        Ok(Self::empty(degree, hi / ratio, hi, jacobi))
+    }
+}
+
 device_pc! {
     /// `BlockJacobi::setup` + `apply` (src/preconditioner/block_jacobi.rs:39-106) as a device `Preconditioner` on the CSR operator
     /// (the reference's `apply` is an inherent method no solver can take).  `blocks`: index sets in the given order, the last block

@@ -235,6 +235,33 @@ int32_t kryst_pc_ilup(kryst_csr_t a, int32_t fill, kryst_pc_t* out);
 int32_t kryst_pc_ilut(kryst_csr_t a, int32_t fill, double droptol, kryst_pc_t* out);
 int32_t kryst_pc_chebyshev_stub(kryst_ctx_t ctx, int32_t degree, kryst_pc_t* out);  /* Chebyshev trait object: apply -> SolveError, chebyshev.rs:68-70 */
 int32_t kryst_pc_chebyshev(kryst_csr_t a, double alpha, double beta, int32_t degree, kryst_pc_t* out); /* extension: apply == apply_chebyshev */
+/* EXTENSION (nothing in the reference corresponds; it stands beside the stub Chebyshev::apply, chebyshev.rs:35-70, which returns Err, and
+ * beside the filter above): the Chebyshev POLYNOMIAL preconditioner z = p_m(W A) W r of Saad's Alg. 12.1 started from z = 0, DESIGN.md
+ * section 4.15.  degree m in 0..64 is the number of SpMVs (m = 0: a scaled Jacobi); 0 < lo < hi, both finite, bound the spectrum of W A;
+ * scaling KRYST_CHEB_SCALE_JACOBI takes W = kryst_pc_jacobi's inv_diag exactly as that forms it (jacobi.rs:69-71: 0.0 where the diagonal is
+ * missing or zero), KRYST_CHEB_SCALE_NONE multiplies by nothing.  Host scalars, in double, un-fused: theta = (hi + lo) / 2, delta = (hi - lo) / 2, sigma = theta / delta, rho_0 = 1 / sigma,
+ * rho_k = 1 / (2 sigma - rho_{k-1}), c1_k = rho_k rho_{k-1}, c2_k = (2 rho_k) / delta.  Vectors: d_0 = (w r) / theta, z_0 = d_0, res_0 = r;
+ * step k: y = A d_{k-1} (the row sum of kryst_spmv), res_k = res_{k-1} - y, t = w res_k, d_k = c1_k d_{k-1} + c2_k t, z_k = z_{k-1} + d_k.
+ * SpMVs and pointwise passes only: row-partitioned operators are taken.  The step runs fused in one kernel on the plain CSR arrays where the
+ * operator is on one rank and has no compressed form (kryst_csr_encoding == 0 at creation), else as kryst_spmv + one pointwise pass: the same
+ * bits.  a is borrowed.  KRYST_ERR_ARG: non-square operator, degree outside 0..64, lo <= 0, lo >= hi, non-finite bounds, unknown scaling. */
+enum { KRYST_CHEB_SCALE_NONE = 0, KRYST_CHEB_SCALE_JACOBI = 1 };
+int32_t kryst_pc_chebyshev_poly(kryst_csr_t a, int32_t degree, int32_t scaling, double lo, double hi, kryst_pc_t* out);
+/* extension (beside chebyshev.rs:35-70): what a kryst_pc_chebyshev_poly object holds; *fused = 1 when its step is the fused kernel.  Any
+ * pointer may be NULL.  Another kind of preconditioner: KRYST_ERR_ARG. */
+int32_t kryst_pc_chebyshev_poly_info(kryst_pc_t pc, int32_t* degree, int32_t* scaling, double* lo, double* hi, int32_t* fused);
+/* extension (beside chebyshev.rs:35-70, whose bounds the caller must know): bounds for kryst_pc_chebyshev_poly.  min(steps, n) Lanczos steps
+ * without reorthogonalisation on S = W^1/2 A W^1/2 (scaling as above; none: S = A) from q_0 = u / sqrt(dot(u, u)), u =
+ * kryst_vec_fill_splitmix(seed, 0): v = s q_j, y = A v, t = s y, alpha_j = dot(q_j, t), t = t - alpha_j q_j, t = t - beta_{j-1} q_{j-1}
+ * (j > 0), beta_j = sqrt(dot(t, t)), stop when beta_j is zero or not finite, q_{j+1} = t / beta_j; every dot in the order of
+ * kryst_reduce_spec.  alpha_out / beta_out (room for `steps` entries each) receive *steps_done coefficients; *theta_min / *theta_max are
+ * kryst_host_tridiag_extreme_eigs of them; *gershgorin = max_i((sum_k |a_ik|) w_i), a true upper bound.  steps in 1..64.  Errors:
+ * KRYST_ERR_ARG (non-square or empty operator, steps, scaling), KRYST_UNSUPPORTED (a distributed operator: pass bounds),
+ * KRYST_INDEFINITE_PRECONDITIONER (Jacobi scaling and a diagonal entry that is missing, not finite or <= 0, or whose reciprocal overflows;
+ * the row in kryst_hip_last_error_row()), KRYST_FACTOR_ERROR (a non-finite Gershgorin bound), KRYST_INDEFINITE_MATRIX
+ * (theta_max <= 0 or not finite; the outputs are filled). */
+int32_t kryst_spectrum_estimate(kryst_csr_t a, int32_t scaling, int32_t steps, uint64_t seed, double* alpha_out, double* beta_out,
+                                int32_t* steps_done, double* theta_min, double* theta_max, double* gershgorin);
 /* ApproxInv with GIVEN inverse rows (ApproxInv::inv_rows, approxinv.rs:66): apply (approxinv.rs:268-298) is the sparse-row
  * product z = M r, i.e. kryst_spmv with M.  m is borrowed (must outlive the preconditioner).  ApproxInv::setup -- a
  * least-squares fit per column through faer's QR (approxinv.rs:129-264) -- stays on the host with the reference. */
@@ -547,6 +574,11 @@ int64_t kryst_host_halo_recv_plan(int32_t rank, int32_t nranks, const int64_t* r
  * Results: L's strictly-lower kept entries with their multipliers, U's strictly-upper kept entries, the kept diagonal (1.0 where none is
  * kept), each row in stored = ascending-column order (Ilut: in the order ilut.rs leaves them). */
 typedef struct kryst_host_factors_s* kryst_host_factors_t;
+/* extension (beside chebyshev.rs:35-70), host only, no GPU: the extreme eigenvalues of the symmetric tridiagonal k x k matrix with diagonal
+ * alpha[0..k) and off-diagonal beta[0..k-1) (k in 1..64) by bisection with Sturm counts, each run until the midpoint of the bracket is one
+ * of its ends: *lo = the lower end of the smallest eigenvalue's bracket, *hi = the upper end of the largest one's (k = 1: alpha[0]; an
+ * entry that is not finite: NaN for both). */
+int32_t kryst_host_tridiag_extreme_eigs(const double* alpha, const double* beta, int32_t k, double* lo, double* hi);
 /* Ilup::new(fill).setup (src/preconditioner/ilup.rs:77-134) as a row pipeline over `threads` host threads (<= 0: up to 16) in round-robin blocks
  * of `block` rows (<= 0: 2048); any thread count and block size gives the bits of the one-thread loop.  KRYST_SOLVE_ERROR on a zero u_jj
  * (ilup.rs:108-110), the column j of the LOWEST row that met one through kryst_hip_last_error_row(). */

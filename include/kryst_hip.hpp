@@ -362,6 +362,39 @@ struct Chebyshev : DevicePc {                                // chebyshev.rs:35-
     Chebyshev(size_t degree, std::optional<double> lmin, std::optional<double> lmax) : degree(degree), lambda_min(lmin), lambda_max(lmax) {}
     void setup(const HipCsrMatrix& a) override { kryst_pc_t h = nullptr; check(kryst_pc_chebyshev_stub(a.context()->handle(), (int32_t)degree, &h)); reset(h, a.context()->handle()); }
 };
+// EXTENSION (kryst_pc_chebyshev_poly, kryst_spectrum_estimate; nothing in the reference corresponds -- Chebyshev above is its stub): the
+// Chebyshev polynomial preconditioner z = p_degree(W A) W r with W = Jacobi's inverse diagonal (jacobi = true) or nothing.
+struct SpectrumEstimate { std::vector<double> alpha, beta; double theta_min = 0.0, theta_max = 0.0, gershgorin = 0.0; };
+// up to `steps` (1..64) Lanczos steps on W^1/2 A W^1/2 and the Gershgorin bound of W A; single-rank operators (else KError(KRYST_UNSUPPORTED))
+inline SpectrumEstimate estimate_spectrum(const HipCsrMatrix& a, bool jacobi = true, int steps = 10, uint64_t seed = 0x5EED) {
+    SpectrumEstimate e;
+    e.alpha.assign((size_t)(steps > 0 ? steps : 1), 0.0); e.beta = e.alpha;
+    int32_t done = 0;
+    check(kryst_spectrum_estimate(a.handle(), jacobi ? KRYST_CHEB_SCALE_JACOBI : KRYST_CHEB_SCALE_NONE, (int32_t)steps, seed, e.alpha.data(),
+                                  e.beta.data(), &done, &e.theta_min, &e.theta_max, &e.gershgorin));
+    e.alpha.resize((size_t)done); e.beta.resize((size_t)done);
+    return e;
+}
+struct ChebyshevPoly : DevicePc {
+    size_t degree; std::optional<double> lambda_min, lambda_max; bool jacobi; int steps; double ratio, safety; uint64_t seed;
+    explicit ChebyshevPoly(size_t degree, std::optional<double> lmin = std::nullopt, std::optional<double> lmax = std::nullopt, bool jacobi = true,
+                           int steps = 10, double ratio = 30.0, double safety = 1.1, uint64_t seed = 0x5EED)
+        : degree(degree), lambda_min(lmin), lambda_max(lmax), jacobi(jacobi), steps(steps), ratio(ratio), safety(safety), seed(seed) {}
+    // a bound that is not given is estimated: lambda_max = min(safety * theta_max, gershgorin), lambda_min = lambda_max / ratio
+    void setup(const HipCsrMatrix& a) override {
+        std::optional<double> lo = lambda_min, hi = lambda_max;
+        if (!lo || !hi) {
+            const SpectrumEstimate e = estimate_spectrum(a, jacobi, steps, seed);
+            if (!hi) hi = std::min(safety * e.theta_max, e.gershgorin);
+            if (!lo) lo = *hi / ratio;
+        }
+        kryst_pc_t h = nullptr;
+        check(kryst_pc_chebyshev_poly(a.handle(), (int32_t)degree, jacobi ? KRYST_CHEB_SCALE_JACOBI : KRYST_CHEB_SCALE_NONE, *lo, *hi, &h));
+        reset(h, a.context()->handle());
+    }
+    bool fused() const { int32_t f = 0; check(kryst_pc_chebyshev_poly_info(h_, nullptr, nullptr, nullptr, nullptr, &f)); return f != 0; }
+    std::pair<double, double> bounds() const { double lo = 0, hi = 0; check(kryst_pc_chebyshev_poly_info(h_, nullptr, nullptr, &lo, &hi, nullptr)); return {lo, hi}; }
+};
 inline void apply_chebyshev(const HipCsrMatrix& a, const Vec& r, Vec& z, double alpha, double beta, size_t m) {   // chebyshev.rs:83-140
     kryst_ctx_t c = a.context()->handle();
     kryst_vec_t rv = nullptr, zv = nullptr;

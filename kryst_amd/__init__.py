@@ -7,6 +7,7 @@ behaviour (paths relative to the kryst crate):
     CsrMatrix.spmv(x, y) / matvec(x, y)                             src/matrix/sparse.rs:56-67, core/traits.rs:4-7
     dot(x, y), norm(x)                                              src/core/wrappers.rs:90-127
     Jacobi / Ilu0 / Ilup / Chebyshev  .setup(a) .apply(r, z)        src/preconditioner/*.rs
+    ChebyshevPoly(degree, ...), estimate_spectrum(a)                Chebyshev polynomial preconditioner with estimated bounds (extension)
     apply_chebyshev(a, r, z, alpha, beta, m)                        src/preconditioner/chebyshev.rs:83-140
     CgSolver / PcgSolver / GmresSolver / BiCgStabSolver .solve(a, pc, b, x) -> SolveStats   src/solver/*.rs
     MultiVec, CsrMatrix.spmm(X, Y), CgSolver / PcgSolver .solve_many(a, pc, B, X)           several right-hand sides at once (extension)
@@ -25,7 +26,7 @@ from . import _ffi
 from ._ffi import KError, lib, check
 
 __all__ = ["Context", "DeviceVec", "CsrMatrix", "dot", "norm", "Jacobi", "Ilu0", "Ilup", "Ilut", "TrueIlu0", "Chebyshev",
-           "ChebyshevPc", "IdentityPc", "ApproxInv", "BlockJacobi", "AdditiveSchwarz", "Sor", "MatSorType", "SparsityPattern", "Spai", "Amg", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
+           "ChebyshevPc", "ChebyshevPoly", "estimate_spectrum", "host_tridiag_extreme_eigs", "IdentityPc", "ApproxInv", "BlockJacobi", "AdditiveSchwarz", "Sor", "MatSorType", "SparsityPattern", "Spai", "Amg", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
            "Preconditioning", "CgSolver", "PcgSolver", "GmresSolver", "FgmresSolver", "PcaGmresSolver", "Orthog", "CgsSolver", "TfqmrSolver", "MinresSolver", "QmrSolver", "CgnrSolver", "CgneSolver", "BiCgStabSolver", "BiCgStabRightPcSolver", "Session", "KspContext", "SolverKind", "PC", "KError", "reduce_spec",
            "host_stencil7", "partition_rows", "halo_recv_plan", "read_matrix_market", "read_petsc_binary", "host_ilup", "host_ilut", "host_amg", "host_levels", "color_graph", "build_blocks_from_colors",
            "DenseMatrix", "LuSolver", "QrSolver", "host_dense_lu", "host_dense_lu_solve", "host_dense_qr_solve",
@@ -681,6 +682,76 @@ class ChebyshevPc(_Pc):
         self._set(a.ctx, h)
         self._a = a
         return self
+
+
+def host_tridiag_extreme_eigs(alpha, beta):
+    """(lo, hi): the extreme eigenvalues of the symmetric tridiagonal matrix with diagonal `alpha` (k entries, k in 1..64) and off-diagonal
+    `beta` (its first k - 1 entries are used) by bisection with Sturm counts (kryst_host_tridiag_extreme_eigs; host only, no GPU)."""
+    al, be = _f64(alpha), _f64(beta)
+    if len(be) < len(al) - 1:
+        raise KError(102, "host_tridiag_extreme_eigs: beta needs len(alpha) - 1 entries")
+    be = _f64(np.concatenate([be, [0.0]]))              # (never NULL)
+    lo, hi = C.c_double(), C.c_double()
+    check(lib().kryst_host_tridiag_extreme_eigs(_dp(al), _dp(be), len(al), C.byref(lo), C.byref(hi)))
+    return lo.value, hi.value
+
+
+def _check_diag(rc):
+    """check(), with the row of a diagonal entry Jacobi scaling cannot use (KRYST_INDEFINITE_PRECONDITIONER) in KError.row"""
+    if rc == 4:
+        msg = lib().kryst_hip_last_error()
+        raise KError(rc, msg.decode() if msg else "", None, lib().kryst_hip_last_error_row())
+    check(rc)
+
+
+def estimate_spectrum(a, jacobi=True, steps=10, seed=0x5EED):
+    """Extension (kryst_spectrum_estimate): up to `steps` Lanczos steps on W^1/2 A W^1/2 (W = Jacobi's inverse diagonal, or nothing with
+    jacobi=False) and the Gershgorin bound of W A -> {"alpha", "beta", "steps_done", "theta_min", "theta_max", "gershgorin"}.  Single-rank
+    operators; a distributed one raises KError(Unsupported)."""
+    steps = int(steps)
+    al, be = np.zeros(max(steps, 1)), np.zeros(max(steps, 1))
+    k, tmin, tmax, g = C.c_int32(0), C.c_double(), C.c_double(), C.c_double()
+    _check_diag(lib().kryst_spectrum_estimate(a.h, 1 if jacobi else 0, steps, seed, _dp(al), _dp(be), C.byref(k), C.byref(tmin), C.byref(tmax), C.byref(g)))
+    return {"alpha": al[:k.value].copy(), "beta": be[:k.value].copy(), "steps_done": k.value, "theta_min": tmin.value, "theta_max": tmax.value,
+            "gershgorin": g.value}
+
+
+class ChebyshevPoly(_Pc):
+    """Extension (kryst_pc_chebyshev_poly; nothing in the reference corresponds -- Chebyshev above is its stub, ChebyshevPc its filter): the
+    Chebyshev polynomial preconditioner z = p_degree(W A) W r, `degree` SpMVs per apply, with W = Jacobi's inverse diagonal (jacobi=True)
+    or nothing.  Bounds of the spectrum of W A that are None are estimated in setup (estimate_spectrum with `steps` and `seed`):
+    lambda_max = min(safety * theta_max, gershgorin), lambda_min = lambda_max / ratio.  Takes row-partitioned operators when both bounds
+    are given."""
+
+    def __init__(self, degree, lambda_min=None, lambda_max=None, jacobi=True, steps=10, ratio=30.0, safety=1.1, seed=0x5EED):
+        super().__init__()
+        self.degree, self.lambda_min, self.lambda_max, self.jacobi = degree, lambda_min, lambda_max, jacobi
+        self.steps, self.ratio, self.safety, self.seed = steps, ratio, safety, seed
+        self.estimate = None
+
+    def setup(self, a):
+        lo, hi = self.lambda_min, self.lambda_max
+        if lo is None or hi is None:
+            self.estimate = estimate_spectrum(a, self.jacobi, self.steps, self.seed)
+            if hi is None:
+                hi = min(float(self.safety) * self.estimate["theta_max"], self.estimate["gershgorin"])
+            if lo is None:
+                lo = hi / float(self.ratio)
+        h = _ffi.Handle()
+        check(lib().kryst_pc_chebyshev_poly(a.h, self.degree, 1 if self.jacobi else 0, lo, hi, C.byref(h)))
+        self._set(a.ctx, h)
+        self._a = a
+        return self
+
+    def info(self):
+        """{"degree", "jacobi", "lambda_min", "lambda_max", "fused"} of the set-up object (kryst_pc_chebyshev_poly_info); "fused": its step is
+        the one-kernel form on the plain CSR arrays."""
+        if self.h is None:
+            raise KError(2, "preconditioner used before setup")
+        d, sc, f = C.c_int32(), C.c_int32(), C.c_int32()
+        lo, hi = C.c_double(), C.c_double()
+        check(lib().kryst_pc_chebyshev_poly_info(self.h, C.byref(d), C.byref(sc), C.byref(lo), C.byref(hi), C.byref(f)))
+        return {"degree": d.value, "jacobi": bool(sc.value), "lambda_min": lo.value, "lambda_max": hi.value, "fused": bool(f.value)}
 
 
 class IdentityPc(_Pc):
@@ -1700,7 +1771,9 @@ class PC:
     still raises KError(Unsupported), as it did before AMG existed).  `PC.AdditiveSchwarz(overlap=0, subdomains=None, nparts=None)`
     builds AdditiveSchwarz as written; a bare `PC("AdditiveSchwarz")` without its parameters keeps raising KError(Unsupported), following
     AMG.  `PC.Ssor(omega=1.0, its=1)` builds Sor(omega, its, 1, SYMMETRIC_SWEEP, 0.0) and `PC.Multicolor(colors)` the same sweeps in the
-    coloured order (labelled extension); the bare `PC("Ssor")` / `PC("Multicolor")` keep raising KError(Unsupported), following AMG."""
+    coloured order (labelled extension); the bare `PC("Ssor")` / `PC("Multicolor")` keep raising KError(Unsupported), following AMG.
+    `PC.ChebyshevPoly(degree, ...)` builds ChebyshevPoly, the polynomial preconditioner (labelled extension); `PC.Chebyshev` stays the
+    reference's stub."""
 
     def __init__(self, kind, **params):
         self.kind, self.params = kind, params
@@ -1727,6 +1800,11 @@ class PC:
     @staticmethod
     def Chebyshev(degree, emin=None, emax=None):
         return PC("Chebyshev", degree=degree, emin=emin, emax=emax)
+
+    @staticmethod
+    def ChebyshevPoly(degree, lambda_min=None, lambda_max=None, jacobi=True, steps=10, ratio=30.0, safety=1.1, seed=0x5EED):   # labelled extension
+        return PC("ChebyshevPoly", degree=degree, lambda_min=lambda_min, lambda_max=lambda_max, jacobi=jacobi, steps=steps, ratio=ratio,
+                  safety=safety, seed=seed)
 
     @staticmethod
     def BlockJacobi(blocks):                      # pc_context.rs:67 BlockJacobi { blocks }
@@ -1764,6 +1842,8 @@ class PC:
             return Ilut(q["fill"], q["droptol"]).setup(a)
         if k == "Chebyshev":                         # the trait object of the reference (apply is the stub of chebyshev.rs:68-70)
             return Chebyshev(q["degree"], q["emin"], q["emax"]).setup(a)
+        if k == "ChebyshevPoly":                     # labelled extension: the polynomial preconditioner, bounds estimated where not given
+            return ChebyshevPoly(**q).setup(a)
         if k == "BlockJacobi":
             return BlockJacobi(q["blocks"]).setup(a)
         if k == "ApproxInv":

@@ -101,6 +101,9 @@ SIGNATURES = {
     "kryst_pc_chebyshev_stub": (C.c_int32, [Handle, C.c_int32, C.POINTER(Handle)]),
     "kryst_pc_chebyshev": (C.c_int32, [Handle, C.c_double, C.c_double, C.c_int32, C.POINTER(Handle)]),
     "kryst_pc_approx_inverse": (C.c_int32, [Handle, C.POINTER(Handle)]),
+    "kryst_pc_chebyshev_poly": (C.c_int32, [Handle, C.c_int32, C.c_int32, C.c_double, C.c_double, C.POINTER(Handle)]),
+    "kryst_pc_chebyshev_poly_info": (C.c_int32, [Handle, c_i32p, c_i32p, c_dp, c_dp, c_i32p]),
+    "kryst_spectrum_estimate": (C.c_int32, [Handle, C.c_int32, C.c_int32, C.c_uint64, c_dp, c_dp, c_i32p, c_dp, c_dp, c_dp]),
     "kryst_pc_block_jacobi": (C.c_int32, [Handle, c_i64p, c_i64p, C.c_int64, C.POINTER(Handle)]),
     "kryst_pc_block_jacobi_uniform": (C.c_int32, [Handle, C.c_int32, C.POINTER(Handle)]),
     "kryst_pc_block_jacobi_export": (C.c_int32, [Handle, c_i64p, c_i64p, c_i32p, c_dp]),
@@ -176,6 +179,7 @@ SIGNATURES = {
     "kryst_host_read_petsc_binary": (C.c_int64, [C.c_char_p, c_i64p, c_i64p, c_i64p, c_i64p, c_dp]),
     "kryst_host_read_matrix_market": (C.c_int64, [C.c_char_p, c_i64p, c_i64p, c_i64p, c_i64p, c_dp]),
     "kryst_host_halo_recv_plan": (C.c_int64, [C.c_int32, C.c_int32, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p]),
+    "kryst_host_tridiag_extreme_eigs": (C.c_int32, [c_dp, c_dp, C.c_int32, c_dp, c_dp]),
     "kryst_host_ilup": (C.c_int32, [C.c_int64, c_i64p, c_i32p, c_dp, C.c_int32, C.c_int32, C.c_int64, C.POINTER(Handle)]),
     "kryst_host_amg": (C.c_int32, [C.c_int64, c_i64p, c_i32p, c_dp, C.c_int32, C.c_double, C.c_int64, C.POINTER(Handle)]),
     "kryst_host_amg_levels": (C.c_int32, [Handle, c_i32p]),
@@ -241,7 +245,7 @@ def source_sha16(only=None):
 
 # what the SpMV kernels and their launch are built from: the PMC traffic of profiles/spmv_traffic.json is stamped with this, so
 # that work on other kernels (the triangular solves, the solvers) does not orphan it
-SPMV_SOURCES = ("spmv.hip", "csr_create.hip", "csr.h", "common.h", "ew.h", "Makefile")
+SPMV_SOURCES = ("spmv.hip", "spmv_window.h", "csr_create.hip", "csr.h", "common.h", "ew.h", "Makefile")
 
 
 def spmv_source_sha16():

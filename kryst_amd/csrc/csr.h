@@ -70,6 +70,10 @@ constexpr int KR_TMAX = 2048;
 // y <- A x on ctx->s_main.  nq = 0: plain.  nq = 1: also tile partials of sum d[i]*y[i] into partial array 0.
 // nq = 2: additionally sum y[i]*y[i] into partial array 1.  `done` (device flag) makes the launch a no-op when set.
 int32_t launch_spmv(kryst_csr_t a, const double* x, double* y, int nq, const double* dvec, const int* done);
+// the tile list (nullptr: natural order), XCD slotting, grid, window size (pair slots per lane: <= 2, <= 4, else 7) and load kind of the plain
+// wave kernel for the whole single-rank operator (spmv.hip: plain_wave_plan)
+struct PlainWavePlan { const int32_t* tiles; int32_t ntiles, xcd_chunk, swizzle, group, amask, slots; unsigned grid; bool nt; };
+PlainWavePlan plain_wave_plan(kryst_csr_t a);
 // CG / PCG with the direction pass inside the SpMV (spmv.hip: spmv_pattern_fuse_kernel): whether the operator can take it, and the launch
 bool spmv_can_fuse_direction(kryst_csr_t a);
 int32_t launch_spmv_fused(kryst_csr_t a, const double* z, const double* p_old, double* p_new, double* xvec, double* y, int nq,

@@ -140,4 +140,24 @@ struct AmgSetOp {                    // z[i] = src ? src[i] : 0.0  (a fresh z fo
     }
 };
 
+// One step of the Chebyshev polynomial preconditioner behind a stored y = A d (cheb_poly.hip):
+//   res = res - y;  t = w * res (SCALED only);  d = c1 * d + c2 * t;  z = z + d
+// FIRST: res_0 is r itself (`rin`) and z_0 is d_0, read from d.  LAST: only z is stored.
+template <bool FIRST, bool LAST, bool SCALED>
+struct ChebPolyStepOp {
+    static constexpr int NQ = 0; static constexpr const char* TAG = "ChebPolyStep";
+    double c1, c2; const double* y; const double* w; const double* rin; double* res; double* d; double* z;
+    __device__ __forceinline__ void pair(int64_t i, bool, bool, double (&)[1]) const {
+        const d2 yy = ld2(y, i), rp = ld2(FIRST ? rin : res, i), dd = ld2(d, i);
+        d2 zz = dd;
+        if constexpr (!FIRST) zz = ld2(z, i);
+        const double ra = rp.a - yy.a, rb = rp.b - yy.b;
+        double ta = ra, tb = rb;
+        if constexpr (SCALED) { const d2 ww = ld2(w, i); ta = ww.a * ra; tb = ww.b * rb; }
+        const double da = c1 * dd.a + c2 * ta, db = c1 * dd.b + c2 * tb;
+        if constexpr (!LAST) { st2(res, i, ra, rb); st2_keep(d, i, da, db); }
+        st2(z, i, zz.a + da, zz.b + db);
+    }
+};
+
 }  // namespace kr

@@ -3,7 +3,7 @@
 #pragma once
 #include "csr.h"
 
-enum { KR_PC_IDENTITY = 1, KR_PC_JACOBI = 2, KR_PC_ILU = 3, KR_PC_CHEB_STUB = 6, KR_PC_CHEB = 7, KR_PC_SPAI = 9, KR_PC_BLOCK_JACOBI = 10, KR_PC_AMG = 11, KR_PC_ASM = 12, KR_PC_SOR = 13, KR_PC_ASM_ILU = 14 };
+enum { KR_PC_IDENTITY = 1, KR_PC_JACOBI = 2, KR_PC_ILU = 3, KR_PC_CHEB_STUB = 6, KR_PC_CHEB = 7, KR_PC_SPAI = 9, KR_PC_BLOCK_JACOBI = 10, KR_PC_AMG = 11, KR_PC_ASM = 12, KR_PC_SOR = 13, KR_PC_ASM_ILU = 14, KR_PC_CHEB_POLY = 15 };
 
 struct kryst_pc_s {
     const kryst_ctx_t ctx;
@@ -40,6 +40,7 @@ inline bool pc_reads_z(kryst_pc_t pc) { return pc && pc->reads_z(); }
 // the kind's state behind a handle, or nullptr when the handle is null or of another kind (the *_info / *_export entry points)
 template <class T> inline T* pc_cast(kryst_pc_t pc) { return pc && pc->kind == T::KIND ? static_cast<T*>(pc) : nullptr; }
 const double* pc_jacobi_inv_diag(kryst_pc_t pc);            // KR_PC_JACOBI only: PCG fuses the Jacobi apply into its residual update
+int32_t jacobi_inv_diag_dev(kryst_csr_t a, double* inv_diag);   // Jacobi's inv_diag (jacobi.rs:69-71) into a vector of the operator's rows, on ctx->s_main (precond.hip)
 int32_t chebyshev_dev(kryst_csr_t a, const double* r, double* z, double alpha, double beta, int64_t m,
                       double* v0, double* v1, double* v2, const int* done);
 }

@@ -21,6 +21,14 @@ __global__ void jacobi_setup_kernel(const int32_t* row_ptr, const int32_t* col, 
     inv_diag[i] = (d != 0.0) ? 1.0 / d : 0.0;                       // jacobi.rs:69-71
 }
 
+int32_t jacobi_inv_diag_dev(kryst_csr_t a, double* inv_diag) {
+    if (a->nrows <= 0) return KRYST_OK;
+    hipLaunchKernelGGL(jacobi_setup_kernel, dim3((unsigned)((a->nrows + 255) / 256)), dim3(256), 0, a->ctx->s_main,
+                       a->d_row_ptr, a->d_col, a->d_val, (int32_t)a->nrows, inv_diag);
+    KR_HIP(hipGetLastError());
+    return KRYST_OK;
+}
+
 struct JacobiOp {                    // y[i] = inv_diag[i] * x[i]   (jacobi.rs:84-92)
     static constexpr int NQ = 0; static constexpr const char* TAG = "Jacobi";
     const double* inv; const double* x; double* y;
@@ -175,11 +183,8 @@ int32_t kryst_pc_jacobi(kryst_csr_t a, kryst_pc_t* out) {
     JacobiPc* pc = new JacobiPc(a);
     int32_t rc = alloc_vec(a->ctx, &pc->d_inv_diag, pc->n);
     if (rc != KRYST_OK) { kryst_pc_destroy(pc); return rc; }
-    if (pc->n > 0) {
-        hipLaunchKernelGGL(jacobi_setup_kernel, dim3((unsigned)((pc->n + 255) / 256)), dim3(256), 0, a->ctx->s_main,
-                           a->d_row_ptr, a->d_col, a->d_val, (int32_t)pc->n, pc->d_inv_diag);
-        KR_HIP(hipGetLastError());
-    }
+    rc = jacobi_inv_diag_dev(a, pc->d_inv_diag);
+    if (rc != KRYST_OK) { kryst_pc_destroy(pc); return rc; }
     *out = pc;
     return KRYST_OK;
 }

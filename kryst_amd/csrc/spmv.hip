@@ -20,13 +20,11 @@
 //    Column indices >= nloc address the halo buffer.
 #include "csr.h"
 #include "ew.h"
+#include "spmv_window.h"
 #include <algorithm>
 
 
 namespace kr {
-
-typedef int    v2i __attribute__((ext_vector_type(2)));
-typedef double v2d __attribute__((ext_vector_type(2)));
 
 struct SpmvArgs {
     const int32_t* row_ptr; const int32_t* col; const double* val;
@@ -49,12 +47,6 @@ struct SpmvArgs {
 #endif
 };
 
-template <bool NT, class T>
-__device__ __forceinline__ T stream_load(const T* p) {
-    if constexpr (NT) return __builtin_nontemporal_load(p);
-    else return *p;
-}
-
 template <bool HALO>
 __device__ __forceinline__ double gather(const SpmvArgs& a, int32_t c) {
     if constexpr (HALO) {
@@ -63,23 +55,6 @@ __device__ __forceinline__ double gather(const SpmvArgs& a, int32_t c) {
     } else {
         return a.x[c];
     }
-}
-
-// ascending serial sum of prod[beg-base .. end-base) continued into s: LDS reads are issued four at a time
-// (clamped, branch-free) and folded in index order
-__device__ __forceinline__ double row_sum(const double* prod, int base, int beg, int end, double s) {
-    for (int k = beg; k < end; k += 4) {
-        const int last = end - 1 - base;
-        const double v0 = prod[k - base];
-        const double v1 = prod[min(k + 1 - base, last)];
-        const double v2 = prod[min(k + 2 - base, last)];
-        const double v3 = prod[min(k + 3 - base, last)];
-        s = s + v0;
-        if (k + 1 < end) s = s + v1;
-        if (k + 2 < end) s = s + v2;
-        if (k + 3 < end) s = s + v3;
-    }
-    return s;
 }
 
 // Products-in-LDS form (plain int32 columns): each of the 4 waves streams the nnz range of ITS 128 rows (lane l: rows
@@ -1601,6 +1576,32 @@ static int32_t launch_tiles(kryst_csr_t a, const double* x, double* y, int nq, c
 #undef KR_SPMV_LAUNCH
     KR_HIP(hipGetLastError());
     return KRYST_OK;
+}
+
+// what launch_tiles<false> hands spmv_wave_kernel for the whole operator under the current settings, for a kernel of another file that walks the
+// plain arrays the same way (cheb_poly.hip)
+PlainWavePlan plain_wave_plan(kryst_csr_t a) {
+    PlainWavePlan p;
+    const bool ordered = uses_tile_order(a);
+    p.tiles = ordered ? a->d_tile_order : nullptr;
+    p.ntiles = (int32_t)(ordered ? a->order_slots1 : a->ntiles);
+    const bool beyond_cache = a->nrows * 8 > (256ll << 20);
+    p.amask = env_int("KRYST_SPMV_ALIGN", beyond_cache ? 1 : 0) ? 31 : 1;
+    p.nt = env_int("KRYST_SPMV_NT", beyond_cache ? 1 : 0) != 0;
+    p.swizzle = ordered ? 0 : env_int("KRYST_SPMV_SWIZZLE", 0);
+    p.group = ordered ? 1 : std::max(1, env_int("KRYST_SPMV_GROUP", 1));
+    int64_t chunk = ((int64_t)p.ntiles + 7) / 8;
+    if (!p.swizzle) chunk = (chunk + p.group - 1) / p.group * p.group;
+    p.xcd_chunk = (int32_t)chunk;
+    int64_t per = chunk;
+    const int bpc = spmv_blocks_per_cu();
+    if (bpc > 0) per = std::min<int64_t>(chunk, std::max<int64_t>(1, (int64_t)a->ctx->num_cu * bpc / 8));
+    p.grid = (unsigned)(per * 8);
+    p.slots = a->slots;
+    if (p.slots > 4 && beyond_cache) p.slots = 4;
+    const int slots_env = env_int("KRYST_SPMV_SLOTS", 0);
+    if (slots_env > 0) p.slots = slots_env;
+    return p;
 }
 
 void halo_send_tiles(kryst_csr_t a, std::vector<std::pair<int64_t, int64_t>>& ranges) {
