@@ -313,7 +313,7 @@ __device__ __forceinline__ int fold2(const double* partials, int64_t stride, int
         for (int q = 0; q < NQ; ++q) __hip_atomic_store(&chunks[q * cstride + blockIdx.x], out[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // the chunk values are write-through (agent-scope) stores: once they have been acknowledged they are visible to the agent-scope
         // loads of the last workgroup.  (An agent-scope FENCE writes back / invalidates the whole L2 on this chip -- measured in
-        // ilu.hip's factorisation kernel: 13 per row made a 14 ms launch 190 ms -- and is not needed on either side.)
+        // ilu_setup_device.hip's factorisation kernel: 13 per row made a 14 ms launch 190 ms -- and is not needed on either side.)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const unsigned int t = atomicAdd(ticket, 1u);
         is_last = (t == gridDim.x - 1) ? 1 : 0;

@@ -309,6 +309,90 @@ void host_ilut_rows(int64_t n, const int64_t* rp, const int32_t* col, const doub
     }, threads);
 }
 
+// ---- ILU(0) on A's pattern (kryst_pc_ilu0's host path)
+int64_t host_ilu0_values(int64_t n, const int64_t* rp, const int32_t* col, const double* val, int mode, double* w) {
+    // diagonal position of every row (halo columns, col >= n, are outside the local block)
+    std::vector<int64_t> dpos((size_t)n, -1);
+    par_rows(n, [&](int64_t lo, int64_t hi) {
+        for (int64_t i = lo; i < hi; ++i)
+            for (int64_t k = rp[i]; k < rp[i + 1]; ++k) if (col[k] == i) dpos[i] = k;
+    });
+    if (mode == 2) {                                  // textbook IKJ restricted to the pattern (Saad Alg. 10.4)
+        std::vector<int64_t> pos((size_t)n, -1);
+        for (int64_t i = 0; i < n; ++i) {
+            for (int64_t k = rp[i]; k < rp[i + 1]; ++k) if (col[k] < n) pos[col[k]] = k;
+            for (int64_t k = rp[i]; k < rp[i + 1]; ++k) {
+                const int64_t c = col[k];
+                if (c >= n) continue;                 // halo column (another rank's row): not part of this rank's block.  A LOWER
+                if (c >= i) break;                    // neighbour's halo column is stored first and numbered n + h: skip, do not stop
+                const int64_t kd = dpos[c];
+                if (kd < 0 || w[kd] == 0.0) return c;
+                w[k] = w[k] / w[kd];
+                for (int64_t kk = rp[c]; kk < rp[c + 1]; ++kk) {
+                    const int64_t j = col[kk];
+                    if (j > c && j < n && pos[j] >= 0) w[pos[j]] = w[pos[j]] - w[k] * w[kk];
+                }
+            }
+            for (int64_t k = rp[i]; k < rp[i + 1]; ++k) if (col[k] < n) pos[col[k]] = -1;
+        }
+        return -1;
+    }
+    // ilu.rs:76-80 / ilup.rs:104-111: l_ij = a_ij / a_jj for stored nonzeros below the diagonal; U = triu(A)
+    std::atomic<long long> bad{-1};                                        // lowest row whose pivot is zero (the reference stops at the first)
+    par_rows(n, [&](int64_t lo, int64_t hi) {
+        for (int64_t i = lo; i < hi; ++i)
+            for (int64_t k = rp[i]; k < rp[i + 1]; ++k) {
+                const int64_t j = col[k];
+                if (j < i && val[k] != 0.0) {
+                    const double ujj = dpos[j] >= 0 ? val[dpos[j]] : 0.0;
+                    if (mode == 1 && ujj == 0.0) {                         // ilup.rs:106-108
+                        long long cur = bad.load();
+                        while ((cur < 0 || (long long)i < cur) && !bad.compare_exchange_weak(cur, (long long)i)) {}
+                        return;
+                    }
+                    w[k] = val[k] / ujj;
+                }
+            }
+    });
+    if (bad.load() < 0) return -1;
+    const int64_t i = bad.load();                                          // that row's first entry with a zero pivot names the column
+    for (int64_t k = rp[i]; k < rp[i + 1]; ++k) {
+        const int64_t j = col[k];
+        if (j < i && val[k] != 0.0 && (dpos[j] < 0 || val[dpos[j]] == 0.0)) return j;
+    }
+    return i;                                                              // (not reached: row i met one)
+}
+
+void host_ilu0_split(int64_t n, const int64_t* rp, const int32_t* col, const double* w, bool divide, FlatRows& le, FlatRows& ue, hvec<double>& dg) {
+    le.ptr.assign((size_t)n + 1, 0); ue.ptr.assign((size_t)n + 1, 0);
+    dg = hvec<double>((size_t)n, 1.0);
+    par_rows(n, [&](int64_t lo, int64_t hi) {                              // count, prefix, then fill (stored order = ascending column)
+        for (int64_t i = lo; i < hi; ++i) {
+            int64_t nl = 0, nu = 0;
+            for (int64_t k = rp[i]; k < rp[i + 1]; ++k) {
+                const int64_t j = col[k];
+                if (j >= n || w[k] == 0.0) continue;                       // halo column / `!= T::zero()` filters
+                if (j < i) ++nl; else if (j > i) ++nu;
+            }
+            le.ptr[i + 1] = nl; ue.ptr[i + 1] = nu;
+        }
+    });
+    for (int64_t i = 0; i < n; ++i) { le.ptr[i + 1] += le.ptr[i]; ue.ptr[i + 1] += ue.ptr[i]; }
+    le.col.resize((size_t)le.ptr[n]); le.val.resize((size_t)le.ptr[n]); ue.col.resize((size_t)ue.ptr[n]); ue.val.resize((size_t)ue.ptr[n]);
+    par_rows(n, [&](int64_t lo, int64_t hi) {
+        for (int64_t i = lo; i < hi; ++i) {
+            int64_t wl = le.ptr[i], wu = ue.ptr[i];
+            for (int64_t k = rp[i]; k < rp[i + 1]; ++k) {
+                const int64_t j = col[k];
+                if (j >= n || w[k] == 0.0) continue;
+                if (j < i) { le.col[wl] = (int32_t)j; le.val[wl] = w[k]; ++wl; }
+                else if (j > i) { ue.col[wu] = (int32_t)j; ue.val[wu] = w[k]; ++wu; }
+                else if (divide) dg[i] = w[k];                             // ilup.rs:160-164 (missing diagonal: no divide)
+            }
+        }
+    });
+}
+
 // ---- dependency levels of a triangular factor
 int32_t host_levels(int64_t n, const int64_t* ptr, const int32_t* col, bool forward, int32_t* lvl) {
     int32_t nl = 0;

@@ -1,6 +1,6 @@
 // Host-side factorisations of the ILU family, free of any device call: the row pipeline of Ilup::new(p).setup (ilup.rs:77-134), the
 // independent rows of Ilut::setup (ilut.rs:80-117) and the dependency levels of a triangular factor (the level scheduler of the general
-// triangular solve).  ilu.hip calls them between the download of the operator's rows and the upload of the factors; the C ABI exports them
+// triangular solve).  ilu_setup_host.hip calls them between the download of the operator's rows and the upload of the factors; the C ABI exports them
 // on plain host arrays (kryst_host_ilup / kryst_host_ilut / kryst_host_levels, include/kryst_hip.h) so that a CPU-only caller -- and the
 // sanitizer tier, `make -C kryst_amd/csrc san SAN=thread` -- can run exactly the code the GPU set-up runs.  No HIP header in here.
 #pragma once
@@ -93,6 +93,13 @@ int host_ilup_rows(int64_t n, const int64_t* rp, const int32_t* col, const doubl
 // Ilut::new(fill, droptol).setup (ilut.rs:80-117: no elimination -- drop by magnitude, keep the `fill` largest of a row, split at the diagonal)
 void host_ilut_rows(int64_t n, const int64_t* rp, const int32_t* col, const double* val, int fill, double droptol,
                     FlatRows& le, FlatRows& ue, hvec<double>& dg, int threads = 0);
+// ILU(0) on A's pattern, the host path of kryst_pc_ilu0, in two steps (the device's IKJ factorisation may stand in for the first).
+// Values: `w` holds A's values on entry and the factor's on return -- mode 0 (Ilu0 as written, ilu.rs:59-122) and 1 (Ilup::new(0), ilup.rs:77-134):
+// l_ij = a_ij / a_jj below the diagonal, everything else as stored; mode 2: the textbook IKJ loop.  Returns -1, or the row whose pivot is zero:
+// mode 2 the pivot row the sequential loop stops at, mode 1 the j the LOWEST row that meets a zero u_jj meets first (mode 0 never fails: it
+// divides by the zero).  (Only kryst_pc_ilu0 calls them: not exported.)  Split: kept (nonzero, local) entries below / above the diagonal in stored order, and the kept diagonal where `divide`.
+__attribute__((visibility("hidden"))) int64_t host_ilu0_values(int64_t n, const int64_t* rp, const int32_t* col, const double* val, int mode, double* w);
+__attribute__((visibility("hidden"))) void host_ilu0_split(int64_t n, const int64_t* rp, const int32_t* col, const double* w, bool divide, FlatRows& le, FlatRows& ue, hvec<double>& dg);
 // dependency levels of a triangular factor given by its strictly-lower (forward) or strictly-upper (!forward) rows: lvl[i] = 1 + the highest
 // level among the rows i depends on (0 when it depends on none).  Returns the number of levels.
 int32_t host_levels(int64_t n, const int64_t* ptr, const int32_t* col, bool forward, int32_t* lvl);

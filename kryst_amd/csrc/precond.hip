@@ -1,5 +1,5 @@
 // Pointwise preconditioner applies for gfx950: Jacobi (src/preconditioner/jacobi.rs), the Chebyshev filter
-// (src/preconditioner/chebyshev.rs:83-140) and the ILU(0)-family triangular solves (ilu.rs / ilup.rs; in ilu.hip).
+// (src/preconditioner/chebyshev.rs:83-140) and the ILU(0)-family triangular solves (ilu.rs / ilup.rs; in ilu.hip, set up in ilu_setup_*.hip).
 #include "pc.h"
 #include "ew.h"
 #include <cfloat>

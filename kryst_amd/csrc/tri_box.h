@@ -301,7 +301,7 @@ __global__ __launch_bounds__(256) void tri_box_kernel(const TriArgs* args, const
                 if (m == sidx && t + sidx < lim && (bad & (qmask << (sidx >> 1))) == 0) m = sidx + 1;
             }
             // out of patience (tri_wave.h): hand over whatever is there, tell every block to do the same, raise the host-visible word; the
-            // host repeats the work with the barrier-free plane kernels (ilu.hip: ilu_health)
+            // host repeats the work with the barrier-free plane kernels (ilu.hip: IluPc::health)
             if (m == 0 && (budget == 1 || ((budget & 255) == 0 && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0))) {
                 __hip_atomic_store(abort_word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(gave_up, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -24,7 +24,7 @@
 //
 // Progress relies on the blocks a resident block waits for being resident or finished (workgroups start in index order, blocks
 // are numbered along anti-diagonals): an observed property, not a HIP guarantee -- every spin has a budget, and a poller that
-// runs out of patience raises the host-visible give-up word (ilu.hip: ilu_health -> plane kernels).
+// runs out of patience raises the host-visible give-up word (ilu.hip: IluPc::health -> plane kernels).
 #pragma once
 
 namespace kr {

@@ -243,7 +243,7 @@ __global__ __launch_bounds__(192) void tri_wave_kernel(const TriArgs* args, cons
             // block waits for are resident or finished, which holds because the hardware starts workgroups in index order -- an
             // observed property, not a HIP guarantee.  Should it ever fail (or a logic error stall the front), hand over the
             // sentinels (NaNs), tell every block to do the same so that the launch ends at once, and raise the host-visible word:
-            // the host then repeats the work with the barrier-free plane kernels (ilu.hip: ilu_health)
+            // the host then repeats the work with the barrier-free plane kernels (ilu.hip: IluPc::health)
             if (m == 0 && (budget == 1 || ((budget & 255) == 0 && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0))) {
                 __hip_atomic_store(abort_word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(gave_up, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // mapped host word, never cleared by the device: the host reads it at its next sync

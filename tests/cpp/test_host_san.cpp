@@ -2,6 +2,7 @@
 //   * the Ilup(p) row pipeline (host_factor.cpp: per-row flag bytes, round-robin blocks, worker arenas) and the parallel Ilut rows at 1, 3 and 16
 //     threads with blocks of 1 ... 2 048 rows, compared with the oracle's dense restatements (kro_ilup_build / kro_ilut_build, compiled in
 //     without OpenMP) entry by entry -- including WHICH zero pivot is reported, with the zero pivot in every position of a block;
+//   * the host loops of ILU(0) (values on A's pattern for the three modes, the split into L and U rows) against the oracle, bit for bit;
 //   * the level scheduler;
 //   * the host block pool and the janitor thread (blocks released on one thread while the next set-up allocates);
 //   * the counted shared mappings of inter-process handles (ipc_table.h) through fake open / close calls, hammered by eight threads.
@@ -138,6 +139,48 @@ static void ilut_cases() {
     }
 }
 
+// ---- ILU(0) on A's pattern (host_ilu0_values / host_ilu0_split: the host path of kryst_pc_ilu0) against the oracle's kro_ilu0_compat_setup,
+// kro_ilup0_setup and kro_ilu0_true_setup, bit for bit on every stored entry; modes 0 Ilu0 as written, 1 Ilup::new(0), 2 textbook ILU(0)
+static bool same_bits(double a, double b) { return memcmp(&a, &b, sizeof a) == 0; }
+static void ilu0_case(const char* name, const Csr& a, int mode, int64_t zero_row) {
+    const kro_csr_t oa{a.n, a.n, a.rp.data(), a.ci64.data(), a.va.data()};
+    const size_t nnz = a.va.size();
+    std::vector<double> lf(nnz), uf(nnz), w(a.va);
+    const int32_t orc = mode == 0 ? kro_ilu0_compat_setup(&oa, lf.data(), uf.data()) : mode == 1 ? kro_ilup0_setup(&oa, lf.data(), uf.data()) : kro_ilu0_true_setup(&oa, lf.data(), uf.data());
+    const int64_t bad = host_ilu0_values(a.n, a.rp.data(), a.ci.data(), a.va.data(), mode, w.data());
+    // the documented returns: Ilu0 as written divides by the zero and succeeds; Ilup(0) is a solve error, textbook ILU(0) a zero pivot, at that row
+    CHECK((bad >= 0) == (orc != KRO_OK), "%s mode %d: zero row %lld, oracle %d", name, mode, (long long)bad, orc);
+    if (orc != KRO_OK) {
+        CHECK(orc == (mode == 1 ? KRO_SOLVE_ERROR : KRO_ZERO_PIVOT) && mode != 0 && bad == zero_row, "%s mode %d: oracle %d, row %lld (expected %lld)", name, mode, orc, (long long)bad, (long long)zero_row);
+        return;
+    }
+    FlatRows le, ue; hvec<double> dg;
+    host_ilu0_split(a.n, a.rp.data(), a.ci.data(), w.data(), mode != 0, le, ue, dg);
+    CHECK((int64_t)le.ptr.size() == a.n + 1 && (int64_t)ue.ptr.size() == a.n + 1 && (int64_t)dg.size() == a.n, "%s mode %d: sizes", name, mode);
+    for (int64_t i = 0; i < a.n && g_fail == 0; ++i) {
+        int64_t ql = le.ptr[(size_t)i], qu = ue.ptr[(size_t)i]; double d = 1.0;
+        for (int64_t k = a.rp[i]; k < a.rp[i + 1] && g_fail == 0; ++k) {
+            const int64_t j = a.ci[k];
+            const double f = j < i ? lf[(size_t)k] : uf[(size_t)k];
+            CHECK(same_bits(w[(size_t)k], f), "%s mode %d: value of entry (%lld, %lld)", name, mode, (long long)i, (long long)j);
+            if (f == 0.0) continue;                                          // not kept
+            if (j < i) { CHECK(ql < le.ptr[(size_t)i + 1] && le.col[(size_t)ql] == j && same_bits(le.val[(size_t)ql], f), "%s mode %d: L row %lld", name, mode, (long long)i); ++ql; }
+            else if (j > i) { CHECK(qu < ue.ptr[(size_t)i + 1] && ue.col[(size_t)qu] == j && same_bits(ue.val[(size_t)qu], f), "%s mode %d: U row %lld", name, mode, (long long)i); ++qu; }
+            else if (mode != 0) d = f;
+        }
+        CHECK(ql == le.ptr[(size_t)i + 1] && qu == ue.ptr[(size_t)i + 1], "%s mode %d: row %lld lengths", name, mode, (long long)i);
+        CHECK(same_bits(d, dg[(size_t)i]), "%s mode %d: diagonal of row %lld", name, mode, (long long)i);
+    }
+}
+static void ilu0_cases() {
+    const Csr grid = stencil7(6), band = random_band(400, 9, 40, 5), holed = random_band(400, 9, 40, 5, 137);
+    for (int mode = 0; mode <= 2; ++mode) {
+        ilu0_case("stencil 6^3", grid, mode, -1);
+        ilu0_case("random band 400", band, mode, -1);
+        ilu0_case("random band 400, zero diagonal in row 137", holed, mode, 137);
+    }
+}
+
 static void level_cases() {
     const Csr a = stencil7(6);
     std::vector<int64_t> lp{0}; std::vector<int32_t> lc;
@@ -206,12 +249,13 @@ static void ipc_table_cases() {
 int main() {
     ilup_cases();
     ilut_cases();
+    ilu0_cases();
     level_cases();
     pool_cases();
     ipc_table_cases();
     janitor_wait();
     if (g_fail) { fprintf(stderr, "test_host_san: %d check(s) failed\n", g_fail); return 1; }
-    printf("test_host_san ok: Ilup row pipeline (1 / 3 / 16 threads x blocks 1..2048 x fill 1..3, zero pivot in 18 positions), Ilut rows, level scheduler, "
+    printf("test_host_san ok: Ilup row pipeline (1 / 3 / 16 threads x blocks 1..2048 x fill 1..3, zero pivot in 18 positions), Ilut rows, ILU(0) values and split (3 modes), level scheduler, "
            "host pool + janitor, counted shared mappings\n");
     return 0;
 }
