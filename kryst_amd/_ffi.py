@@ -245,7 +245,7 @@ def source_sha16(only=None):
 
 # what the SpMV kernels and their launch are built from: the PMC traffic of profiles/spmv_traffic.json is stamped with this, so
 # that work on other kernels (the triangular solves, the solvers) does not orphan it
-SPMV_SOURCES = ("spmv.hip", "spmv_window.h", "csr_create.hip", "csr.h", "common.h", "ew.h", "Makefile")
+SPMV_SOURCES = ("spmv.hip", "spmv.h", "spmv_stream.hip", "spmv_pattern.hip", "spmv_fuse.hip", "halo.hip", "spmv_window.h", "csr_create.hip", "csr.h", "common.h", "ew.h", "Makefile")
 
 
 def spmv_source_sha16():

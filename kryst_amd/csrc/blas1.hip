@@ -78,7 +78,7 @@ __global__ __launch_bounds__(KR_F) void final_fold_kernel(const double* partials
 }
 
 bool fold_gave_up(kryst_ctx_t ctx) {
-    unsigned int w[2] = {0, 0};          // [0]: a fold's polling hand-off, [1]: a halo pull (spmv.hip: halo_pull_kernel) ran out of patience
+    unsigned int w[2] = {0, 0};          // [0]: a fold's polling hand-off, [1]: a halo pull (halo.hip: halo_pull_kernel) ran out of patience
     if (hipMemcpyAsync(w, fold_err(ctx), sizeof w, hipMemcpyDeviceToHost, ctx->s_main) != hipSuccess || hipStreamSynchronize(ctx->s_main) != hipSuccess) { (void)hipGetLastError(); return false; }
     if (!w[0] && !w[1]) return false;
     (void)hipMemsetAsync(fold_err(ctx), 0, sizeof w, ctx->s_main);

@@ -27,7 +27,7 @@ struct ChebStepArgs {
     const int* done;
 };
 
-// spmv_wave_kernel (spmv.hip) with x = d_old and, in place of the y store, the step of ChebPolyStepOp on the two rows the lane owns:
+// spmv_wave_kernel (spmv_stream.hip) with x = d_old and, in place of the y store, the step of ChebPolyStepOp on the two rows the lane owns:
 // the row sums s0, s1 ARE y.  d_new is another buffer than d_old (other rows still gather it); res and z are touched by their owner only.
 template <bool FIRST, bool LAST, bool SCALED, int SLOTS, bool NT>
 __global__ __launch_bounds__(KR_T) void cheb_poly_step_kernel(const ChebStepArgs a) {

@@ -140,7 +140,7 @@ struct kryst_ctx_s {
     bool ipc_on = false;                         // reduce_then uses the mailbox path
     bool ipc_failed = false;                     // the test reduction over the mailboxes failed (agreed across ranks): never switched on again
     kr::PhaseTimer* phase = nullptr;     // non-null while kryst_phase_timing is on
-    std::vector<void*> deferred_free;    // device allocations that outlive their owner and go with the context (spmv.hip: halo_peer_destroy)
+    std::vector<void*> deferred_free;    // device allocations that outlive their owner and go with the context (halo.hip: halo_peer_destroy)
     int num_cu = 256;
 };
 

@@ -74,11 +74,11 @@ int32_t launch_spmv(kryst_csr_t a, const double* x, double* y, int nq, const dou
 // wave kernel for the whole single-rank operator (spmv.hip: plain_wave_plan)
 struct PlainWavePlan { const int32_t* tiles; int32_t ntiles, xcd_chunk, swizzle, group, amask, slots; unsigned grid; bool nt; };
 PlainWavePlan plain_wave_plan(kryst_csr_t a);
-// CG / PCG with the direction pass inside the SpMV (spmv.hip: spmv_pattern_fuse_kernel): whether the operator can take it, and the launch
+// CG / PCG with the direction pass inside the SpMV (spmv_fuse.hip: spmv_pattern_fuse_kernel): whether the operator can take it, and the launch
 bool spmv_can_fuse_direction(kryst_csr_t a);
 int32_t launch_spmv_fused(kryst_csr_t a, const double* z, const double* p_old, double* p_new, double* xvec, double* y, int nq,
                           const double* alpha, const double* beta, const long long* xpend, long long it, const int* done);
-// CG without a stored A p (spmv.hip: cg_recompute_residual_kernel): whether the fused launch of an iteration may drop its y store (launch_spmv_fused
+// CG without a stored A p (spmv_fuse.hip: cg_recompute_residual_kernel): whether the fused launch of an iteration may drop its y store (launch_spmv_fused
 // with y == nullptr: the marching kernel, nq == 1, no xvec) -- read ONCE per iteration and handed to both launches -- and the residual pass that goes
 // with it: r -= alpha A p with the tile partials of (r, r), A p formed again from p.  keep: r is stored temporal (keep_in_cache)
 bool spmv_can_recompute_ap(kryst_csr_t a);

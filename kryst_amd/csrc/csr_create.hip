@@ -1,5 +1,5 @@
 // Building the device operator: validation (SymbolicSparseRowMat::new_checked, sparse.rs:36-42), the CSR arrays, the lossless
-// re-encodings the SpMV kernels stream (CSR-D8 offset codes, CSR-D16 value codes, CSR-P16 row patterns; see spmv.hip), the
+// re-encodings the SpMV kernels stream (CSR-D8 offset codes, CSR-D16 value codes, CSR-P16 row patterns; see spmv.hip and the units it maps), the
 // row-partitioned form with its halo plan, and the device-side generator of the synthetic 7-point operators.
 #include "csr.h"
 #include "ew.h"

@@ -79,7 +79,7 @@ static int32_t mvec_transfer(kryst_mvec_t mv, double* host, int64_t ld, bool up)
 }
 
 // ---------------------------------------------------------------------------------------------------- SpMM
-// The shape of spmv_rows_kernel (spmv.hip) on K interleaved columns.  A workgroup owns 512-row tiles, thread t rows 2t and 2t+1.  Phase 1:
+// The shape of spmv_rows_kernel (spmv_stream.hip) on K interleaved columns.  A workgroup owns 512-row tiles, thread t rows 2t and 2t+1.  Phase 1:
 // each wave streams the (col, val) run of its 128 rows into a private LDS window, every load of the window in flight at once, ordered by
 // wave barriers only.  Phase 2: the owner lane walks its two rows in ascending column order and loads the K contiguous doubles of X-row c
 // with 16-byte loads, U entries of each row in flight; 2 K running sums stay in registers.  Rows longer than a window loop over windows.

@@ -129,7 +129,7 @@ struct GateXPending {                // runs while the solve is under way, and o
     __device__ __forceinline__ bool skip() const { return st->done && st->xlast != it; }
 };
 // The direction pass on a distributed operator whose neighbours get contiguous runs of rows (k-slab partitions): the tiles that hold
-// those rows first, then the halo exchange of the new p is STARTED (spmv.hip: halo_begin), then the rest of the vector -- the planes
+// those rows first, then the halo exchange of the new p is STARTED (halo.hip: halo_begin), then the rest of the vector -- the planes
 // travel while the pass is still writing the interior, not only during the next SpMV's interior tiles (which the staged-window
 // kernel has made shorter than the exchange).  Same launches' worth of work, same bits.  KRYST_HALO_EARLY=0: one launch, exchange
 // started by the SpMV as before.
@@ -334,7 +334,7 @@ struct CgRun : SolverRun {
     }
     int32_t begin() override {
         KR_TRY(solve_args_check(io, bv, xv));
-        // the direction pass inside the SpMV (spmv.hip: spmv_pattern_fuse_kernel) where the operator's form allows it
+        // the direction pass inside the SpMV (spmv_fuse.hip: spmv_pattern_fuse_kernel) where the operator's form allows it
         const bool deferred = cg_defer_x() && !prm.has_radius && !prm.has_obj_target && prm.norm_type != 2;
         fuse = deferred && spmv_can_fuse_direction(a);
         xb = fuse ? cg_x_batch(false) : deferred ? cg_x_batch_unfused() : 1;
@@ -360,7 +360,7 @@ struct CgRun : SolverRun {
     int32_t iterate(int64_t it) override {
         if (fuse) {
             // iteration it: [x += alpha p_old owed by iteration it - 1 (xb == 1); p = r + beta p_old; Ap; (p, Ap)] in ONE pass, alpha, the residual pass, beta
-            // recompute: the fused launch stores no Ap and the residual pass forms it again from p_new (spmv.hip: cg_recompute_residual_kernel) -- decided
+            // recompute: the fused launch stores no Ap and the residual pass forms it again from p_new (spmv_fuse.hip: cg_recompute_residual_kernel) -- decided
             // ONCE per iteration, here, for both launches (KRYST_CG_RECOMPUTE_AP may change between session steps); every other iteration keeps ap
             const bool recompute = fused_upto == it - 1 && it > 1 && xb > 1 && spmv_can_recompute_ap(a);
             if (fused_upto == it - 1 && it > 1) {
@@ -500,7 +500,7 @@ struct PcgRun : SolverRun {
     int32_t begin() override {
         KR_TRY(solve_args_check(io, bv, xv));
         // radius / obj_target are fields of PcgSolver (pcg.rs:39-41) but PcgSolver::solve never reads them: accepted, ignored
-        fuse = cg_defer_x() && spmv_can_fuse_direction(a);                                        // (spmv.hip: spmv_pattern_fuse_kernel)
+        fuse = cg_defer_x() && spmv_can_fuse_direction(a);                                        // (spmv_fuse.hip: spmv_pattern_fuse_kernel)
         xb = fuse ? cg_x_batch(true) : cg_defer_x() ? cg_x_batch_unfused() : 1;
         xb = ring_if_it_fits(ctx, n, xb, 4 + xb + 1);
         ringdir = !fuse && xb > 1;

@@ -1,4 +1,4 @@
-// What the window kernels of the plain CSR arrays share (spmv.hip: spmv_wave_kernel; cheb_poly.hip: cheb_poly_step_kernel): the
+// What the window kernels of the plain CSR arrays share (spmv_stream.hip: spmv_wave_kernel; cheb_poly.hip: cheb_poly_step_kernel): the
 // streamed loads and the ascending row sum over a wave's LDS window of products.
 #pragma once
 #include "common.h"

@@ -1208,7 +1208,7 @@ def test_deferred_x_update_on_every_exit_path(ctx, rs, defer_x, xbatch, monkeypa
 @pytest.mark.parametrize("N,kind,T", [(10, "aniso", "2"), (16, "poisson", "2"), (16, "poisson", "4"), (32, "convdiff", "2"), (40, "poisson", "4")])
 def test_direction_pass_inside_the_spmv_on_every_exit_path(ctx, rs, fuse, xbatch, N, kind, T, monkeypatch):
     """Round 5: on stencil operators in their staged CSR-P16 form CG / PCG form p = z + beta p_old INSIDE the next iteration's SpMV
-    (spmv.hip: spmv_pattern_fuse_kernel) and the deferred x += alpha p rides on the same pass -- two direction vectors alternate, the x
+    (spmv_fuse.hip: spmv_pattern_fuse_kernel) and the deferred x += alpha p rides on the same pass -- two direction vectors alternate, the x
     update of iteration k is paid by the fused SpMV of iteration k + 1 or, when none follows, by a flush at the end.  KRYST_CG_FUSE_P=0 is
     the unfused form.  Both must leave iteration counts, histories and x as the oracle does on every way out: convergence (the device runs
     ahead of the host: fused SpMVs enqueued behind the final iteration must pay the owed update exactly once), the iteration cap (1, 2, 3,

@@ -1,4 +1,4 @@
-"""CG without a stored Ap (KRYST_CG_RECOMPUTE_AP; spmv.hip: cg_recompute_residual_kernel, spmv_pattern_fuse_kernel<.., MARCH, YS = false>).
+"""CG without a stored Ap (KRYST_CG_RECOMPUTE_AP; spmv_fuse.hip: cg_recompute_residual_kernel, spmv_pattern_fuse_kernel<.., MARCH, YS = false>).
 
 In a fused iteration with x in batches the marching kernel stores p_new only, and the residual pass forms A p again from p_new -- the doubles
 the fused kernel had in its windows, the same arithmetic -- before r -= alpha Ap and the (r, r) partials.  Nothing but the traffic changes, so

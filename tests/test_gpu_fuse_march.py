@@ -1,4 +1,4 @@
-"""The marching mode of the fused direction + SpMV kernel of CG / PCG (spmv.hip: spmv_pattern_fuse_kernel<.., MARCH>).
+"""The marching mode of the fused direction + SpMV kernel of CG / PCG (spmv_fuse.hip: spmv_pattern_fuse_kernel<.., MARCH>).
 
 A workgroup keeps a strip of 512 T rows of a grid plane and walks a segment of S planes; the operands one plane away come out of its own
 LDS windows (below: the lane's own pair of the previous step, in registers; above: the next plane's window) and only the first and the last

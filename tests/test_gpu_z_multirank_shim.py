@@ -81,7 +81,7 @@ def test_multirank_on_one_gpu(tmp_path, P, N, kind, hostgen):
     # (not between rank THREADS that share the device -- refused by design, see dist.cpp: ipc_map_peers -- the 5-process cases cover more ranks)
     assert all(int(r["peer_active"][0]) == (0 if per > 1 else 1) for r in R), "the peer-store halo exchange could not be set up between the ranks of this box"
     # round 5: a context of several ranks and a new row-partitioned operator START on the hipIpc forms when their set-up and their checked
-    # test reduction / test exchange succeed on every rank (ctx.cpp: kryst_ctx_create_dist, spmv.hip: halo_default_mode)
+    # test reduction / test exchange succeed on every rank (ctx.cpp: kryst_ctx_create_dist, halo.hip: halo_default_mode)
     # (rank threads that share the device: the mailboxes' checked test reduction may or may not find the sibling's kernel on another hardware
     # queue -- but its verdict is agreed, so every rank starts on the same path)
     assert len({int(r["default_scalar_ipc"][0]) for r in R}) == 1, "the ranks started on different scalar all-reduce paths"
