@@ -270,3 +270,29 @@ extern "C" {
     pub fn kryst_pcg_solve_multi(b: *const f64, x: *mut f64, n: i64, k: i32, ld: i64, a: Csr, pc: Pc, params: *const Params,
                                  stats: *mut Stats, status: *mut i32, hist: *mut f64, hist_cap: i64, hist_len: *mut i64) -> i32;
 }
+
+// mixed precision: fp32 as a storage format (fp64 arithmetic and scalars), CG / Jacobi-PCG on it and fp64 iterative refinement around them
+pub type Vec32 = *mut c_void;
+pub type Csr32 = *mut c_void;
+extern "C" {
+    pub fn kryst_reduce_spec32(t: *mut i32, v: *mut i32, f: *mut i32);
+    pub fn kryst_vec32_create(ctx: Ctx, n: i64, out: *mut Vec32) -> i32;
+    pub fn kryst_vec32_destroy(v: Vec32) -> i32;
+    pub fn kryst_vec32_upload(v: Vec32, host: *const f32, n: i64) -> i32;
+    pub fn kryst_vec32_download(v: Vec32, host: *mut f32, n: i64) -> i32;
+    pub fn kryst_vec32_from_f64(dst: Vec32, src: Vecd) -> i32;
+    pub fn kryst_vec32_to_f64(dst: Vecd, src: Vec32) -> i32;
+    pub fn kryst_dot32(x: Vec32, y: Vec32, out: *mut f64) -> i32;
+    pub fn kryst_csr32_lower(a: Csr, out: *mut Csr32) -> i32;
+    pub fn kryst_csr32_info(a: Csr32, info: *mut i64) -> i32;
+    pub fn kryst_csr32_destroy(a: Csr32) -> i32;
+    pub fn kryst_host_round_f32(v: *const f64, n: i64, out: *mut f32, info: *mut i64) -> i32;
+    pub fn kryst_spmv32(a: Csr32, x: Vec32, y: Vec32) -> i32;
+    pub fn kryst_cg32_solve_dev(b: Vec32, x: Vec32, a: Csr32, pc: Pc, params: *const Params, stats: *mut Stats, hist: *mut f64,
+                                hist_cap: i64, hist_len: *mut i64) -> i32;
+    pub fn kryst_pcg32_solve_dev(b: Vec32, x: Vec32, a: Csr32, pc: Pc, params: *const Params, stats: *mut Stats, hist: *mut f64,
+                                 hist_cap: i64, hist_len: *mut i64) -> i32;
+    pub fn kryst_refine_solve_dev(b: Vecd, x: Vecd, a: Csr, a32: Csr32, pc: Pc, outer: *const Params, inner: *const Params,
+                                  stats: *mut Stats, hist: *mut f64, hist_cap: i64, hist_len: *mut i64, inner_iters: *mut i64,
+                                  inner_cap: i64) -> i32;
+}

@@ -676,6 +676,66 @@ int32_t kryst_pcg_solve_multi(const double* b, double* x, int64_t n, int32_t k, 
                               const kryst_params_t* params, kryst_stats_t* stats, int32_t* status, double* hist, int64_t hist_cap,
                               int64_t* hist_len);
 
+/* ---- mixed precision: fp32 as a STORAGE format, and fp64 iterative refinement on top of it ----
+ * A LABELLED DEVIATION from the reference at T = f32 (CsrMatrix<f32>, CgSolver<f32>, `T: Float`), which would round every operation: here
+ * fp32 is how vector elements and matrix values are STORED.  Every kernel widens what it loads, computes in fp64 in the fixed order of its
+ * fp64 twin (separate multiply and add) and rounds once -- (float), round to nearest even, fp32 subnormals kept -- when it stores; every
+ * scalar (alpha, beta, the inner products, the residual norms, the exits) is fp64 and is the fp64 solver's own code.  One rank; plain CSR
+ * arrays only; nothing here runs unless it is called. */
+typedef struct kryst_vec32_s* kryst_vec32_t;
+typedef struct kryst_csr32_s* kryst_csr32_t;
+/* kryst_reduce_spec for fp32-stored vectors: T = 256 threads own V = 4 consecutive elements each (a 1024-element tile, one 16-byte access
+ * per lane); a term is (double)a * (double)b, exact; the thread folds its 4 terms in index order from 0.0, then the tree of
+ * kryst_reduce_spec with the library's F. */
+void    kryst_reduce_spec32(int32_t* T, int32_t* V, int32_t* F);
+/* V = Vec<f32> of core/wrappers.rs on the device: ceil(n / 1024) * 1024 + 1024 floats, zero at creation (kryst_vec_create's rule at the fp32
+ * tile size); upload / download move n floats (kryst_vec_upload / _download) */
+int32_t kryst_vec32_create(kryst_ctx_t ctx, int64_t n, kryst_vec32_t* out);
+int32_t kryst_vec32_destroy(kryst_vec32_t v);
+int32_t kryst_vec32_upload(kryst_vec32_t v, const float* host, int64_t n);
+int32_t kryst_vec32_download(kryst_vec32_t v, float* host, int64_t n);
+/* dst[i] = (float)src[i] (rounds) / dst[i] = (double)src[i] (widens, exact), on the device; lengths must agree */
+int32_t kryst_vec32_from_f64(kryst_vec32_t dst, kryst_vec_t src);
+int32_t kryst_vec32_to_f64(kryst_vec_t dst, kryst_vec32_t src);
+/* InnerProduct::dot (wrappers.rs:90-108) on fp32-stored vectors: fp64 terms and sums in the tree of kryst_reduce_spec32 */
+int32_t kryst_dot32(kryst_vec32_t x, kryst_vec32_t y, double* out);
+/* CsrMatrix<f32> from a CsrMatrix<f64> (sparse.rs:22-46): device-to-device COPIES of the operator's row pointers and columns and its values
+ * rounded to fp32 on the device (nnz + 8 entries, zeroed tail) -- no lifetime tie to `a`.  REFUSED with KRYST_UNSUPPORTED, nothing
+ * created: a finite value that would round to +-inf; a distributed operator.  A non-square operator is accepted (kryst_spmv32 handles it,
+ * the solvers refuse it). */
+int32_t kryst_csr32_lower(kryst_csr_t a, kryst_csr32_t* out);
+/* info[0]: values the rounding changed; info[1]: nonzero values that became zero or fp32-subnormal; info[2]: rows */
+int32_t kryst_csr32_info(kryst_csr32_t a, int64_t info[3]);
+int32_t kryst_csr32_destroy(kryst_csr32_t a);
+/* host twin of the lowering's rounding, no GPU: out[i] = (float)v[i], info[0] / info[1] as kryst_csr32_info (info may be NULL);
+ * KRYST_UNSUPPORTED when a finite value rounds to +-inf (the verdict of kryst_csr32_lower) */
+int32_t kryst_host_round_f32(const double* v, int64_t n, float* out, int64_t info[2]);
+/* SparseMatrix::spmv (sparse.rs:56-67, the row loop of :107-113 on widened operands): y[i] = (float) of the fold from 0.0, in stored
+ * (ascending column) order, of (double)val * (double)x[col].  x and y the same vector: KRYST_ERR_ARG before any launch. */
+int32_t kryst_spmv32(kryst_csr32_t a, kryst_vec32_t x, kryst_vec32_t y);
+/* CgSolver::solve (cg.rs:114-288) / PcgSolver::solve (pcg.rs:114-222) on fp32-stored vectors and operator, with the scalar steps and exits
+ * of kryst_cg_solve_dev / kryst_pcg_solve_dev: x = (float)(x + alpha p), r = (float)(r - alpha Ap), p = (float)(z + beta p),
+ * z = (float)(dinv r); three launches per iteration.  x is written once, at the end, and only on KRYST_OK; b and x may be the same vector.
+ * kryst_cg32_solve_dev ignores pc (cg.rs:115); kryst_pcg32_solve_dev takes NULL, Identity or Jacobi (jacobi.rs:84-86, its inverse
+ * diagonal rounded to fp32 once per solve).  KRYST_UNSUPPORTED, nothing written: any other preconditioner kind, norm_type outside {0, 1},
+ * has_radius, has_obj_target, a non-square operator.  No monitor, no stepping session; one solve per context at a time (KRYST_ERR_BUSY). */
+int32_t kryst_cg32_solve_dev(kryst_vec32_t b, kryst_vec32_t x, kryst_csr32_t a, kryst_pc_t pc, const kryst_params_t* params,
+                             kryst_stats_t* stats, double* hist, int64_t hist_cap, int64_t* hist_len);
+int32_t kryst_pcg32_solve_dev(kryst_vec32_t b, kryst_vec32_t x, kryst_csr32_t a, kryst_pc_t pc, const kryst_params_t* params,
+                              kryst_stats_t* stats, double* hist, int64_t hist_cap, int64_t* hist_len);
+/* fp64 iterative refinement around the fp32 solvers (an extension: the reference has no counterpart; it stands beside LinearSolver::solve,
+ * src/solver/mod.rs:43-49).  Outer work in fp64 with kryst_spmv's own kernel for `a`: r = b - A x, rho0 = ||r|| (pushed to hist); for
+ * k = 1 .. outer->max_iters: solve a32 c = (float)(r / rho) from c = 0 with kryst_cg32 (pc NULL / Identity) or kryst_pcg32 (Jacobi) under
+ * `inner` (its iteration count goes to inner_iters[k - 1] while k - 1 < inner_cap); an inner error status is returned as it is, x untouched,
+ * iterations = k - 1; x' = x + rho * (double)c, rho' = ||b - A x'|| (pushed); !(rho' < rho): the step is REJECTED -- x stays the last
+ * accepted iterate, iterations = k, converged = 0, final_residual = rho, KRYST_OK; else accepted and Convergence::check(rho, rho0, k)
+ * (convergence.rs:18-34: reaching the cap reports converged).  outer->max_iters <= 0 or rho0 == 0: KRYST_OK, converged = 1, x untouched.
+ * a32 must be the lowering of an operator of a's shape (KRYST_ERR_ARG); refusals as the fp32 solvers'.  stats, hist, hist_len, inner_iters
+ * may be NULL.  The host reads one scalar per outer step. */
+int32_t kryst_refine_solve_dev(kryst_vec_t b, kryst_vec_t x, kryst_csr_t a, kryst_csr32_t a32, kryst_pc_t pc, const kryst_params_t* outer,
+                               const kryst_params_t* inner, kryst_stats_t* stats, double* hist, int64_t hist_cap, int64_t* hist_len,
+                               int64_t* inner_iters, int64_t inner_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@
 // Rust's assert_eq! panics on length mismatches become KError{ArgumentError}.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <functional>
 #include <memory>
 #include <optional>
@@ -764,6 +765,70 @@ public:
         check(kryst_qr_solve(a.handle(), nullptr, b.data(), x.data(), (int64_t)b.size(), &st));
         return {(size_t)st.iterations, st.final_residual, st.converged != 0};
     }
+};
+
+// ---- mixed precision (an extension): fp32 as a storage format, fp64 arithmetic and scalars -------------------------
+// CsrMatrix<f32> lowered from a HipCsrMatrix: copies of its index arrays, its values rounded to fp32 on the device
+class HipCsrMatrix32 {
+public:
+    explicit HipCsrMatrix32(const HipCsrMatrix& a) : ctx_(a.context()) { check(kryst_csr32_lower(a.handle(), &h_)); }
+    HipCsrMatrix32(HipCsrMatrix32&& o) noexcept : ctx_(std::move(o.ctx_)), h_(o.h_) { o.h_ = nullptr; }
+    HipCsrMatrix32(const HipCsrMatrix32&) = delete; HipCsrMatrix32& operator=(const HipCsrMatrix32&) = delete;
+    ~HipCsrMatrix32() { if (h_) kryst_csr32_destroy(h_); }
+    // {values the rounding changed, nonzero values that became zero or fp32-subnormal, rows}
+    std::array<int64_t, 3> info() const { std::array<int64_t, 3> i{}; check(kryst_csr32_info(h_, i.data())); return i; }
+    void spmv(const std::vector<float>& x, std::vector<float>& y) const {        // sparse.rs:56-67 on fp32 storage
+        kryst_vec32_t xv = nullptr, yv = nullptr;
+        int32_t rc = kryst_vec32_create(ctx_->handle(), (int64_t)x.size(), &xv);
+        if (rc == 0) rc = kryst_vec32_create(ctx_->handle(), (int64_t)y.size(), &yv);
+        if (rc == 0) rc = kryst_vec32_upload(xv, x.data(), (int64_t)x.size());
+        if (rc == 0) rc = kryst_spmv32(h_, xv, yv);
+        if (rc == 0) rc = kryst_vec32_download(yv, y.data(), (int64_t)y.size());
+        if (xv) kryst_vec32_destroy(xv);
+        if (yv) kryst_vec32_destroy(yv);
+        check(rc);
+    }
+    kryst_csr32_t handle() const { return h_; }
+private:
+    std::shared_ptr<Context> ctx_; kryst_csr32_t h_ = nullptr;
+};
+
+// fp64 iterative refinement around CG / Jacobi-PCG on the lowered operator (kryst_refine_solve_dev); pc: none, Identity or Jacobi
+class RefinementSolver : public LinearSolver<HipCsrMatrix, Vec> {
+public:
+    RefinementSolver(double tol, size_t max_outer) : conv{tol, max_outer} {}
+    RefinementSolver& with_inner(double tol, size_t max_iters) { inner = {tol, max_iters}; return *this; }
+    SolveStats<double> solve(const HipCsrMatrix& a, const Preconditioner<HipCsrMatrix, Vec>* pc, const Vec& b, Vec& x) override {
+        if (b.size() != x.size()) throw KError(KRYST_ERR_ARG);
+        const HipCsrMatrix32 a32(a);
+        kryst_params_t po{}, pi{};
+        po.tol = conv.tol; po.max_iters = (int64_t)conv.max_iters; po.norm_type = 1;
+        pi.tol = inner.tol; pi.max_iters = (int64_t)inner.max_iters; pi.norm_type = 1;
+        const size_t cap = conv.max_iters + 2;
+        residual_history.assign(cap, 0.0);
+        inner_iterations.assign(conv.max_iters, 0);
+        int64_t hlen = 0;
+        kryst_stats_t st{};
+        kryst_ctx_t c = a.context()->handle();
+        kryst_vec_t bv = nullptr, xv = nullptr;
+        int32_t rc = kryst_vec_create(c, (int64_t)b.size(), &bv);
+        if (rc == 0) rc = kryst_vec_create(c, (int64_t)x.size(), &xv);
+        if (rc == 0) rc = kryst_vec_upload(bv, b.data(), (int64_t)b.size());
+        if (rc == 0) rc = kryst_vec_upload(xv, x.data(), (int64_t)x.size());
+        if (rc == 0) rc = kryst_refine_solve_dev(bv, xv, a.handle(), a32.handle(), pc ? pc->device_handle() : nullptr, &po, &pi, &st,
+                                                 residual_history.data(), (int64_t)cap, &hlen, inner_iterations.data(), (int64_t)inner_iterations.size());
+        if (rc == 0) rc = kryst_vec_download(xv, x.data(), (int64_t)x.size());
+        if (bv) kryst_vec_destroy(bv);
+        if (xv) kryst_vec_destroy(xv);
+        check(rc);
+        residual_history.resize(std::min(cap, (size_t)hlen));
+        inner_iterations.resize(residual_history.empty() ? 0 : std::min(inner_iterations.size(), residual_history.size() - 1));
+        return {(size_t)st.iterations, st.final_residual, st.converged != 0};
+    }
+    Convergence<double> conv;
+    Convergence<double> inner{1e-6, 1000};
+    Vec residual_history;
+    std::vector<int64_t> inner_iterations;
 };
 
 }  // namespace kryst

@@ -11,6 +11,7 @@ behaviour (paths relative to the kryst crate):
     apply_chebyshev(a, r, z, alpha, beta, m)                        src/preconditioner/chebyshev.rs:83-140
     CgSolver / PcgSolver / GmresSolver / BiCgStabSolver .solve(a, pc, b, x) -> SolveStats   src/solver/*.rs
     MultiVec, CsrMatrix.spmm(X, Y), CgSolver / PcgSolver .solve_many(a, pc, B, X)           several right-hand sides at once (extension)
+    DeviceVec32, CsrMatrix.lower() -> CsrMatrix32, Cg32Solver / Pcg32Solver, RefinementSolver   fp32 storage + fp64 refinement (extension)
     DenseMatrix.from_raw(nrows, ncols, data) .matvec(x, y)          src/matrix/dense.rs:16-25, core/wrappers.rs:27-38
     LuSolver / QrSolver .solve(a, pc, b, x), LuSolver.solve_cached  src/solver/direct_lu.rs
     Convergence, SolveStats, KError, CgNormType, Preconditioning    src/utils/convergence.rs, src/error.rs
@@ -30,7 +31,8 @@ __all__ = ["Context", "DeviceVec", "CsrMatrix", "dot", "norm", "Jacobi", "Ilu0",
            "Preconditioning", "CgSolver", "PcgSolver", "GmresSolver", "FgmresSolver", "PcaGmresSolver", "Orthog", "CgsSolver", "TfqmrSolver", "MinresSolver", "QmrSolver", "CgnrSolver", "CgneSolver", "BiCgStabSolver", "BiCgStabRightPcSolver", "Session", "KspContext", "SolverKind", "PC", "KError", "reduce_spec",
            "host_stencil7", "partition_rows", "halo_recv_plan", "read_matrix_market", "read_petsc_binary", "host_ilup", "host_ilut", "host_amg", "host_levels", "color_graph", "build_blocks_from_colors",
            "DenseMatrix", "LuSolver", "QrSolver", "host_dense_lu", "host_dense_lu_solve", "host_dense_qr_solve",
-           "MultiVec", "split_widths"]
+           "MultiVec", "split_widths",
+           "DeviceVec32", "CsrMatrix32", "dot32", "Cg32Solver", "Pcg32Solver", "RefinementSolver", "reduce_spec32", "host_round_f32"]
 
 
 def _dp(a):
@@ -283,6 +285,126 @@ class MultiVec:
             pass
 
 
+def _fp(a):
+    return a.ctypes.data_as(_ffi.c_fp)
+
+
+def reduce_spec32():
+    """(T, V, F) of the inner-product tree of fp32-stored vectors (kryst_reduce_spec32): 256 threads x 4 elements per tile."""
+    t, v, f = C.c_int32(), C.c_int32(), C.c_int32()
+    lib().kryst_reduce_spec32(C.byref(t), C.byref(v), C.byref(f))
+    return t.value, v.value, f.value
+
+
+def host_round_f32(values):
+    """The rounding of CsrMatrix.lower() on the host, no GPU (kryst_host_round_f32) -> (float32 array, changed, tiny): the values the
+    rounding changed and the nonzero values that became zero or fp32-subnormal.  A finite value that would round to +-inf raises
+    KError Unsupported, as lower() does."""
+    v = _f64(values).ravel()
+    out = np.empty(len(v), dtype=np.float32)
+    info = (C.c_int64 * 2)()
+    check(lib().kryst_host_round_f32(_dp(v), len(v), _fp(out), info))
+    return out, info[0], info[1]
+
+
+class DeviceVec32:
+    """A Vec<f32> resident in HBM (kryst_vec32_t): fp32 is how the elements are stored, every kernel computes in fp64."""
+
+    def __init__(self, ctx, n_or_array):
+        self.ctx = ctx
+        self.h = _ffi.Handle()
+        if np.isscalar(n_or_array):
+            self.n = int(n_or_array)
+            check(lib().kryst_vec32_create(ctx.h, self.n, C.byref(self.h)))
+        else:
+            a = np.ascontiguousarray(n_or_array, dtype=np.float32)
+            self.n = len(a)
+            check(lib().kryst_vec32_create(ctx.h, self.n, C.byref(self.h)))
+            self.upload(a)
+
+    def __len__(self):
+        return self.n
+
+    def upload(self, a):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        check(lib().kryst_vec32_upload(self.h, _fp(a), len(a)))
+        return self
+
+    def to_host(self):
+        out = np.empty(self.n, dtype=np.float32)
+        check(lib().kryst_vec32_download(self.h, _fp(out), self.n))
+        return out
+
+    @staticmethod
+    def from_f64(v):
+        """(float)v[i] of a DeviceVec, rounded on the device."""
+        out = DeviceVec32(v.ctx, v.n)
+        check(lib().kryst_vec32_from_f64(out.h, v.h))
+        return out
+
+    def to_f64(self, out=None):
+        """(double)self[i] as a DeviceVec, widened on the device."""
+        out = DeviceVec(self.ctx, self.n) if out is None else out
+        check(lib().kryst_vec32_to_f64(out.h, self.h))
+        return out
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                lib().kryst_vec32_destroy(self.h)
+        except Exception:
+            pass
+
+
+def dot32(x, y):
+    """InnerProduct::dot on fp32-stored device vectors: exact fp64 terms folded in the tree of reduce_spec32()."""
+    out = C.c_double()
+    check(lib().kryst_dot32(x.h, y.h, C.byref(out)))
+    return out.value
+
+
+class CsrMatrix32:
+    """CsrMatrix<f32> lowered from a CsrMatrix (kryst_csr32_lower): its own copies of the index arrays, the values rounded to fp32."""
+
+    def __init__(self, a):
+        self.ctx = a.ctx
+        self.h = _ffi.Handle()
+        check(lib().kryst_csr32_lower(a.h, C.byref(self.h)))
+        self._nrows, self._ncols, self.nnz = a.nrows(), a.ncols(), a.nnz
+
+    def nrows(self):
+        return self._nrows
+
+    def ncols(self):
+        return self._ncols
+
+    @property
+    def info(self):
+        """{"changed", "tiny", "rows"}: values the rounding changed, nonzero values that became zero or fp32-subnormal, rows."""
+        i = (C.c_int64 * 3)()
+        check(lib().kryst_csr32_info(self.h, i))
+        return {"changed": i[0], "tiny": i[1], "rows": i[2]}
+
+    def spmv(self, x, y=None):
+        """y <- (float)(A x): the row fold in fp64 over the stored order, rounded once.  DeviceVec32 stays on the device; a host array is
+        converted to float32 and round-trips."""
+        if isinstance(x, DeviceVec32):
+            if y is None:
+                y = DeviceVec32(self.ctx, self._nrows)
+            check(lib().kryst_spmv32(self.h, x.h, y.h))
+            return y
+        xv, yv = DeviceVec32(self.ctx, x), DeviceVec32(self.ctx, self._nrows)
+        check(lib().kryst_spmv32(self.h, xv.h, yv.h))
+        return yv.to_host()
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                lib().kryst_csr32_destroy(self.h)
+        except Exception:
+            pass
+
+
 def dot(x, y):
     """InnerProduct::dot (wrappers.rs:90-108) on device vectors."""
     out = C.c_double()
@@ -443,6 +565,10 @@ class CsrMatrix:
                 out[:, at:at + w] = self.spmm(MultiVec.from_numpy(xa[:, at:at + w], ctx=self.ctx)).to_numpy()
             at += w
         return out
+
+    def lower(self):
+        """This operator with fp32-stored values (CsrMatrix32; an extension): a copy, with no tie to this one's lifetime."""
+        return CsrMatrix32(self)
 
     ENCODINGS = ("csr", "csr-d8", "csr-d16", "csr-p16", "csr-dia")
 
@@ -1434,6 +1560,102 @@ class PcgSolver(_Solver):
     """PcgSolver::new(tol, max_iters)  src/solver/pcg.rs:31-91,114-222."""
     _HOST, _DEV = "kryst_pcg_solve", "kryst_pcg_solve_dev"
     _MULTI_DEV = "kryst_pcg_solve_multi_dev"
+
+
+class _Solver32(_Solver):
+    """CG / PCG on fp32-stored vectors and a lowered operator (an extension; fp64 arithmetic, scalars and exits).  solve(a32, pc, b, x):
+    a32 a CsrMatrix32; b, x DeviceVec32 (x in/out on the device) or arrays (x a float32 array written in place on success)."""
+    _DEV32 = None
+
+    def solve(self, a, pc, b, x):
+        prm = self._params()
+        st = _ffi.Stats()
+        cap = min(self.conv.max_iters + 8, (1 << 22) + 8)
+        hist = np.zeros(cap)
+        hlen = C.c_int64(0)
+        pch = pc.h if pc is not None else None
+        if pc is not None and pch is None:
+            raise KError(2, "preconditioner used before setup")
+        host = not isinstance(b, DeviceVec32)
+        if host:
+            if not (isinstance(x, np.ndarray) and x.dtype == np.float32 and x.flags.c_contiguous):
+                raise KError(102, "x must be a contiguous float32 numpy array (it is written in place)")
+        bv = DeviceVec32(a.ctx, b) if host else b
+        xv = DeviceVec32(a.ctx, x) if host else x
+        rc = getattr(lib(), self._DEV32)(bv.h, xv.h, a.h, pch, C.byref(prm), C.byref(st), _dp(hist), cap, C.byref(hlen))
+        if host and rc == 0:
+            x[:] = xv.to_host()
+        self.residual_history.extend(hist[:min(hlen.value, cap)].tolist())
+        stats = SolveStats(st.iterations, st.final_residual, bool(st.converged))
+        check(rc, stats)
+        return stats
+
+
+class Cg32Solver(_Solver32):
+    """CgSolver::new(tol, max_iters) on fp32 storage (kryst_cg32_solve_dev; pc is ignored, cg.rs:115)."""
+    _DEV32 = "kryst_cg32_solve_dev"
+
+
+class Pcg32Solver(_Solver32):
+    """PcgSolver::new(tol, max_iters) on fp32 storage (kryst_pcg32_solve_dev; pc: None, IdentityPc or Jacobi)."""
+    _DEV32 = "kryst_pcg32_solve_dev"
+
+
+class RefinementSolver:
+    """fp64 iterative refinement around CG (pc None / Identity) or Jacobi-PCG on the fp32-stored operator (kryst_refine_solve_dev; an
+    extension).  RefinementSolver(tol, max_outer).with_inner(tol, max_iters); solve(a, pc, b, x) lowers `a` on first use and keeps the
+    lowered operator per operator object; the SolveStats it returns carries .inner_iterations (one count per outer step taken)."""
+
+    def __init__(self, tol, max_outer):
+        self.conv = Convergence(tol, max_outer)
+        self.inner = Convergence(1e-6, 1000)
+        self.residual_history = []
+        self._lowered = {}
+
+    def with_inner(self, tol, max_iters):
+        self.inner = Convergence(tol, max_iters)
+        return self
+
+    def clear_history(self):
+        self.residual_history.clear()
+
+    def lowered(self, a):
+        key = id(a)
+        hit = self._lowered.get(key)
+        if hit is None or hit[0] is not a:
+            hit = (a, a.lower())
+            self._lowered[key] = hit
+        return hit[1]
+
+    def solve(self, a, pc, b, x):
+        pch = pc.h if pc is not None else None
+        if pc is not None and pch is None:
+            raise KError(2, "preconditioner used before setup")
+        a32 = self.lowered(a)
+        un = int(CgNormType.Unpreconditioned)
+        po = _ffi.Params(self.conv.tol, self.conv.max_iters, 0, 0, un, 0, 0, 0.0, 0, 0.0, 0)
+        pi = _ffi.Params(self.inner.tol, self.inner.max_iters, 0, 0, un, 0, 0, 0.0, 0, 0.0, 0)
+        st = _ffi.Stats()
+        steps = min(max(int(self.conv.max_iters), 0), 1 << 20)      # outer steps recorded (the count of residuals still runs on)
+        cap = steps + 2
+        hist = np.zeros(cap)
+        hlen = C.c_int64(0)
+        inner = np.full(max(steps, 1), -1, dtype=np.int64)
+        host = not isinstance(b, DeviceVec)
+        if host and not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.flags.c_contiguous):
+            raise KError(102, "x must be a contiguous float64 numpy array (it is written in place)")
+        bv = DeviceVec(a.ctx, b) if host else b
+        xv = DeviceVec(a.ctx, x) if host else x
+        rc = lib().kryst_refine_solve_dev(bv.h, xv.h, a.h, a32.h, pch, C.byref(po), C.byref(pi), C.byref(st), _dp(hist), cap,
+                                          C.byref(hlen), inner.ctypes.data_as(_ffi.c_i64p), steps)
+        if host and rc == 0:
+            x[:] = xv.to_host()
+        pushed = min(hlen.value, cap)
+        self.residual_history.extend(hist[:pushed].tolist())
+        stats = SolveStats(st.iterations, st.final_residual, bool(st.converged))
+        stats.inner_iterations = inner[inner >= 0].tolist()        # one count per inner solve that ran (its last one may have ended in an error)
+        check(rc, stats)
+        return stats
 
 
 class GmresSolver(_Solver):

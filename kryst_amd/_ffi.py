@@ -13,6 +13,7 @@ ERR_NAMES = {1: "FactorError", 2: "SolveError", 3: "IndefiniteMatrix", 4: "Indef
              103: "CsrError", 104: "ContextBusy"}
 
 c_dp = C.POINTER(C.c_double)
+c_fp = C.POINTER(C.c_float)
 c_i64p = C.POINTER(C.c_int64)
 c_u64p = C.POINTER(C.c_uint64)
 c_i32p = C.POINTER(C.c_int32)
@@ -34,6 +35,8 @@ class Stats(C.Structure):
 _SOLVE_TAIL = [Handle, Handle, C.POINTER(Params), C.POINTER(Stats), c_dp, C.c_int64, c_i64p, MONITOR, C.c_void_p]
 # the batched solves: operator, pc, params, stats[k], status[k], hist (k slices of hist_cap), hist_cap, hist_len[k]
 _MULTI_TAIL = [Handle, Handle, C.POINTER(Params), C.POINTER(Stats), c_i32p, c_dp, C.c_int64, c_i64p]
+# the fp32-stored solves: lowered operator, pc, params, stats, hist, hist_cap, hist_len (no monitor)
+_SOLVE32_TAIL = [Handle, Handle, C.POINTER(Params), C.POINTER(Stats), c_dp, C.c_int64, c_i64p]
 
 # name -> (restype, argtypes): every symbol include/kryst_hip.h declares
 SIGNATURES = {
@@ -204,6 +207,23 @@ SIGNATURES = {
     "kryst_pcg_solve_multi_dev": (C.c_int32, [Handle, Handle] + _MULTI_TAIL),
     "kryst_cg_solve_multi": (C.c_int32, [c_dp, c_dp, C.c_int64, C.c_int32, C.c_int64] + _MULTI_TAIL),
     "kryst_pcg_solve_multi": (C.c_int32, [c_dp, c_dp, C.c_int64, C.c_int32, C.c_int64] + _MULTI_TAIL),
+    "kryst_reduce_spec32": (None, [c_i32p, c_i32p, c_i32p]),
+    "kryst_vec32_create": (C.c_int32, [Handle, C.c_int64, C.POINTER(Handle)]),
+    "kryst_vec32_destroy": (C.c_int32, [Handle]),
+    "kryst_vec32_upload": (C.c_int32, [Handle, c_fp, C.c_int64]),
+    "kryst_vec32_download": (C.c_int32, [Handle, c_fp, C.c_int64]),
+    "kryst_vec32_from_f64": (C.c_int32, [Handle, Handle]),
+    "kryst_vec32_to_f64": (C.c_int32, [Handle, Handle]),
+    "kryst_dot32": (C.c_int32, [Handle, Handle, c_dp]),
+    "kryst_csr32_lower": (C.c_int32, [Handle, C.POINTER(Handle)]),
+    "kryst_csr32_info": (C.c_int32, [Handle, c_i64p]),
+    "kryst_csr32_destroy": (C.c_int32, [Handle]),
+    "kryst_host_round_f32": (C.c_int32, [c_dp, C.c_int64, c_fp, c_i64p]),
+    "kryst_spmv32": (C.c_int32, [Handle, Handle, Handle]),
+    "kryst_cg32_solve_dev": (C.c_int32, [Handle, Handle] + _SOLVE32_TAIL),
+    "kryst_pcg32_solve_dev": (C.c_int32, [Handle, Handle] + _SOLVE32_TAIL),
+    "kryst_refine_solve_dev": (C.c_int32, [Handle, Handle, Handle, Handle, Handle, C.POINTER(Params), C.POINTER(Params), C.POINTER(Stats),
+                                           c_dp, C.c_int64, c_i64p, c_i64p, C.c_int64]),
 }
 
 _lib = None

@@ -1,0 +1,37 @@
+// Mixed precision: fp32 as a STORAGE format.  Vectors and matrix values are kept as floats; every kernel widens what
+// it loads, computes in fp64 in the fixed order of its fp64 twin and rounds once -- (float), round to nearest even -- when it stores.  Scalars,
+// inner products, DevState and the logic structs of cg_logic.h stay fp64 and are the fp64 solvers' own code.
+#pragma once
+#include "csr.h"
+
+// ---- the fp32 inner-product tree (kryst_reduce_spec32): a tile is 256 threads x 4 consecutive elements, one 16-byte access per array and lane ----
+#define KR32_T 256
+#define KR32_V 4
+#define KR32_TILE (KR32_T * KR32_V)
+
+struct kryst_vec32_s {
+    kryst_ctx_t ctx = nullptr;
+    int64_t n = 0;
+    float* d = nullptr;             // ceil(n / 1024) * 1024 + 1024 floats, zero at creation (kryst_vec_t's rule at the fp32 tile size)
+};
+
+// the lowered operator: copies of the fp64 operator's index arrays and its values rounded to fp32 -- no lifetime tie to the operator it came from
+struct kryst_csr32_s {
+    kryst_ctx_t ctx = nullptr;
+    int64_t nrows = 0, ncols = 0, nnz = 0;
+    int32_t* d_row_ptr = nullptr;   // nrows + 1
+    int32_t* d_col = nullptr;       // nnz + 8, zeroed tail
+    float* d_val = nullptr;         // nnz + 8, zeroed tail
+    int64_t changed = 0, tiny = 0;  // values the rounding changed / nonzero values that became zero or fp32-subnormal
+};
+
+namespace kr {
+
+inline int64_t ntiles32_of(int64_t n) { return (n + KR32_TILE - 1) / KR32_TILE; }
+inline int64_t vec32_len(int64_t n) { return ntiles32_of(n) * KR32_TILE + KR32_TILE; }      // allocated floats
+
+// y <- (float)(A x) on ctx->s_main; nq = 1: also the tile partials of sum_i d[i] * y[i] (y as stored) in the fp32 tree into partial array 0.
+// `done` (device flag) makes the launch a no-op when set.
+int32_t launch_spmv32(kryst_csr32_t a, const float* x, float* y, int nq, const float* dvec, const int* done);
+
+}  // namespace kr

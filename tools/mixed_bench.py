@@ -1,0 +1,239 @@
+#!/usr/bin/env python3
+"""Mixed precision, measured: one JSON line per case on stdout (and appended to --out FILE).  One GPU, one process.
+
+  mixed_bench.py spmv   N [--op poisson|varcoef|band]   kryst_spmv32 against the plain-CSR fp64 kryst_spmv, each as a fraction of 8 TB/s on its own bytes
+  mixed_bench.py rate   N [--op ...]                    CG32 / PCG32 iterations per second against fp64 CG / Jacobi-PCG on plain CSR and on the
+                                                        operator's default encoding, at the same capped iteration counts
+  mixed_bench.py refine N [--op ...] [--reps R]         time to tolerance: RefinementSolver (outer 1e-10, inner 1e-6) against fp64 CG / Jacobi-PCG to
+                                                        1e-10 on plain CSR and on the default encoding: outer steps, total inner iterations, ms
+
+The versions ALTERNATE inside the process after a warm-up; every timed window lasts at least half a second (spmv: a run of launches between
+two hipEvents; rate: the difference of two solves at IT and 3 IT iterations with tol = 0, wall clock, IT sized from a calibration solve so that
+2 IT iterations take >= 0.6 s; refine: whole solves, wall clock, lowering and first-use allocations taken out by a warm-up call).  Medians.
+
+Bytes, from shapes: fp64 plain-CSR SpMV 12 nnz + 4 (n + 1) + 16 n; spmv32 8 nnz + 4 (n + 1) + 8 n.  `band`: the non-stencil operator of
+tools/multi_rhs_only.py (seven entries per row at jittered offsets, no two rows alike: no compressed form applies)."""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import kryst_amd as K
+
+PEAK = 8.0e12
+WINDOW_S = 0.5
+OUT = None
+
+
+def emit(rec):
+    rec["sources"] = K._ffi.source_sha16()
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if OUT:
+        with open(OUT, "a") as f:
+            f.write(line + "\n")
+
+
+def band(N, ctx):
+    n = N ** 3
+    g = max(N * N // 4, 2)
+    rng = np.random.default_rng(1234)
+    base = np.array([-3 * g, -2 * g, -g, 0, g, 2 * g, 3 * g], dtype=np.int64)
+    rows = np.arange(n, dtype=np.int64)
+    jit = rng.integers(0, g, size=(n, 7), dtype=np.int64)
+    jit[:, 3] = 0
+    cols = rows[:, None] + base[None, :] + jit
+    vals = -0.5 * rng.random((n, 7))
+    vals[:, 3] = 8.0
+    valid = (cols >= 0) & (cols < n)
+    rp = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(valid.sum(axis=1), out=rp[1:])
+    return K.CsrMatrix.from_csr_i32(n, n, rp, cols[valid].astype(np.int32), vals[valid], ctx=ctx)
+
+
+def use(plain):
+    """which form of the operator the fp64 SpMV streams from now on: plain CSR (KRYST_SPMV_COMPRESS=0) or the library's own choice -- the
+    knob is read per launch outside a solve and once per solve inside one"""
+    if plain:
+        os.environ["KRYST_SPMV_COMPRESS"] = "0"
+    else:
+        os.environ.pop("KRYST_SPMV_COMPRESS", None)
+
+
+def operator(name, N, ctx):
+    return band(N, ctx) if name == "band" else K.CsrMatrix.stencil7(N, name, ctx=ctx)
+
+
+def encoding(a, plain):
+    use(plain)
+    e = a.encoding()[0]
+    assert not plain or e == "csr", e
+    return e
+
+
+def alternate(sides, reps):
+    got = {k: [] for k in sides}
+    for _ in range(reps):
+        for k, f in sides.items():
+            got[k].append(f())
+    return {k: statistics.median(v) for k, v in got.items()}
+
+
+# ---------------------------------------------------------------------------------------------------------------- SpMV
+def spmv_case(name, N, reps):
+    ctx = K.Context(0)
+    a = operator(name, N, ctx)
+    a32 = a.lower()
+    n, nnz = a.nrows(), a.nnz
+    encoding(a, True)                                      # plain CSR for the whole case
+    x, y = ctx.vec(n).fill_splitmix(3), ctx.vec(n)
+    x32, y32 = K.DeviceVec32.from_f64(x), K.DeviceVec32(ctx, n)
+
+    def window(fn, launches):
+        ctx.timer_start()
+        for _ in range(launches):
+            fn()
+        return ctx.timer_stop() / launches
+
+    f64, f32 = (lambda: a.spmv(x, y)), (lambda: a32.spmv(x32, y32))
+    count = {}
+    for k, fn in (("fp64", f64), ("fp32", f32)):
+        window(fn, 20)
+        count[k] = max(20, int(math.ceil(WINDOW_S * 1.2 / (window(fn, 50) * 1e-3))))
+    r = alternate({"fp64": lambda: window(f64, count["fp64"]), "fp32": lambda: window(f32, count["fp32"])}, reps)
+    b64, b32 = 12 * nnz + 4 * (n + 1) + 16 * n, 8 * nnz + 4 * (n + 1) + 8 * n
+    emit({"case": "spmv", "op": name, "N": N, "n": n, "nnz": nnz, "windows": reps, "launches_per_window": count, "info": a32.info,
+          "spmv_fp64_plain_csr_ms": round(r["fp64"], 5), "spmv32_ms": round(r["fp32"], 5),
+          "bytes_fp64": b64, "bytes_fp32": b32, "bytes_per_row_fp64": round(b64 / n, 2), "bytes_per_row_fp32": round(b32 / n, 2),
+          "fp64_frac_8TBps": round(b64 / (r["fp64"] * 1e-3) / PEAK, 4), "fp32_frac_8TBps": round(b32 / (r["fp32"] * 1e-3) / PEAK, 4),
+          "time_ratio_fp64_over_fp32": round(r["fp64"] / r["fp32"], 3), "byte_ratio_fp64_over_fp32": round(b64 / b32, 3)})
+
+
+# ---------------------------------------------------------------------------------------------------------------- iteration rate
+def rate_case(name, N, reps):
+    ctx = K.Context(0)
+    plain = dflt = operator(name, N, ctx)                   # one operator, streamed in either form
+    a32 = plain.lower()
+    n = plain.nrows()
+    default_encoding = encoding(dflt, False)
+    b = plain.spmv(ctx.vec(n).fill(1.0))
+    b32 = K.DeviceVec32.from_f64(b)
+    x, x32 = ctx.vec(n), K.DeviceVec32(ctx, n)
+    zero32 = np.zeros(n, dtype=np.float32)
+    for method, cls64, cls32 in (("cg", K.CgSolver, K.Cg32Solver), ("pcg_jacobi", K.PcgSolver, K.Pcg32Solver)):
+        pcs = {"plain": K.Jacobi().setup(plain), "default": K.Jacobi().setup(dflt)} if method != "cg" else {"plain": None, "default": None}
+
+        def timed(kind, iters):
+            use(kind == "fp64_plain")
+            if kind == "fp32":
+                x32.upload(zero32)
+            else:
+                x.fill(0.0)
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            if kind == "fp32":
+                st = cls32(0.0, iters).solve(a32, pcs["plain"], b32, x32)
+            else:
+                st = cls64(0.0, iters).solve(plain if kind == "fp64_plain" else dflt, pcs["plain" if kind == "fp64_plain" else "default"], b, x)
+            return time.perf_counter() - t0, st.iterations
+
+        rec = {"case": "rate", "op": name, "N": N, "n": n, "method": method, "windows": reps, "default_encoding": default_encoding}
+        kinds = ("fp32", "fp64_plain", "fp64_default")
+        its, lo, hi = {}, {k: [] for k in kinds}, {k: [] for k in kinds}
+        for kind in kinds:                                   # calibration: IT such that 2 IT iterations take >= 0.6 s
+            timed(kind, 10)
+            per = max((timed(kind, 60)[0] - timed(kind, 20)[0]) / 40, 1e-6)
+            its[kind] = max(20, int(math.ceil(0.3 / per)))
+        for _ in range(reps):                                # the versions alternate
+            for kind in kinds:
+                lo[kind].append(timed(kind, its[kind]))
+                hi[kind].append(timed(kind, 3 * its[kind]))
+        for kind in kinds:
+            t_lo, t_hi = statistics.median(t for t, _ in lo[kind]), statistics.median(t for t, _ in hi[kind])
+            n_lo, n_hi = lo[kind][0][1], hi[kind][0][1]      # (a solve whose residual reaches exactly 0 ends before its cap: counted as run)
+            rec[kind + "_iterations"] = [n_lo, n_hi]
+            rec[kind + "_window_s"] = round(t_hi - t_lo, 4)
+            # (no rate when both solves ended at the same iteration: a grid too small for a half-second window)
+            rec[kind + "_iterations_per_s"] = round((n_hi - n_lo) / (t_hi - t_lo), 2) if n_hi > n_lo and t_hi > t_lo else None
+        for other in ("fp64_plain", "fp64_default"):
+            if rec["fp32_iterations_per_s"] and rec[other + "_iterations_per_s"]:
+                rec["ratio_fp32_over_" + other] = round(rec["fp32_iterations_per_s"] / rec[other + "_iterations_per_s"], 3)
+        emit(rec)
+
+
+# ---------------------------------------------------------------------------------------------------------------- time to tolerance
+def refine_case(name, N, reps, jacobi):
+    ctx = K.Context(0)
+    a = operator(name, N, ctx)                             # one operator, streamed in either form
+    n = a.nrows()
+    default_encoding = encoding(a, False)
+    encoding(a, True)
+    b = a.spmv(ctx.vec(n).fill_splitmix(7))
+    x = ctx.vec(n)
+    cap = 20000
+    pc = K.Jacobi().setup(a) if jacobi else None
+    fp64 = K.PcgSolver if jacobi else K.CgSolver
+    ref = K.RefinementSolver(1e-10, 40).with_inner(1e-6, cap)
+    ref.lowered(a)                                         # (the lowering is made once per operator: not part of a solve's time)
+    rec = {"case": "refine", "op": name, "N": N, "n": n, "inner": "pcg_jacobi" if jacobi else "cg", "outer_tol": 1e-10, "inner_tol": 1e-6,
+           "runs": reps, "default_encoding": default_encoding, "lowering": ref.lowered(a).info}
+
+    def run_refine(plain):
+        use(plain)
+        x.fill(0.0)
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        st = ref.solve(a, pc, b, x)
+        ms = (time.perf_counter() - t0) * 1e3
+        rec["refine_" + ("plain" if plain else "default")] = {
+            "outer_steps": st.iterations, "inner_iterations": st.inner_iterations, "total_inner": sum(st.inner_iterations),
+            "converged": st.converged, "final_over_first": ref.residual_history[-1] / ref.residual_history[0]}
+        ref.clear_history()
+        return ms
+
+    def run_fp64(plain):
+        use(plain)
+        x.fill(0.0)
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        st = fp64(1e-10, cap).solve(a, pc, b, x)
+        ms = (time.perf_counter() - t0) * 1e3
+        rec["fp64_" + ("plain" if plain else "default")] = {"iterations": st.iterations, "converged": st.converged}
+        return ms
+
+    # warm-up: first-use allocations (the work arena, the reduction scratch) on both paths
+    warm = K.RefinementSolver(1e-10, 1).with_inner(1e-6, 5)
+    warm._lowered.update(ref._lowered)
+    warm.solve(a, pc, b, ctx.vec(n))
+    fp64(0.0, 5).solve(a, pc, b, ctx.vec(n))
+    ms = alternate({"refine_plain": lambda: run_refine(True), "fp64_plain": lambda: run_fp64(True),
+                    "refine_default": lambda: run_refine(False), "fp64_default": lambda: run_fp64(False)}, reps)
+    for k, v in ms.items():
+        rec[k]["ms"] = round(v, 2)
+    for form in ("plain", "default"):
+        rec["time_ratio_fp64_over_refine_" + form] = round(ms["fp64_" + form] / ms["refine_" + form], 3)
+    emit(rec)
+
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("mode", choices=("spmv", "rate", "refine"))
+    ap.add_argument("N", type=int)
+    ap.add_argument("--op", default="poisson", choices=("poisson", "varcoef", "band"))
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--jacobi", action="store_true", help="refine: Jacobi-PCG inside and as the fp64 yardstick (default for varcoef)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    OUT = args.out
+    if args.mode == "spmv":
+        spmv_case(args.op, args.N, args.reps)
+    elif args.mode == "rate":
+        rate_case(args.op, args.N, args.reps)
+    else:
+        refine_case(args.op, args.N, args.reps, args.jacobi or args.op == "varcoef")
