@@ -280,6 +280,7 @@ extern "C" {
     pub fn kryst_vec32_destroy(v: Vec32) -> i32;
     pub fn kryst_vec32_upload(v: Vec32, host: *const f32, n: i64) -> i32;
     pub fn kryst_vec32_download(v: Vec32, host: *mut f32, n: i64) -> i32;
+    pub fn kryst_bench_vec32_padding(v: Vec32, fill: *const f32, dirty: *mut i64) -> i32;
     pub fn kryst_vec32_from_f64(dst: Vec32, src: Vecd) -> i32;
     pub fn kryst_vec32_to_f64(dst: Vecd, src: Vec32) -> i32;
     pub fn kryst_dot32(x: Vec32, y: Vec32, out: *mut f64) -> i32;

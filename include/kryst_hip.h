@@ -694,6 +694,9 @@ int32_t kryst_vec32_create(kryst_ctx_t ctx, int64_t n, kryst_vec32_t* out);
 int32_t kryst_vec32_destroy(kryst_vec32_t v);
 int32_t kryst_vec32_upload(kryst_vec32_t v, const float* host, int64_t n);
 int32_t kryst_vec32_download(kryst_vec32_t v, float* host, int64_t n);
+/* test hook, kryst_bench_vec_padding for an fp32 vector: *dirty (may be NULL) counts the allocated floats of index >= n whose 32 bits are
+ * not +0.0, then *fill (may be NULL) sets them all; elements below n are never touched */
+int32_t kryst_bench_vec32_padding(kryst_vec32_t v, const float* fill, int64_t* dirty);
 /* dst[i] = (float)src[i] (rounds) / dst[i] = (double)src[i] (widens, exact), on the device; lengths must agree */
 int32_t kryst_vec32_from_f64(kryst_vec32_t dst, kryst_vec_t src);
 int32_t kryst_vec32_to_f64(kryst_vec_t dst, kryst_vec32_t src);

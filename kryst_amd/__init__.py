@@ -336,9 +336,9 @@ class DeviceVec32:
         return out
 
     @staticmethod
-    def from_f64(v):
+    def from_f64(v, out=None):
         """(float)v[i] of a DeviceVec, rounded on the device."""
-        out = DeviceVec32(v.ctx, v.n)
+        out = DeviceVec32(v.ctx, v.n) if out is None else out
         check(lib().kryst_vec32_from_f64(out.h, v.h))
         return out
 
@@ -347,6 +347,21 @@ class DeviceVec32:
         out = DeviceVec(self.ctx, self.n) if out is None else out
         check(lib().kryst_vec32_to_f64(out.h, self.h))
         return out
+
+    QUIET_NAN_BITS = 0x7FC00000
+
+    def poison_padding(self, value=None):
+        """Test hook (kryst_bench_vec32_padding): every allocated float behind the n-th -- the rest of the last 1024-element tile and the
+        whole extra tile -- becomes `value` (default: the quiet NaN 0x7FC00000).  Results must not depend on it."""
+        fill = np.array([self.QUIET_NAN_BITS], dtype=np.uint32).view(np.float32) if value is None else np.array([value], dtype=np.float32)
+        check(lib().kryst_bench_vec32_padding(self.h, _fp(fill), None))
+        return self
+
+    def padding_dirty(self):
+        """How many allocated floats behind the n-th are not +0.0 (kryst_bench_vec32_padding)."""
+        dirty = C.c_int64(-1)
+        check(lib().kryst_bench_vec32_padding(self.h, None, C.byref(dirty)))
+        return dirty.value
 
     def __del__(self):
         try:

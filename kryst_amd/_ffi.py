@@ -212,6 +212,7 @@ SIGNATURES = {
     "kryst_vec32_destroy": (C.c_int32, [Handle]),
     "kryst_vec32_upload": (C.c_int32, [Handle, c_fp, C.c_int64]),
     "kryst_vec32_download": (C.c_int32, [Handle, c_fp, C.c_int64]),
+    "kryst_bench_vec32_padding": (C.c_int32, [Handle, c_fp, c_i64p]),
     "kryst_vec32_from_f64": (C.c_int32, [Handle, Handle]),
     "kryst_vec32_to_f64": (C.c_int32, [Handle, Handle]),
     "kryst_dot32": (C.c_int32, [Handle, Handle, c_dp]),

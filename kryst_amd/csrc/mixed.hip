@@ -60,6 +60,15 @@ __global__ void lower_values_kernel(float* dst, const double* src, int64_t n, un
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = round_count(src[i], cnt);
     for (int k = 0; k < 3; ++k) { if (cnt[k]) atomicAdd(count + k, cnt[k]); }
 }
+// elements [n, cap): count those whose bits are not +0.0, then (fill) overwrite them.  One workgroup.
+__global__ void vec32_padding_kernel(float* d, int64_t n, int64_t cap, int fill, float value, unsigned long long* count) {
+    unsigned long long mine = 0;
+    for (int64_t e = n + threadIdx.x; e < cap; e += blockDim.x) {
+        if (__float_as_uint(d[e]) != 0u) ++mine;
+        if (fill) d[e] = value;
+    }
+    if (mine) atomicAdd(count, mine);
+}
 
 // ---------------------------------------------------------------------------------------------------- pointwise passes
 // Op: static constexpr int NQ; quad(i, n, acc): thread t of tile q owns elements q * 1024 + 4 t .. + 3; a fused reduction folds the thread's terms
@@ -603,6 +612,26 @@ int32_t kryst_vec32_download(kryst_vec32_t v, float* host, int64_t n) {
     KR_HIP(hipSetDevice(v->ctx->device));
     if (n > 0) KR_HIP(hipMemcpyAsync(host, v->d, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, v->ctx->s_main));
     KR_HIP(hipStreamSynchronize(v->ctx->s_main));
+    return KRYST_OK;
+}
+
+int32_t kryst_bench_vec32_padding(kryst_vec32_t v, const float* fill, int64_t* dirty) {
+    KR_TRY(vec32_check(v));
+    kryst_ctx_t ctx = v->ctx;
+    KR_HIP(hipSetDevice(ctx->device));
+    unsigned long long* d_count = nullptr;
+    KR_HIP(hipMalloc(&d_count, sizeof(unsigned long long)));
+    hipError_t e = hipMemsetAsync(d_count, 0, sizeof(unsigned long long), ctx->s_main);
+    unsigned long long count = 0;
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(vec32_padding_kernel, dim3(1), dim3(1024), 0, ctx->s_main, v->d, v->n, vec32_len(v->n), fill ? 1 : 0, fill ? *fill : 0.0f, d_count);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->s_main);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->s_main);
+    (void)hipFree(d_count);
+    KR_HIP(e);
+    if (dirty) *dirty = (int64_t)count;
     return KRYST_OK;
 }
 

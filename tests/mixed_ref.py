@@ -74,8 +74,9 @@ def _check(res, res0, i, tol, max_iters):
     return bool(rel <= tol) or i >= max_iters
 
 
-def cg32(a32, b32, x32, tol, max_iters, rs=RS32):
-    """kryst_cg32_solve_dev: cg.rs:114-288 with norm type Preconditioned / Unpreconditioned (both (r, r))"""
+def cg32(a32, b32, x32, tol, max_iters, rs=RS32, watch=None):
+    """kryst_cg32_solve_dev: cg.rs:114-288 with norm type Preconditioned / Unpreconditioned (both (r, r)).  watch(i, ap, x, r, p), if
+    given, sees the stored vectors of iteration i after its x and r updates (p: the direction the iteration used)"""
     with np.errstate(all="ignore"):
         x = x32.copy()
         r = store(wide(b32) - wide(a32.spmv(x)))                        # cg.rs:120-125
@@ -94,6 +95,8 @@ def cg32(a32, b32, x32, tol, max_iters, rs=RS32):
             alpha = rsq / pap                                           # :175
             x = store(wide(x) + alpha * wide(p))                        # :207-209
             r = store(wide(r) - alpha * wide(ap))                       # :210-212
+            if watch is not None:
+                watch(i, ap, x, r, p)
             rsq_new = dot32(r, r, rs)                                   # :223
             res = np.sqrt(rsq_new)
             if rsq_new / rsq < 0.0:                                     # :254-259

@@ -86,6 +86,9 @@ def test_spmv32(ctx, name):
         y = d32.spmv(K.DeviceVec32(ctx, x)).to_host()
         want = ref.spmv(x)
         assert same32(y, want), (name, int(np.sum(b32(y) != b32(want))))
+        full = K.DeviceVec32(ctx, np.full(a.nrows, np.nan, np.float32))          # every row is stored, the empty ones as +0.0
+        y = d32.spmv(K.DeviceVec32(ctx, x), full).to_host()
+        assert same32(y, want), (name, "into a NaN-filled y", int(np.sum(b32(y) != b32(want))))
     assert same32(d32.spmv(MC.vec32(a.ncols)), ref.spmv(MC.vec32(a.ncols)))       # host arrays round-trip
 
 
