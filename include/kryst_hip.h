@@ -167,6 +167,11 @@ int32_t kryst_csr_pattern_info(kryst_csr_t a, int64_t* info);
  * info[2] T, info[3] strips per plane, info[4] S, info[5] segments (info[3 .. 5] 0 when not eligible), info[6] 1 if a fused CG iteration would
  * now store no A p and form it again in its residual pass (KRYST_CG_RECOMPUTE_AP; the marching mode on, x updated in batches).  info: 7 values */
 int32_t kryst_csr_fuse_march_info(kryst_csr_t a, int64_t* info);
+/* measurement hook: the marching kernels keep a tile's row-pattern ids in registers where they repeat those of the tile one grid plane below
+ * (a per-tile table made once at creation; KRYST_SPMV_PID_REUSE = 0 hands the kernels no table: every plane loads its ids; the same bits either
+ * way).  info[0] 1 if a marching launch would be handed the table now, info[1] tiles flagged as repeating, info[2] tiles the table covers
+ * (info[1], info[2] 0 for an operator without a table).  info: 3 values */
+int32_t kryst_csr_pid_reuse_info(kryst_csr_t a, int64_t* info);
 int32_t kryst_csr_download(kryst_csr_t a, int64_t* row_ptr, int32_t* col_idx_local, double* vals);
 /* Measurement hook (ABI 5): where the CSR arrays live.  The same plain-CSR stream mix runs at 0.70 .. 0.76 of the HBM peak depending on where
  * the driver put the three arrays (round 4, 512^3), so a single-rank creation may try several homes for (row_ptr, col, val) -- K =

@@ -608,11 +608,15 @@ class CsrMatrix:
     def fuse_march_info(self):
         """Measurement hook (kryst_csr_fuse_march_info): the marching mode of the fused direction + SpMV kernel under the current
         KRYST_SPMV_FUSE_* settings -- {"eligible", "on", "T", "strips", "S", "segments"} -- and "recompute_ap": whether a fused CG iteration would
-        now store no Ap and form it again in its residual pass (KRYST_CG_RECOMPUTE_AP, x in batches)."""
+        now store no Ap and form it again in its residual pass (KRYST_CG_RECOMPUTE_AP, x in batches).  From kryst_csr_pid_reuse_info: "pid_reuse":
+        whether a marching launch would now keep repeated row-pattern ids in registers (KRYST_SPMV_PID_REUSE and the operator's per-tile table),
+        "pid_same_tiles": tiles whose ids repeat the tile one plane below, "tiles": tiles the table covers (both 0 without a table)."""
         info = (C.c_int64 * 7)()
         check(lib().kryst_csr_fuse_march_info(self.h, info))
+        reuse = (C.c_int64 * 3)()
+        check(lib().kryst_csr_pid_reuse_info(self.h, reuse))
         return {"eligible": bool(info[0]), "on": bool(info[1]), "T": info[2], "strips": info[3], "S": info[4], "segments": info[5],
-                "recompute_ap": bool(info[6])}
+                "recompute_ap": bool(info[6]), "pid_reuse": bool(reuse[0]), "pid_same_tiles": reuse[1], "tiles": reuse[2]}
 
     def placement_info(self):
         """Where the CSR arrays live (kryst_csr_placement_info): {"tries", "chosen", "skeleton_ms": [...]} of the homes tried at creation."""

@@ -22,6 +22,9 @@ struct kryst_csr_s {
     double* d_vdict = nullptr;      // 256 values: val = d_vdict[code >> 8]  (<= 256 distinct value bit patterns)
     // CSR-P16: one 16-bit pattern id per ROW; a pattern is the row's whole sequence of (col - row, value) pairs
     uint16_t* d_pid = nullptr;      // nrows (+ KR_TILE pad) pattern ids, or nullptr
+    // per tile: 1 = all 512 ids equal those of the tile one plane (pat_far_hi rows) below, so a marching workgroup keeps them in registers; nullptr
+    // unless the far offsets are uniform, +- one plane, and planes and box are whole tiles / planes (csr_create.hip: build_pid_same)
+    uint8_t* d_pid_same = nullptr; int64_t pid_same_count = 0;      // ntiles flags (+ pad), and how many are set
     uint32_t* d_pmeta = nullptr;    // per pattern, 2 words: (first table entry of its base | base length << 16, presence mask)
     int32_t* d_poff = nullptr;      // table: col - row
     double* d_pval = nullptr;       // table: value

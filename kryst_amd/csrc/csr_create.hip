@@ -140,6 +140,40 @@ static int32_t build_patterns(kryst_csr_t a, const std::vector<int32_t>& rp, con
     return upload_patterns(a, pid, meta, poff, pval);
 }
 
+// CSR-P16 for the marching kernels (spmv_fuse.hip: fuse_march, cg_recompute_residual_kernel): same[q] = 1 iff tile q is not in the first plane and all
+// 512 ids of tile q are those of tile q - tpp, the same (i, j) rows one plane below.  One workgroup per tile, a lane per pair of ids.
+__global__ __launch_bounds__(KR_T) void pid_same_kernel(const uint16_t* __restrict__ pid, int64_t ntiles, int64_t tpp, uint8_t* __restrict__ same) {
+    const int64_t q = blockIdx.x;
+    if (q >= ntiles) return;                                                 // (uniform over the workgroup)
+    int eq = 0;
+    if (q >= tpp) {                                                          // (uniform)
+        const unsigned* cur = reinterpret_cast<const unsigned*>(pid + q * KR_TILE);
+        const unsigned* below = reinterpret_cast<const unsigned*>(pid + (q - tpp) * KR_TILE);
+        eq = cur[threadIdx.x] == below[threadIdx.x] ? 1 : 0;
+    }
+    const int all = __syncthreads_and(eq);
+    if (threadIdx.x == 0) same[q] = all ? 1 : 0;
+}
+// Built once per operator, after its ids are on the device (upload_patterns or the stencil generator), where a marching plan can be eligible at all
+// (fuse_march_plan's conditions that do not depend on T): one rank, uniform far offsets of +- one plane, planes of whole tiles, a box of whole planes.
+// ntiles bytes (256 KiB at 512^3) and one read of the ids; every other operator keeps d_pid_same == nullptr ("never the same").
+static int32_t build_pid_same(kryst_csr_t a) {
+    const int64_t plane = a->pat_far_uniform ? (int64_t)a->pat_far_hi : 0;
+    if (!(a->d_pid && !a->dist && a->pat_stage_n > 0 && a->pat_stage_n <= 512 && plane > 0 && (int64_t)a->pat_far_lo == -plane && plane % KR_TILE == 0 &&
+          a->nrows % plane == 0 && a->nrows == a->xlen)) return KRYST_OK;
+    kryst_ctx_t ctx = a->ctx;
+    const int64_t ntiles = a->nrows / KR_TILE, tpp = plane / KR_TILE;
+    KR_HIP(hipMalloc(&a->d_pid_same, (size_t)ntiles + 8));                   // (+ 8: a strip's flags are read as one word)
+    KR_HIP(hipMemsetAsync(a->d_pid_same, 0, (size_t)ntiles + 8, ctx->s_main));
+    hipLaunchKernelGGL(pid_same_kernel, dim3((unsigned)ntiles), dim3(KR_T), 0, ctx->s_main, a->d_pid, ntiles, tpp, a->d_pid_same);
+    KR_HIP(hipGetLastError());
+    std::vector<uint8_t> flags((size_t)ntiles);
+    KR_HIP(hipMemcpyAsync(flags.data(), a->d_pid_same, flags.size(), hipMemcpyDeviceToHost, ctx->s_main));
+    KR_HIP(hipStreamSynchronize(ctx->s_main));
+    a->pid_same_count = 0;
+    for (uint8_t f : flags) a->pid_same_count += f;
+    return KRYST_OK;
+}
 
 // ---------------------------------------------------------------- CSR-DIA (built on the device from the CSR-D8 form)
 // used[] : 256-bit map of the offset codes that occur
@@ -417,6 +451,7 @@ static int32_t encode_csr(kryst_csr_t a, const std::vector<int32_t>& rp, const s
     const double per_slice = a->nrows > 0 ? (double)a->nnz / (double)((a->nrows + 127) / 128) : 0.0;
     a->slots = per_slice <= 256.0 ? 2 : (per_slice <= 512.0 ? 4 : 7);
     KR_TRY(build_patterns(a, rp, col, val));
+    KR_TRY(build_pid_same(a));
     KR_TRY(build_dia(a));
     KR_TRY(build_tile_order(a));
     return KRYST_OK;
@@ -836,6 +871,7 @@ static int32_t create_stencil7_device(kryst_ctx_t ctx, int32_t N, int32_t kind, 
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->s_main) != hipSuccess) { set_error("stencil7 generation failed"); rc = KRYST_ERR_HIP; break; }
         a->ntiles = ntiles_of(nloc);
         a->slots = 7;
+        if ((rc = build_pid_same(a)) != KRYST_OK) break;
         if ((rc = build_dia(a)) != KRYST_OK) break;
         if ((rc = build_tile_order(a)) != KRYST_OK) break;
         if (!dist) break;
@@ -911,7 +947,7 @@ int32_t kryst_csr_destroy(kryst_csr_t a) {
     (void)hipStreamSynchronize(a->ctx->s_main);
     (void)hipStreamSynchronize(a->ctx->s_comm);
     (void)hipFree(a->d_row_ptr); (void)hipFree(a->d_col); (void)hipFree(a->d_val); (void)hipFree(a->d_code); (void)hipFree(a->d_dict); (void)hipFree(a->d_code16); (void)hipFree(a->d_vdict);
-    (void)hipFree(a->d_pid); (void)hipFree(a->d_pmeta); (void)hipFree(a->d_poff); (void)hipFree(a->d_pval); (void)hipFree(a->d_dia);
+    (void)hipFree(a->d_pid); (void)hipFree(a->d_pid_same); (void)hipFree(a->d_pmeta); (void)hipFree(a->d_poff); (void)hipFree(a->d_pval); (void)hipFree(a->d_dia);
     (void)hipFree(a->d_tiles_interior); (void)hipFree(a->d_tiles_boundary); (void)hipFree(a->d_tile_order);
     (void)hipFree(a->plan.d_send_idx); (void)hipFree(a->plan.d_sendbuf); (void)hipFree(a->plan.d_halo);
     halo_peer_destroy(a);

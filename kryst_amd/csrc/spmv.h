@@ -17,6 +17,7 @@ struct SpmvArgs {
     const uint8_t* code; const int32_t* dict;      // CSR-D8: col = row + dict[code] (nullptr when not compressed)
     const uint16_t* code16; const double* vdict;   // CSR-D16: col = row + dict[c & 255], val = vdict[c >> 8]
     const uint16_t* pid; const uint32_t* pmeta; const int32_t* poff; const double* pval; int32_t npat, ntab;   // CSR-P16
+    const uint8_t* pid_same;                       // marching kernels: per tile, 1 = its ids are those of the tile one plane below (nullptr: never the same)
     int32_t pat_red_off;                           // byte offset of the reduction scratch in the kernel's dynamic LDS
     int32_t nloc8;                                 // 8 * nloc
     int32_t tpw;                                   // pattern kernel: consecutive tile slots per workgroup

@@ -3,6 +3,19 @@
 #include "spmv.h"
 
 namespace kr {
+// KRYST_SPMV_PID_REUSE (the marching kernels; csr_create.hip: build_pid_same): the pid_same flags of a strip's T tiles in the plane whose strip starts
+// at row r0, as one word -- byte k: tile r0 / 512 + k, a multiple of T, so the word is aligned; 0 ("never the same") without a table.  The address
+// depends on the workgroup's strip and the plane alone: the value is uniform, and so is every branch on it.
+template <int T>
+__device__ __forceinline__ unsigned pid_same_word(const SpmvArgs& a, const int32_t r0) {
+    if (!a.pid_same) return 0u;
+    const uint8_t* f = a.pid_same + r0 / KR_TILE;
+    unsigned w;
+    if constexpr (T == 4) w = *reinterpret_cast<const unsigned*>(f);
+    else w = *reinterpret_cast<const unsigned short*>(f);
+    return w;
+}
+
 // CG / PCG with the direction pass INSIDE the SpMV (spmv_pattern_fuse_kernel; round 5).  An iteration used to end with the
 // direction pass  x += alpha p, p = z + beta p  (5 vector words per row) and the next one began with the SpMV reading that p again.  Here the
 // staged-window kernel forms p itself: its window fill reads z and p_old instead of p and stores  z + beta p_old  -- cg.rs:274-276 /
@@ -28,7 +41,8 @@ struct FuseArgs { const double* z; const double* p_old; double* p_new; double* x
 // (clamped at the ends of the box), as the un-marched kernel does for every tile: per own line 1 + (2 n + 4) / R + 2 / S lines of z and p_old are
 // requested instead of 3 + (2 n + 4) / R, and the halo lines are a neighbouring strip's own lines on the same XCD.
 //   LDS: TWO windows of R + 2 n + 4 doubles, W(s) and W(s + 1).  A step is
-//     a. request W(s + 2): z, p_old (and the owed x) of the whole window into REGISTERS, and the ids of plane s + 1 -- in flight under b.  (Not by
+//     a. request W(s + 2): z, p_old (and the owed x) of the whole window into REGISTERS, and the ids of plane s + 1 -- of those tiles whose pid_same
+//        flag is clear: the others repeat the plane below and stay in ids[k], KRYST_SPMV_PID_REUSE -- in flight under b.  (Not by
 //        LDS-DMA as the un-marched fill: beside a pending DMA the compiler drains vmcnt(0) before the first LDS read of b. and before every use of
 //        an ordinary load, which serialises the step; plain loads are counted exactly.  Both forms read at the same rate.)
 //     b. the tiles of plane s out of W(s) and W(s + 1), y stored (YS; not when the residual pass recomputes it), partials per wave into red;
@@ -120,6 +134,8 @@ __device__ __forceinline__ void fuse_march(const SpmvArgs& a, const FuseArgs& f,
     };
     unsigned ids[T], idn[T];
     v2d prev[T], hi[T];
+    // the flags of plane s + 1, read one step ahead like the ids they stand for (the segment's first plane always loads its ids)
+    unsigned same = ns > 1 ? pid_same_word<T>(a, rbeg + plane) : 0u, samen = 0u;
     // ---- the segment's first two windows
 #pragma unroll
     for (int k = 0; k < T; ++k) { ids[k] = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(a.pid + (size_t)rbeg + k * KR_TILE + 2 * t)); idn[k] = 0u; }
@@ -140,9 +156,14 @@ __device__ __forceinline__ void fuse_march(const SpmvArgs& a, const FuseArgs& f,
         const bool last = s + 1 == ns, fill = s + 2 < ns;                   // (uniform)
         // a.
         if (fill) request(r0 + 2 * plane);
+        samen = fill ? pid_same_word<T>(a, r0 + 2 * plane) : 0u;
+        // byte k set: the ids of tile k repeat the plane below and stay in ids[k] -- no load now, no hand-over at the step's end (uniform; the
+        // segment's last plane requests nothing)
+        const unsigned sw = last ? ~0u : __builtin_amdgcn_readfirstlane(same);
         if (!last) {
 #pragma unroll
-            for (int k = 0; k < T; ++k) idn[k] = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(a.pid + (size_t)(r0 + plane) + k * KR_TILE + 2 * t));
+            for (int k = 0; k < T; ++k)
+                if (!((sw >> (8 * k)) & 1u)) idn[k] = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(a.pid + (size_t)(r0 + plane) + k * KR_TILE + 2 * t));
         } else {
 #pragma unroll
             for (int k = 0; k < T; ++k) hi[k] = far_pair((int64_t)r0 + k * KR_TILE + 2 * t + plane);
@@ -197,7 +218,8 @@ __device__ __forceinline__ void fuse_march(const SpmvArgs& a, const FuseArgs& f,
         if (fill) write_window(r0 + 2 * plane, w0);
         __syncthreads();                                                     // barrier 2
 #pragma unroll
-        for (int k = 0; k < T; ++k) ids[k] = idn[k];
+        for (int k = 0; k < T; ++k) if (!((sw >> (8 * k)) & 1u)) ids[k] = idn[k];       // (a hand-over, not a copy back and forth: the compiler gathers T plain copies into one register tuple)
+        same = samen;
         double* w = w0; w0 = w1; w1 = w;
     }
 }
@@ -388,7 +410,8 @@ __global__ __launch_bounds__(KR_T) void spmv_pattern_fuse_kernel(const SpmvArgs 
 //   Resources (gfx950, T = 4, n = 512): 165 VGPRs, no scratch (the compiler keeps a tile's LDS reads and the window in flight side by side: three waves
 //   per SIMD would fit, two are resident); LDS 3 x 24 608 B of windows + 8 B per pattern and table entry + 256 B of red, padded to 81 408 B (half a CU's LDS less 512).  Measured at
 //   512^3 (profiles/recompute/): the fused kernel 810 -> 632 us (35.3 -> 27.2 bytes per row), the residual pass 507 -> 620 us (24.1 -> 26.5), CG 628 ->
-//   674 it/s.
+//   674 it/s.  With the ids kept where they repeat (KRYST_SPMV_PID_REUSE, fuse_march's step a.; profiles/pid_reuse/): 168 VGPRs, the residual pass
+//   621 -> 576 us (26.5 -> 24.5 bytes per row).
 //   a.group: strips per XCD; a.xcd_chunk: S; a.tpw: strips per plane; every strip and every plane is whole, so every row of a strip is a row of the box.
 // KEEP: r is stored temporal (keep_in_cache: the next launch reads it again out of the Infinity Cache), as CgResidualOp<KEEP> does.
 template <int T, bool KEEP>
@@ -439,6 +462,7 @@ __global__ __launch_bounds__(KR_T) void cg_recompute_residual_kernel(const SpmvA
     unsigned ids[T], idn[T];
     d2 rr[T], rn[T];
     v2d prev[T], hi[T];
+    unsigned same = ns > 1 ? pid_same_word<T>(a, rbeg + plane) : 0u, samen = 0u;     // fuse_march's: the flags of plane s + 1, one step ahead
     // ---- the segment's first two windows, r and the ids of its first plane
 #pragma unroll
     for (int k = 0; k < T; ++k) {
@@ -463,10 +487,12 @@ __global__ __launch_bounds__(KR_T) void cg_recompute_residual_kernel(const SpmvA
         double* redb = red + (s & 1) * (T * (KR_T / 64));
         // a.
         if (fill) request(r0 + 2 * plane);
+        samen = fill ? pid_same_word<T>(a, r0 + 2 * plane) : 0u;
+        const unsigned sw = last ? ~0u : __builtin_amdgcn_readfirstlane(same);     // fuse_march's: byte k set, the ids of tile k stay in ids[k] (uniform)
         if (!last) {
 #pragma unroll
             for (int k = 0; k < T; ++k) {
-                idn[k] = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(a.pid + (size_t)(r0 + plane) + k * KR_TILE + 2 * t));
+                if (!((sw >> (8 * k)) & 1u)) idn[k] = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(a.pid + (size_t)(r0 + plane) + k * KR_TILE + 2 * t));
                 rn[k] = ld2(r, (int64_t)(r0 + plane) + k * KR_TILE + 2 * t);
             }
         } else {
@@ -514,7 +540,8 @@ __global__ __launch_bounds__(KR_T) void cg_recompute_residual_kernel(const SpmvA
             a.partials[r0 / KR_TILE + t] = sum;
         }
 #pragma unroll
-        for (int k = 0; k < T; ++k) { ids[k] = idn[k]; rr[k] = rn[k]; }
+        for (int k = 0; k < T; ++k) { if (!((sw >> (8 * k)) & 1u)) ids[k] = idn[k]; rr[k] = rn[k]; }
+        same = samen;
         double* w = w0; w0 = w1; w1 = w2; w2 = w;
     }
 }
@@ -583,6 +610,10 @@ static RecomputePlan recompute_plan(kryst_csr_t a) {
     return q;
 }
 bool spmv_can_recompute_ap(kryst_csr_t a) { return spmv_can_fuse_direction(a) && recompute_plan(a).on; }
+// The marching kernels keep a tile's pattern ids in registers from plane to plane where the operator's pid_same table says they repeat (csr.h:
+// d_pid_same; on a box with constant coefficients every plane but the first two and the last).  KRYST_SPMV_PID_REUSE (0 / 1, read per launch): 0
+// hands the kernels no table, and every plane loads its ids again.
+static const uint8_t* pid_same_table(kryst_csr_t a) { return env_int("KRYST_SPMV_PID_REUSE", 1) != 0 ? a->d_pid_same : nullptr; }
 // r -= alpha A p with the tile partials of (r, r), A p formed from p on the way (the launch after launch_spmv_fused(.., y = nullptr, ..) and alpha's fold)
 int32_t launch_cg_residual_recompute(kryst_csr_t a, const double* p, double* r, const double* alpha, bool keep, const int* done) {
     kryst_ctx_t ctx = a->ctx;
@@ -594,6 +625,7 @@ int32_t launch_cg_residual_recompute(kryst_csr_t a, const double* p, double* r, 
     args.xsafe = xsafe_of(a);
     const int spx = (q.m.strips + 7) / 8;
     args.group = spx; args.xcd_chunk = q.m.S; args.tpw = q.m.strips; args.pat_red_off = (int32_t)q.lds.red_off;
+    args.pid_same = pid_same_table(a);
     // two resident workgroups per CU, like the fused kernel: the dynamic LDS request is padded so that no third one fits (T = 2)
     const size_t lds = std::max(q.lds.bytes, (size_t)(160 << 10) / 2 - 512);
     static bool raised = false;
@@ -647,6 +679,7 @@ static int32_t launch_spmv_fused_impl(kryst_csr_t a, const double* z, const doub
 #endif
         const int spx = (m.strips + 7) / 8;
         args.group = spx; args.xcd_chunk = m.S; args.tpw = m.strips; args.pat_red_off = (int32_t)m.lds.red_off;
+        args.pid_same = pid_same_table(a);
         size_t lds_m = m.lds.bytes;
         // resident workgroups per CU: two unless KRYST_SPMV_FUSE_WG_PER_CU says otherwise (the three that fit at T = 4 are slower: 512^3 CG 620-624 against
         // 636 it/s, profiles/march/sweep512.jsonl)
@@ -712,6 +745,18 @@ int32_t kryst_csr_fuse_march_info(kryst_csr_t a, int64_t* info) {
     if (form) m = fuse_march_plan(a, 2);
     info[0] = m.eligible ? 1 : 0; info[1] = m.eligible && m.on ? 1 : 0; info[2] = m.T; info[3] = m.strips; info[4] = m.S; info[5] = m.segs;
     info[6] = form && recompute_plan(a).on ? 1 : 0;
+    return KRYST_OK;
+}
+// info[0]: a marching launch would now be handed the operator's pid_same table (the marching mode on, KRYST_SPMV_PID_REUSE, a table); info[1]: tiles
+// flagged "the ids of the tile one plane below"; info[2]: tiles the table covers (info[1 .. 2] 0 without a table)
+int32_t kryst_csr_pid_reuse_info(kryst_csr_t a, int64_t* info) {
+    KR_ARG(a && info, "csr_pid_reuse_info");
+    FuseMarchPlan m;
+    memset(&m, 0, sizeof m);
+    if (fuse_form(a)) m = fuse_march_plan(a, 2);
+    info[0] = m.eligible && m.on && pid_same_table(a) ? 1 : 0;
+    info[1] = a->d_pid_same ? a->pid_same_count : 0;
+    info[2] = a->d_pid_same ? a->nrows / KR_TILE : 0;
     return KRYST_OK;
 }
 // Measurement hook: average milliseconds per launch of the fused direction + SpMV kernel of CG / PCG (spmv_pattern_fuse_kernel) on work vectors of its
