@@ -286,6 +286,8 @@ extern "C" {
     pub fn kryst_vec32_to_f64(dst: Vecd, src: Vec32) -> i32;
     pub fn kryst_dot32(x: Vec32, y: Vec32, out: *mut f64) -> i32;
     pub fn kryst_csr32_lower(a: Csr, out: *mut Csr32) -> i32;
+    pub fn kryst_csr32_lower_form(a: Csr, form: i32, out: *mut Csr32) -> i32;        // form: 0 plain, 1 auto, 2 pattern (CSR-P16)
+    pub fn kryst_csr32_encoding(a: Csr32, kernel: *mut i32) -> i32;
     pub fn kryst_csr32_info(a: Csr32, info: *mut i64) -> i32;
     pub fn kryst_csr32_destroy(a: Csr32) -> i32;
     pub fn kryst_host_round_f32(v: *const f64, n: i64, out: *mut f32, info: *mut i64) -> i32;

@@ -685,8 +685,8 @@ int32_t kryst_pcg_solve_multi(const double* b, double* x, int64_t n, int32_t k, 
  * A LABELLED DEVIATION from the reference at T = f32 (CsrMatrix<f32>, CgSolver<f32>, `T: Float`), which would round every operation: here
  * fp32 is how vector elements and matrix values are STORED.  Every kernel widens what it loads, computes in fp64 in the fixed order of its
  * fp64 twin (separate multiply and add) and rounds once -- (float), round to nearest even, fp32 subnormals kept -- when it stores; every
- * scalar (alpha, beta, the inner products, the residual norms, the exits) is fp64 and is the fp64 solver's own code.  One rank; plain CSR
- * arrays only; nothing here runs unless it is called. */
+ * scalar (alpha, beta, the inner products, the residual norms, the exits) is fp64 and is the fp64 solver's own code.  One rank; the plain CSR
+ * arrays, or (kryst_csr32_lower_form) the CSR-P16 row-pattern form; nothing here runs unless it is called. */
 typedef struct kryst_vec32_s* kryst_vec32_t;
 typedef struct kryst_csr32_s* kryst_csr32_t;
 /* kryst_reduce_spec for fp32-stored vectors: T = 256 threads own V = 4 consecutive elements each (a 1024-element tile, one 16-byte access
@@ -712,6 +712,22 @@ int32_t kryst_dot32(kryst_vec32_t x, kryst_vec32_t y, double* out);
  * created: a finite value that would round to +-inf; a distributed operator.  A non-square operator is accepted (kryst_spmv32 handles it,
  * the solvers refuse it). */
 int32_t kryst_csr32_lower(kryst_csr_t a, kryst_csr32_t* out);
+/* The lowering with a choice of what the lowered operator keeps.  Every form keeps the plain arrays exactly as kryst_csr32_lower (= PLAIN) makes
+ * them -- the counts of kryst_csr32_info, the overflow refusal and the fallback kernel are the same.  PATTERN, and AUTO when `a` has a CSR-P16
+ * (row-pattern) form, ALSO keeps its own copies of that form: one 16-bit pattern id per row (re-padded to the 1024-row fp32 tile), the pattern
+ * table's offsets, and its values rounded with the same (float) as the CSR values, so a table value is bit for bit the lowered value of every row
+ * that uses it and kryst_spmv32 gives the same bits on either form.  KRYST_UNSUPPORTED, *out untouched: PATTERN on an operator without a CSR-P16
+ * form, or whose vectors do not fit 32-bit byte offsets (AUTO keeps the plain arrays alone in both cases); a distributed operator.  An unknown
+ * form: KRYST_ERR_ARG. */
+#define KRYST_CSR32_PLAIN 0
+#define KRYST_CSR32_AUTO 1
+#define KRYST_CSR32_PATTERN 2
+int32_t kryst_csr32_lower_form(kryst_csr_t a, int32_t form, kryst_csr32_t* out);
+/* *kernel: the kernel the next kryst_spmv32 (and every SpMV of the fp32 solvers) takes under the current settings -- 0 the plain wave kernel,
+ * 1 the row-pattern kernel, 2 the row-pattern kernel with the near operands staged in LDS (boxes of lines of n points, n % 4 == 0, uniform far
+ * offsets).  Settings, read at every launch (once per solve inside one): KRYST_SPMV32_FORM = plain | pattern (default: the most compact form
+ * held), KRYST_SPMV32_STAGE = 0 | 1 (default 1). */
+int32_t kryst_csr32_encoding(kryst_csr32_t a, int32_t* kernel);
 /* info[0]: values the rounding changed; info[1]: nonzero values that became zero or fp32-subnormal; info[2]: rows */
 int32_t kryst_csr32_info(kryst_csr32_t a, int64_t info[3]);
 int32_t kryst_csr32_destroy(kryst_csr32_t a);

@@ -379,12 +379,18 @@ def dot32(x, y):
 
 
 class CsrMatrix32:
-    """CsrMatrix<f32> lowered from a CsrMatrix (kryst_csr32_lower): its own copies of the index arrays, the values rounded to fp32."""
+    """CsrMatrix<f32> lowered from a CsrMatrix (kryst_csr32_lower_form): its own copies of the index arrays, the values rounded to fp32.
+    form "plain" keeps the CSR arrays alone; "pattern" also keeps the operator's CSR-P16 row-pattern form with fp32 tables (KError Unsupported
+    when it has none); "auto" keeps it where there is one."""
+    FORMS = {"plain": 0, "auto": 1, "pattern": 2}
+    KERNELS = ("plain", "pattern", "pattern-stage")
 
-    def __init__(self, a):
+    def __init__(self, a, form="plain"):
         self.ctx = a.ctx
         self.h = _ffi.Handle()
-        check(lib().kryst_csr32_lower(a.h, C.byref(self.h)))
+        if form not in self.FORMS:
+            raise KError(102, f"form must be one of {sorted(self.FORMS)}, not {form!r}")
+        check(lib().kryst_csr32_lower_form(a.h, self.FORMS[form], C.byref(self.h)))
         self._nrows, self._ncols, self.nnz = a.nrows(), a.ncols(), a.nnz
 
     def nrows(self):
@@ -399,6 +405,13 @@ class CsrMatrix32:
         i = (C.c_int64 * 3)()
         check(lib().kryst_csr32_info(self.h, i))
         return {"changed": i[0], "tiny": i[1], "rows": i[2]}
+
+    def encoding(self):
+        """The kernel the next spmv (and every SpMV of a solve) takes under the current settings (kryst_csr32_encoding): "plain",
+        "pattern" or "pattern-stage".  KRYST_SPMV32_FORM=plain|pattern and KRYST_SPMV32_STAGE=0|1 steer it."""
+        k = C.c_int32(-1)
+        check(lib().kryst_csr32_encoding(self.h, C.byref(k)))
+        return self.KERNELS[k.value]
 
     def spmv(self, x, y=None):
         """y <- (float)(A x): the row fold in fp64 over the stored order, rounded once.  DeviceVec32 stays on the device; a host array is
@@ -581,9 +594,10 @@ class CsrMatrix:
             at += w
         return out
 
-    def lower(self):
-        """This operator with fp32-stored values (CsrMatrix32; an extension): a copy, with no tie to this one's lifetime."""
-        return CsrMatrix32(self)
+    def lower(self, form="plain"):
+        """This operator with fp32-stored values (CsrMatrix32; an extension): a copy, with no tie to this one's lifetime.  form: "plain"
+        (the CSR arrays), "pattern" (also the CSR-P16 row-pattern form; refused where the operator has none) or "auto"."""
+        return CsrMatrix32(self, form)
 
     ENCODINGS = ("csr", "csr-d8", "csr-d16", "csr-p16", "csr-dia")
 
@@ -1630,9 +1644,19 @@ class RefinementSolver:
         self.inner = Convergence(1e-6, 1000)
         self.residual_history = []
         self._lowered = {}
+        self.form = "plain"
 
     def with_inner(self, tol, max_iters):
         self.inner = Convergence(tol, max_iters)
+        return self
+
+    def with_form(self, form):
+        """How lowered(a) lowers: "plain" (the default), "auto" or "pattern" (CsrMatrix.lower)."""
+        if form not in CsrMatrix32.FORMS:
+            raise KError(102, f"form must be one of {sorted(CsrMatrix32.FORMS)}, not {form!r}")
+        if form != self.form:
+            self._lowered = {}
+        self.form = form
         return self
 
     def clear_history(self):
@@ -1642,7 +1666,7 @@ class RefinementSolver:
         key = id(a)
         hit = self._lowered.get(key)
         if hit is None or hit[0] is not a:
-            hit = (a, a.lower())
+            hit = (a, a.lower(self.form))
             self._lowered[key] = hit
         return hit[1]
 

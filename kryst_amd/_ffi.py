@@ -218,6 +218,8 @@ SIGNATURES = {
     "kryst_vec32_to_f64": (C.c_int32, [Handle, Handle]),
     "kryst_dot32": (C.c_int32, [Handle, Handle, c_dp]),
     "kryst_csr32_lower": (C.c_int32, [Handle, C.POINTER(Handle)]),
+    "kryst_csr32_lower_form": (C.c_int32, [Handle, C.c_int32, C.POINTER(Handle)]),
+    "kryst_csr32_encoding": (C.c_int32, [Handle, C.POINTER(C.c_int32)]),
     "kryst_csr32_info": (C.c_int32, [Handle, c_i64p]),
     "kryst_csr32_destroy": (C.c_int32, [Handle]),
     "kryst_host_round_f32": (C.c_int32, [c_dp, C.c_int64, c_fp, c_i64p]),

@@ -23,6 +23,13 @@ struct kryst_csr32_s {
     int32_t* d_col = nullptr;       // nnz + 8, zeroed tail
     float* d_val = nullptr;         // nnz + 8, zeroed tail
     int64_t changed = 0, tiny = 0;  // values the rounding changed / nonzero values that became zero or fp32-subnormal
+    // the row-pattern form (CSR-P16 with fp32 tables; kryst_csr32_lower_form PATTERN, or AUTO where the operator has one): the operator's own copies
+    uint16_t* d_pid = nullptr;      // ntiles32 * 1024 + 1024 ids, zeroed tail (a lane reads its four ids with one 8-byte load), or nullptr
+    uint32_t* d_pmeta = nullptr;    // 2 words per pattern, as kryst_csr_s::d_pmeta
+    int32_t* d_poff = nullptr;      // table: col - row
+    float* d_pval = nullptr;        // table: (float)value -- bit for bit the rounded CSR value of every row that uses the entry
+    int32_t npat = 0, ntab = 0, pat_unroll = 8; bool pat_single = false;
+    int32_t pat_stage_n = 0, pat_far_lo = 0, pat_far_hi = 0; bool pat_far_uniform = false;
 };
 
 namespace kr {
@@ -33,5 +40,11 @@ inline int64_t vec32_len(int64_t n) { return ntiles32_of(n) * KR32_TILE + KR32_T
 // y <- (float)(A x) on ctx->s_main; nq = 1: also the tile partials of sum_i d[i] * y[i] (y as stored) in the fp32 tree into partial array 0.
 // `done` (device flag) makes the launch a no-op when set.
 int32_t launch_spmv32(kryst_csr32_t a, const float* x, float* y, int nq, const float* dvec, const int* done);
+// the kernel that launch takes under the current settings (KRYST_SPMV32_FORM, KRYST_SPMV32_STAGE): 0 spmv32_wave_kernel on the plain arrays,
+// 1 spmv32_pattern_kernel, 2 spmv32_pattern_stage_kernel.  The ONE place that decides; kryst_csr32_encoding reports it.
+int spmv32_kernel(kryst_csr32_t a);
+// mixed_pattern.hip: the two kernels of the row-pattern form
+int32_t enqueue_spmv32_pattern(kryst_csr32_t a, const float* x, float* y, int nq, const float* dvec, const int* done);
+int32_t enqueue_spmv32_pattern_stage(kryst_csr32_t a, const float* x, float* y, int nq, const float* dvec, const int* done);
 
 }  // namespace kr

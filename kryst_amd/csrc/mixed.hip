@@ -9,6 +9,7 @@
 #include "cg_logic.h"
 #include <cfloat>
 #include <cmath>
+#include <cstring>
 
 namespace kr {
 
@@ -334,11 +335,39 @@ __global__ __launch_bounds__(KR32_T) void spmv32_wave_kernel(const Spmv32Args a)
     }
 }
 
+// KRYST_SPMV32_FORM = plain | pattern: -1 unset (or neither word), 0 plain, 1 pattern.  Read as env_int reads a number: at every launch outside a
+// solve, once per solve inside one (EnvFreeze)
+static int spmv32_form_knob() {
+    static EnvSlot slot;
+    auto parse = [](const char* v) -> long long { return !v ? -1 : !strcmp(v, "plain") ? 0 : !strcmp(v, "pattern") ? 1 : -1; };
+    if (g_env_frozen > 0) {
+        const uint32_t e = g_env_epoch.load(std::memory_order_relaxed);
+        if (slot.epoch.load(std::memory_order_acquire) == e) return (int)slot.val.load(std::memory_order_relaxed);
+        const long long v = parse(getenv("KRYST_SPMV32_FORM"));
+        slot.has.store(1, std::memory_order_relaxed); slot.val.store(v, std::memory_order_relaxed);
+        slot.epoch.store(e, std::memory_order_release);
+        return (int)v;
+    }
+    return (int)parse(getenv("KRYST_SPMV32_FORM"));
+}
+
+// the choice: pattern-stage, then pattern, then plain, from the forms the lowered operator holds and the two settings
+int spmv32_kernel(kryst_csr32_t a) {
+    if (!a->d_pid || spmv32_form_knob() == 0) return 0;
+    const bool stage = a->pat_stage_n > 0 && a->pat_stage_n % 4 == 0 && a->pat_far_uniform && env_int("KRYST_SPMV32_STAGE", 1) != 0;
+    return stage ? 2 : 1;
+}
+
 int32_t launch_spmv32(kryst_csr32_t a, const float* x, float* y, int nq, const float* dvec, const int* done) {
     kryst_ctx_t ctx = a->ctx;
     const int64_t nt = ntiles32_of(a->nrows);
     if (nt <= 0) return KRYST_OK;
     if (nq) KR_TRY(ensure_partials(ctx, nt));
+    if (const int kernel = spmv32_kernel(a)) {
+        KR_TRY(kernel == 2 ? enqueue_spmv32_pattern_stage(a, x, y, nq, dvec, done) : enqueue_spmv32_pattern(a, x, y, nq, dvec, done));
+        phase_mark(ctx, KR_PH_SPMV);
+        return KRYST_OK;
+    }
     const Spmv32Args args{a->d_row_ptr, a->d_col, a->d_val, x, y, dvec, ctx->d_partials, (int)a->nrows, (int)nt, done};
     // LDS: 64 KiB per workgroup (two fit a compute unit); a capped grid that strides the tiles, like the other streaming kernels.  Measured at 256^3,
     // 7-point: windows of 512 / 1024 / 2048 entries per wave 0.50 / 0.43 / 0.38 ms -- the fewer trips through the window loop the better
@@ -379,6 +408,7 @@ static void csr32_free(kryst_csr32_t a) {
     if (!a) return;
     (void)hipStreamSynchronize(a->ctx->s_main);
     (void)hipFree(a->d_row_ptr); (void)hipFree(a->d_col); (void)hipFree(a->d_val);
+    (void)hipFree(a->d_pid); (void)hipFree(a->d_pmeta); (void)hipFree(a->d_poff); (void)hipFree(a->d_pval);
     delete a;
 }
 
@@ -675,12 +705,21 @@ int32_t kryst_dot32(kryst_vec32_t x, kryst_vec32_t y, double* out) {
     return KRYST_OK;
 }
 
-int32_t kryst_csr32_lower(kryst_csr_t a, kryst_csr32_t* out) {
+int32_t kryst_csr32_lower(kryst_csr_t a, kryst_csr32_t* out) { return kryst_csr32_lower_form(a, KRYST_CSR32_PLAIN, out); }
+
+int32_t kryst_csr32_lower_form(kryst_csr_t a, int32_t form, kryst_csr32_t* out) {
     KR_ARG(a && out, "csr32_lower");
+    KR_ARG(form == KRYST_CSR32_PLAIN || form == KRYST_CSR32_AUTO || form == KRYST_CSR32_PATTERN, "csr32_lower: unknown form");
     kryst_ctx_t ctx = a->ctx;
     if (a->dist || ctx->nranks > 1) { set_error("csr32_lower: distributed operators are not supported"); return KRYST_UNSUPPORTED; }
     KR_ARG(a->d_row_ptr && a->d_col && a->d_val, "csr32_lower: the operator keeps no CSR arrays");
     KR_ARG(a->nrows < (1ll << 31) - KR32_TILE && a->nnz < (1ll << 31) - 4096, "csr32_lower: too many rows or entries");
+    // the row-pattern form: the operator must have one, and the kernels address x and y with 32-bit byte offsets
+    const bool has_p16 = a->d_pid && a->d_pmeta && a->d_poff && a->d_pval && a->npat > 0;
+    const bool fits = vec32_len(std::max(a->nrows, a->ncols)) * (int64_t)sizeof(float) < (1ll << 31);
+    if (form == KRYST_CSR32_PATTERN && !has_p16) { set_error("csr32_lower: the operator has no CSR-P16 form"); return KRYST_UNSUPPORTED; }
+    if (form == KRYST_CSR32_PATTERN && !fits) { set_error("csr32_lower: the vectors do not fit 32-bit byte offsets"); return KRYST_UNSUPPORTED; }
+    const bool pattern = form != KRYST_CSR32_PLAIN && has_p16 && fits;
     KR_HIP(hipSetDevice(ctx->device));
     kryst_csr32_t m = new kryst_csr32_s();
     m->ctx = ctx; m->nrows = a->nrows; m->ncols = a->ncols; m->nnz = a->nnz;
@@ -700,6 +739,24 @@ int32_t kryst_csr32_lower(kryst_csr_t a, kryst_csr32_t* out) {
         hipLaunchKernelGGL(lower_values_kernel, dim3(grid_for(a->nnz)), dim3(256), 0, ctx->s_main, m->d_val, a->d_val, a->nnz, d_count);
         e = hipGetLastError();
     }
+    if (e == hipSuccess && pattern) {
+        // ids re-padded to the fp32 tile (the fp64 array is padded to a 512-row tile only); the tables as they are, the values rounded as the CSR values are
+        const size_t nid = (size_t)ntiles32_of(a->nrows) * KR32_TILE + KR32_TILE;
+        e = hipMalloc(&m->d_pid, sizeof(uint16_t) * nid);
+        if (e == hipSuccess) e = hipMalloc(&m->d_pmeta, sizeof(uint32_t) * 2 * (size_t)a->npat);
+        if (e == hipSuccess) e = hipMalloc(&m->d_poff, sizeof(int32_t) * (size_t)std::max(a->ntab, 1));
+        if (e == hipSuccess) e = hipMalloc(&m->d_pval, sizeof(float) * (size_t)std::max(a->ntab, 1));
+        if (e == hipSuccess) e = hipMemsetAsync(m->d_pid, 0, sizeof(uint16_t) * nid, ctx->s_main);
+        if (e == hipSuccess) e = hipMemcpyAsync(m->d_pid, a->d_pid, sizeof(uint16_t) * (size_t)a->nrows, hipMemcpyDeviceToDevice, ctx->s_main);
+        if (e == hipSuccess) e = hipMemcpyAsync(m->d_pmeta, a->d_pmeta, sizeof(uint32_t) * 2 * (size_t)a->npat, hipMemcpyDeviceToDevice, ctx->s_main);
+        if (e == hipSuccess && a->ntab > 0) e = hipMemcpyAsync(m->d_poff, a->d_poff, sizeof(int32_t) * (size_t)a->ntab, hipMemcpyDeviceToDevice, ctx->s_main);
+        if (e == hipSuccess && a->ntab > 0) {
+            hipLaunchKernelGGL(round_kernel, dim3(grid_for(a->ntab)), dim3(256), 0, ctx->s_main, m->d_pval, a->d_pval, (int64_t)a->ntab, 0, 1.0);
+            e = hipGetLastError();
+        }
+        m->npat = a->npat; m->ntab = a->ntab; m->pat_unroll = a->pat_unroll; m->pat_single = a->pat_single;
+        m->pat_stage_n = a->pat_stage_n; m->pat_far_lo = a->pat_far_lo; m->pat_far_hi = a->pat_far_hi; m->pat_far_uniform = a->pat_far_uniform;
+    }
     if (e == hipSuccess) e = hipMemcpyAsync(cnt, d_count, sizeof cnt, hipMemcpyDeviceToHost, ctx->s_main);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->s_main);
     (void)hipFree(d_count);
@@ -718,6 +775,13 @@ int32_t kryst_csr32_info(kryst_csr32_t a, int64_t info[3]) {
     KR_TRY(csr32_check(a));
     KR_ARG(info, "csr32_info");
     info[0] = a->changed; info[1] = a->tiny; info[2] = a->nrows;
+    return KRYST_OK;
+}
+
+int32_t kryst_csr32_encoding(kryst_csr32_t a, int32_t* kernel) {
+    KR_TRY(csr32_check(a));
+    KR_ARG(kernel, "csr32_encoding");
+    *kernel = spmv32_kernel(a);
     return KRYST_OK;
 }
 

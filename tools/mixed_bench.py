@@ -6,12 +6,17 @@
                                                         operator's default encoding, at the same capped iteration counts
   mixed_bench.py refine N [--op ...] [--reps R]         time to tolerance: RefinementSolver (outer 1e-10, inner 1e-6) against fp64 CG / Jacobi-PCG to
                                                         1e-10 on plain CSR and on the default encoding: outer steps, total inner iterations, ms
+  mixed_bench.py pspmv  N                               the row-pattern lowering (CsrMatrix.lower("pattern")): kryst_spmv32 per kernel -- plain, pattern,
+                                                        pattern-stage with runs of 1 and of 2 tiles -- against the fp64 kryst_spmv on the default encoding
+  mixed_bench.py prate  N                               CG32 / PCG32 it/s on the pattern-lowered and on the plain-lowered operator against fp64 CG /
+                                                        Jacobi-PCG on the default encoding (CSR-P16 for the stencil operators)
+  mixed_bench.py prefine N [--reps R]                   RefinementSolver.with_form("pattern") and ("plain") against fp64 CG on the default encoding
 
 The versions ALTERNATE inside the process after a warm-up; every timed window lasts at least half a second (spmv: a run of launches between
 two hipEvents; rate: the difference of two solves at IT and 3 IT iterations with tol = 0, wall clock, IT sized from a calibration solve so that
 2 IT iterations take >= 0.6 s; refine: whole solves, wall clock, lowering and first-use allocations taken out by a warm-up call).  Medians.
 
-Bytes, from shapes: fp64 plain-CSR SpMV 12 nnz + 4 (n + 1) + 16 n; spmv32 8 nnz + 4 (n + 1) + 8 n.  `band`: the non-stencil operator of
+Bytes, from shapes: fp64 plain-CSR SpMV 12 nnz + 4 (n + 1) + 16 n; spmv32 8 nnz + 4 (n + 1) + 8 n; CSR-P16 18 n in fp64 and 10 n in fp32.  `band`: the non-stencil operator of
 tools/multi_rhs_only.py (seven entries per row at jittered offsets, no two rows alike: no compressed form applies)."""
 import argparse
 import json
@@ -221,9 +226,162 @@ def refine_case(name, N, reps, jacobi):
 
 
 
+# ---------------------------------------------------------------------------------------------------------------- the row-pattern lowering
+SPMV32_KNOBS = ("KRYST_SPMV32_FORM", "KRYST_SPMV32_STAGE", "KRYST_SPMV32_STAGE_T")
+SPMV32_KERNELS = {"fp32_plain": ({"KRYST_SPMV32_FORM": "plain"}, "plain"), "fp32_pattern": ({"KRYST_SPMV32_STAGE": "0"}, "pattern"),
+                  "fp32_stage_t1": ({"KRYST_SPMV32_STAGE_T": "1"}, "pattern-stage"), "fp32_stage_t2": ({"KRYST_SPMV32_STAGE_T": "2"}, "pattern-stage")}
+
+
+def knobs32(env):
+    for k in SPMV32_KNOBS:
+        os.environ.pop(k, None)
+    os.environ.update(env)
+
+
+def pspmv_case(name, N, reps):
+    ctx = K.Context(0)
+    a = operator(name, N, ctx)
+    a32 = a.lower("pattern")
+    n, nnz = a.nrows(), a.nnz
+    enc = encoding(a, False)                               # the fp64 yardstick: the operator's own encoding, for the whole case
+    x, y = ctx.vec(n).fill_splitmix(3), ctx.vec(n)
+    x32, y32 = K.DeviceVec32.from_f64(x), K.DeviceVec32(ctx, n)
+    knobs32({})
+    staged = a32.encoding() == "pattern-stage"
+
+    def window(fn, launches, env):
+        knobs32(env)
+        ctx.timer_start()
+        for _ in range(launches):
+            fn()
+        return ctx.timer_stop() / launches
+
+    sides = {"fp64_default": ((lambda: a.spmv(x, y)), {})}
+    for k, (env, kernel) in SPMV32_KERNELS.items():
+        if kernel != "pattern-stage" or staged:
+            knobs32(env)
+            assert a32.encoding() == kernel, (k, a32.encoding())
+            sides[k] = ((lambda: a32.spmv(x32, y32)), env)
+    count = {}
+    for k, (fn, env) in sides.items():
+        window(fn, 20, env)
+        count[k] = max(20, int(math.ceil(WINDOW_S * 1.2 / (window(fn, 50, env) * 1e-3))))
+    r = alternate({k: (lambda k=k: window(sides[k][0], count[k], sides[k][1])) for k in sides}, reps)
+    knobs32({})
+    nbytes = {"fp64_default": 18 * n if enc == "csr-p16" else None, "fp32_plain": 8 * nnz + 4 * (n + 1) + 8 * n}
+    rec = {"case": "pspmv", "op": name, "N": N, "n": n, "nnz": nnz, "windows": reps, "launches_per_window": count, "fp64_encoding": enc,
+           "fp64_pattern_info": a.pattern_info(), "default_kernel": a32.encoding()}
+    for k in sides:
+        b = nbytes.get(k, 10 * n)
+        rec[k + "_ms"] = round(r[k], 5)
+        if b:
+            rec[k + "_bytes_per_row"] = round(b / n, 2)
+            rec[k + "_frac_8TBps"] = round(b / (r[k] * 1e-3) / PEAK, 4)
+        if k != "fp64_default":
+            rec["time_ratio_fp64_over_" + k] = round(r["fp64_default"] / r[k], 3)
+    emit(rec)
+
+
+def prate_case(name, N, reps):
+    ctx = K.Context(0)
+    a = operator(name, N, ctx)
+    lowered = {"fp32_pattern": a.lower("pattern"), "fp32_plain": a.lower()}
+    n = a.nrows()
+    enc = encoding(a, False)
+    knobs32({})
+    b = a.spmv(ctx.vec(n).fill(1.0))
+    b32 = K.DeviceVec32.from_f64(b)
+    x, x32 = ctx.vec(n), K.DeviceVec32(ctx, n)
+    zero32 = np.zeros(n, dtype=np.float32)
+    for method, cls64, cls32 in (("cg", K.CgSolver, K.Cg32Solver), ("pcg_jacobi", K.PcgSolver, K.Pcg32Solver)):
+        pc = K.Jacobi().setup(a) if method != "cg" else None
+
+        def timed(kind, iters):
+            if kind == "fp64_default":
+                x.fill(0.0)
+            else:
+                x32.upload(zero32)
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            st = cls64(0.0, iters).solve(a, pc, b, x) if kind == "fp64_default" else cls32(0.0, iters).solve(lowered[kind], pc, b32, x32)
+            return time.perf_counter() - t0, st.iterations
+
+        rec = {"case": "prate", "op": name, "N": N, "n": n, "method": method, "windows": reps, "fp64_encoding": enc,
+               "fp32_pattern_kernel": lowered["fp32_pattern"].encoding()}
+        kinds = ("fp32_pattern", "fp32_plain", "fp64_default")
+        its, lo, hi = {}, {k: [] for k in kinds}, {k: [] for k in kinds}
+        for kind in kinds:
+            timed(kind, 10)
+            per = max((timed(kind, 60)[0] - timed(kind, 20)[0]) / 40, 1e-6)
+            its[kind] = max(20, int(math.ceil(0.3 / per)))
+        for _ in range(reps):
+            for kind in kinds:
+                lo[kind].append(timed(kind, its[kind]))
+                hi[kind].append(timed(kind, 3 * its[kind]))
+        for kind in kinds:
+            t_lo, t_hi = statistics.median(t for t, _ in lo[kind]), statistics.median(t for t, _ in hi[kind])
+            n_lo, n_hi = lo[kind][0][1], hi[kind][0][1]
+            rec[kind + "_iterations"] = [n_lo, n_hi]
+            rec[kind + "_window_s"] = round(t_hi - t_lo, 4)
+            rec[kind + "_iterations_per_s"] = round((n_hi - n_lo) / (t_hi - t_lo), 2) if n_hi > n_lo and t_hi > t_lo else None
+        for kind in ("fp32_pattern", "fp32_plain"):
+            if rec[kind + "_iterations_per_s"] and rec["fp64_default_iterations_per_s"]:
+                rec["ratio_" + kind + "_over_fp64_default"] = round(rec[kind + "_iterations_per_s"] / rec["fp64_default_iterations_per_s"], 3)
+        emit(rec)
+
+
+def prefine_case(name, N, reps, jacobi):
+    ctx = K.Context(0)
+    a = operator(name, N, ctx)
+    n = a.nrows()
+    enc = encoding(a, False)
+    knobs32({})
+    b = a.spmv(ctx.vec(n).fill_splitmix(7))
+    x = ctx.vec(n)
+    cap = 20000
+    pc = K.Jacobi().setup(a) if jacobi else None
+    fp64 = K.PcgSolver if jacobi else K.CgSolver
+    refs = {form: K.RefinementSolver(1e-10, 40).with_inner(1e-6, cap).with_form(form) for form in ("pattern", "plain")}
+    rec = {"case": "prefine", "op": name, "N": N, "n": n, "inner": "pcg_jacobi" if jacobi else "cg", "outer_tol": 1e-10, "inner_tol": 1e-6,
+           "runs": reps, "fp64_encoding": enc, "kernels": {form: r.lowered(a).encoding() for form, r in refs.items()}}
+
+    def run_refine(form):
+        ref = refs[form]
+        x.fill(0.0)
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        st = ref.solve(a, pc, b, x)
+        ms = (time.perf_counter() - t0) * 1e3
+        rec["refine_" + form] = {"outer_steps": st.iterations, "inner_iterations": st.inner_iterations, "total_inner": sum(st.inner_iterations),
+                                 "converged": st.converged, "final_over_first": ref.residual_history[-1] / ref.residual_history[0]}
+        ref.clear_history()
+        return ms
+
+    def run_fp64():
+        x.fill(0.0)
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        st = fp64(1e-10, cap).solve(a, pc, b, x)
+        ms = (time.perf_counter() - t0) * 1e3
+        rec["fp64_default"] = {"iterations": st.iterations, "converged": st.converged}
+        return ms
+
+    for form, r in refs.items():                           # warm-up: first-use allocations on every path
+        warm = K.RefinementSolver(1e-10, 1).with_inner(1e-6, 5).with_form(form)
+        warm._lowered.update(r._lowered)
+        warm.solve(a, pc, b, ctx.vec(n))
+    fp64(0.0, 5).solve(a, pc, b, ctx.vec(n))
+    ms = alternate({"refine_pattern": lambda: run_refine("pattern"), "fp64_default": run_fp64, "refine_plain": lambda: run_refine("plain")}, reps)
+    for k, v in ms.items():
+        rec[k]["ms"] = round(v, 2)
+    for form in ("pattern", "plain"):
+        rec["time_ratio_fp64_over_refine_" + form] = round(ms["fp64_default"] / ms["refine_" + form], 3)
+    emit(rec)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=("spmv", "rate", "refine"))
+    ap.add_argument("mode", choices=("spmv", "rate", "refine", "pspmv", "prate", "prefine"))
     ap.add_argument("N", type=int)
     ap.add_argument("--op", default="poisson", choices=("poisson", "varcoef", "band"))
     ap.add_argument("--reps", type=int, default=3)
@@ -235,5 +393,11 @@ if __name__ == "__main__":
         spmv_case(args.op, args.N, args.reps)
     elif args.mode == "rate":
         rate_case(args.op, args.N, args.reps)
+    elif args.mode == "pspmv":
+        pspmv_case(args.op, args.N, args.reps)
+    elif args.mode == "prate":
+        prate_case(args.op, args.N, args.reps)
+    elif args.mode == "prefine":
+        prefine_case(args.op, args.N, args.reps, args.jacobi or args.op == "varcoef")
     else:
         refine_case(args.op, args.N, args.reps, args.jacobi or args.op == "varcoef")
