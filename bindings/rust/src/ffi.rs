@@ -225,6 +225,11 @@ extern "C" {
                                               params: *const Params, stats: *mut Stats, hist: *mut f64, hist_cap: i64, hist_len: *mut i64,
                                               monitor: MonitorFn, user: *mut c_void) -> i32;
 
+    // compressed-basis GMRES (extension): basis 0 = fp64 (control), 1 = fp32-stored Krylov basis; sides None and Right; device vectors only
+    pub fn kryst_cbgmres_solve_dev(b: Vecd, x: Vecd, basis: i32, a: Csr, pc: Pc,
+                                   params: *const Params, stats: *mut Stats, hist: *mut f64, hist_cap: i64, hist_len: *mut i64,
+                                   monitor: MonitorFn, user: *mut c_void) -> i32;
+
     pub fn kryst_session_begin(method: i32, b: Vecd, x: Vecd, a: Csr, pc: Pc, params: *const Params, out: *mut Session) -> i32;
     pub fn kryst_session_step(s: Session, k: i64) -> i32;
     pub fn kryst_session_end(s: Session, stats: *mut Stats, hist: *mut f64, hist_cap: i64, hist_len: *mut i64) -> i32;

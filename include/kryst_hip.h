@@ -504,6 +504,18 @@ int32_t kryst_pca_gmres_solve_dev(kryst_vec_t b, kryst_vec_t x, int32_t block_si
  * exact to the column; converged = ||b - A x|| <= tol ||r0|| at a cycle end. */
 int32_t kryst_pca_gmres_textbook_solve_dev(kryst_vec_t b, kryst_vec_t x, int32_t block_size, int32_t pipeline_depth, double tau, KRYST_SOLVE_ARGS);
 
+/* extension (not in the reference): compressed-basis GMRES(restart) -- the Krylov basis V is STORED in fp32 (basis = KRYST_BASIS_F32), everything
+ * else is fp64: the operator (every SpMV encoding as it is), the preconditioner (every kind), z, x, the Hessenberg matrix, all scalars and all
+ * arithmetic.  A basis vector is rounded once, (float) round-to-nearest-even, when it is stored; every later use widens exactly what was stored;
+ * the true residual is recomputed in fp64 at every restart, so the fp32 basis does not cap the attainable accuracy.  KRYST_BASIS_F64 is the control:
+ * the same loop with nothing rounded.  params: tol, max_iters, restart (1..4096), precond_side.  Side 0 or pc == NULL: the loop of
+ * kryst_gmres_solve_dev side 0, statement for statement (with KRYST_BASIS_F64: its bits).  Side 2: TEXTBOOK right preconditioning -- a deviation
+ * from the as-written Right arm of gmres.rs: Arnoldi on A M^-1 from the true residual, v0 = r0 / ||r0||, only V kept, x += M^-1 (sum_j y_j V_j)
+ * with one apply per cycle.  Sides 1 and 3 and contexts of several ranks: KRYST_UNSUPPORTED; basis outside {0, 1}, restart outside 1..4096:
+ * KRYST_ERR_ARG; x untouched on every error.  History: |g[j+1]| per iteration, as kryst_gmres_solve_dev. */
+enum { KRYST_BASIS_F64 = 0, KRYST_BASIS_F32 = 1 };
+int32_t kryst_cbgmres_solve_dev(kryst_vec_t b, kryst_vec_t x, int32_t basis, KRYST_SOLVE_ARGS);
+
 /* ---- stepping session: the same solver split into begin / step / end, so that a caller (bench.py) can
  * enqueue and time exactly K iterations.  method: 0 CgSolver, 1 PcgSolver, 2 BiCgStabSolver, 3 CgsSolver, 4 TfqmrSolver,
  * 5 MinresSolver, 6 QmrSolver, 7 CgnrSolver (all three as written), 8 textbook MINRES, 9 textbook CGNR (extensions).

@@ -601,6 +601,29 @@ protected:
         return rc;
     }
 };
+enum class Basis { F64 = KRYST_BASIS_F64, F32 = KRYST_BASIS_F32 };
+struct CbGmresSolver : TextbookSolverBase {                   // extension: GMRES(restart) with the Krylov basis stored in fp32 (Basis::F64: the control);
+    size_t restart; Basis basis = Basis::F32;                 // NoPc and (textbook) Right only; device form only
+    Preconditioning preconditioning = Preconditioning::Right;
+    CbGmresSolver(size_t restart, double tol, size_t max_iters) : TextbookSolverBase(tol, max_iters), restart(restart) {
+        restart_ = (int)restart; side_ = (int)preconditioning;
+    }
+    CbGmresSolver& with_basis(Basis b) { basis = b; return *this; }
+    CbGmresSolver& with_preconditioning(Preconditioning m) { preconditioning = m; side_ = (int)m; return *this; }
+protected:
+    int32_t call(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS) override {
+        kryst_vec_t bv = nullptr, xv = nullptr;
+        int32_t rc = kryst_vec_create(ctx_h_, n, &bv);
+        if (rc == 0) rc = kryst_vec_create(ctx_h_, n, &xv);
+        if (rc == 0) rc = kryst_vec_upload(bv, b, n);
+        if (rc == 0) rc = kryst_vec_upload(xv, x, n);
+        if (rc == 0) rc = kryst_cbgmres_solve_dev(bv, xv, (int32_t)basis, KRYST_FWD);
+        if (rc == 0) rc = kryst_vec_download(xv, x, n);
+        if (bv) kryst_vec_destroy(bv);
+        if (xv) kryst_vec_destroy(xv);
+        return rc;
+    }
+};
 struct QmrSolver : SolverBase {                              // qmr.rs:61-166 as written (a BiCGStab-type loop)
     QmrSolver(double tol, size_t max_iters) : SolverBase(tol, max_iters) {}
 protected:

@@ -28,7 +28,7 @@ from ._ffi import KError, lib, check
 
 __all__ = ["Context", "DeviceVec", "CsrMatrix", "dot", "norm", "Jacobi", "Ilu0", "Ilup", "Ilut", "TrueIlu0", "Chebyshev",
            "ChebyshevPc", "ChebyshevPoly", "estimate_spectrum", "host_tridiag_extreme_eigs", "IdentityPc", "ApproxInv", "BlockJacobi", "AdditiveSchwarz", "Sor", "MatSorType", "SparsityPattern", "Spai", "Amg", "apply_chebyshev", "Convergence", "SolveStats", "CgNormType",
-           "Preconditioning", "CgSolver", "PcgSolver", "GmresSolver", "FgmresSolver", "PcaGmresSolver", "Orthog", "CgsSolver", "TfqmrSolver", "MinresSolver", "QmrSolver", "CgnrSolver", "CgneSolver", "BiCgStabSolver", "BiCgStabRightPcSolver", "Session", "KspContext", "SolverKind", "PC", "KError", "reduce_spec",
+           "Preconditioning", "CgSolver", "PcgSolver", "GmresSolver", "FgmresSolver", "PcaGmresSolver", "CbGmresSolver", "Orthog", "CgsSolver", "TfqmrSolver", "MinresSolver", "QmrSolver", "CgnrSolver", "CgneSolver", "BiCgStabSolver", "BiCgStabRightPcSolver", "Session", "KspContext", "SolverKind", "PC", "KError", "reduce_spec",
            "host_stencil7", "partition_rows", "halo_recv_plan", "read_matrix_market", "read_petsc_binary", "host_ilup", "host_ilut", "host_amg", "host_levels", "color_graph", "build_blocks_from_colors",
            "DenseMatrix", "LuSolver", "QrSolver", "host_dense_lu", "host_dense_lu_solve", "host_dense_qr_solve",
            "MultiVec", "split_widths",
@@ -1786,6 +1786,33 @@ class PcaGmresSolver(_Solver):
 
     def with_textbook(self):
         self._HOST, self._DEV = None, "kryst_pca_gmres_textbook_solve_dev"
+        return self
+
+
+class CbGmresSolver(_Solver):
+    """LABELLED EXTENSION (not in the reference): GMRES(restart) whose Krylov basis is stored in fp32 -- rounded once
+    when a basis vector is stored, widened exactly at every use -- while the operator, the preconditioner, x, the Hessenberg matrix and all
+    arithmetic stay fp64 and the true residual is recomputed in fp64 at every restart.  with_basis("f64") is the control: the same loop with
+    nothing rounded (NoPc: the bits of GmresSolver).  NoPc, or Right in its textbook form (Arnoldi on A M^-1 from the true residual, only V
+    kept, x += M^-1 (sum y_j V_j) once per cycle); Left and LeftTextbook raise KError(UNSUPPORTED).  One GPU; device form only."""
+    _HOST, _DEV = None, "kryst_cbgmres_solve_dev"
+    BASES = {"f64": 0, "f32": 1}
+
+    def __init__(self, restart, tol, max_iters):
+        super().__init__(tol, max_iters)
+        self.restart = restart
+        self.basis = "f32"
+        self.preconditioning = Preconditioning.Right
+
+    def _extra(self):
+        return (int(self.BASES.get(self.basis, self.basis)),)
+
+    def with_basis(self, basis):
+        self.basis = basis
+        return self
+
+    def with_preconditioning(self, mode):
+        self.preconditioning = mode
         return self
 
 

@@ -155,6 +155,7 @@ SIGNATURES = {
     "kryst_pca_gmres_solve": (C.c_int32, [c_dp, c_dp, C.c_int64, C.c_int32, C.c_int32, C.c_double] + _SOLVE_TAIL),
     "kryst_pca_gmres_solve_dev": (C.c_int32, [Handle, Handle, C.c_int32, C.c_int32, C.c_double] + _SOLVE_TAIL),
     "kryst_pca_gmres_textbook_solve_dev": (C.c_int32, [Handle, Handle, C.c_int32, C.c_int32, C.c_double] + _SOLVE_TAIL),
+    "kryst_cbgmres_solve_dev": (C.c_int32, [Handle, Handle, C.c_int32] + _SOLVE_TAIL),
     "kryst_bicgstab_solve_dev": (C.c_int32, [Handle, Handle] + _SOLVE_TAIL),
     "kryst_bicgstab_rpc_solve_dev": (C.c_int32, [Handle, Handle] + _SOLVE_TAIL),
     "kryst_session_begin": (C.c_int32, [C.c_int32, Handle, Handle, Handle, Handle, C.POINTER(Params), C.POINTER(Handle)]),

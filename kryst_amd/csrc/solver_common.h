@@ -263,6 +263,27 @@ struct Workspace {
         *out = p;
         return KRYST_OK;
     }
+    // an fp32-stored vector (gmres_cb.hip: the compressed basis): half the bytes of a work vector, the same padding rule (whole tiles plus one
+    // spare tile), zero filled.  vecs_for32(count): what `count` of them add to a reserve() call, in work vectors.
+    size_t vec32_bytes() const {
+        const size_t b = sizeof(float) * (size_t)((n + KR_TILE - 1) / KR_TILE * KR_TILE + KR_TILE);
+        return (b + 4095) & ~(size_t)4095;
+    }
+    int64_t vecs_for32(int64_t count) const { return (int64_t)((vec32_bytes() * (size_t)count + vec_bytes() - 1) / vec_bytes()); }
+    int32_t vec32(float** out) {
+        const size_t bytes = vec32_bytes();
+        float* p = nullptr;
+        if (owns_arena && ctx->arena_used + bytes <= ctx->arena_bytes) {
+            p = reinterpret_cast<float*>(ctx->arena + ctx->arena_used);
+            ctx->arena_used += bytes;
+        } else {
+            KR_HIP(hipMalloc(&p, bytes));
+            vecs.push_back(reinterpret_cast<double*>(p));
+        }
+        KR_HIP(hipMemsetAsync(p, 0, bytes, ctx->s_main));
+        *out = p;
+        return KRYST_OK;
+    }
     // history entries kept per solve: max_iters + 2, but never more than this (a caller's "effectively unbounded"
     // max_iters must not turn into gigabytes of pinned memory); the reported length still counts every push
     static constexpr int64_t HIST_MAX = (int64_t)1 << 22;

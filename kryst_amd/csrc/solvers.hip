@@ -766,6 +766,7 @@ SolverRun* make_cgnr_run(kryst_vec_t b, kryst_vec_t x, const SolveIO& io, bool t
 int32_t fgmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32_t orthog, double haptol, int32_t preallocate);   // fgmres.hip
 int32_t pca_gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32_t block_size, int32_t pipeline_depth, double tau,
                         bool textbook);   // pca_gmres.hip
+int32_t cbgmres_solve(kryst_vec_t bv, kryst_vec_t xv, int32_t basis, const SolveIO& io);   // gmres_cb.hip
 
 // ---- one checked reduction through freshly mapped mailboxes (dist.cpp: ipc_reduce_setup) before a solver relies on them: rank r sends
 // r + 1 through the very kernel the inner products use, every rank must read P (P + 1) / 2, and the verdict is agreed through RCCL -- the
@@ -944,6 +945,9 @@ int32_t kryst_pca_gmres_solve(const double* b, double* x, int64_t n, int32_t blo
 }
 int32_t kryst_pca_gmres_textbook_solve_dev(kryst_vec_t b, kryst_vec_t x, int32_t block_size, int32_t pipeline_depth, double tau, KRYST_SOLVE_ARGS) {
     IO_FROM_ARGS; return retry_on_pc_fallback(pc, [&] { return pca_gmres_solve(b, x, io, block_size, pipeline_depth, tau, true); });
+}
+int32_t kryst_cbgmres_solve_dev(kryst_vec_t b, kryst_vec_t x, int32_t basis, KRYST_SOLVE_ARGS) {
+    IO_FROM_ARGS; return retry_on_pc_fallback(pc, [&] { return cbgmres_solve(b, x, basis, io); });
 }
 int32_t kryst_gmres_solve(const double* b, double* x, int64_t n, KRYST_SOLVE_ARGS) {
     IO_FROM_ARGS; return host_solve(b, x, n, io, [](kryst_vec_t bv, kryst_vec_t xv, const SolveIO& i) { return retry_on_pc_fallback(i.pc, [&] { return gmres_solve(bv, xv, i); }); });
