@@ -175,6 +175,14 @@ private:
 // ---- preconditioners --------------------------------------------------------------------------------------------
 class DevicePc : public Preconditioner<HipCsrMatrix, Vec> {
 public:
+    DevicePc() = default;
+    // move-only, like every other handle owner here: a copy would hand the same kryst_pc_t to kryst_pc_destroy twice
+    DevicePc(const DevicePc&) = delete; DevicePc& operator=(const DevicePc&) = delete;
+    DevicePc(DevicePc&& o) noexcept : h_(o.h_), ctx_(o.ctx_) { o.h_ = nullptr; o.ctx_ = nullptr; }
+    DevicePc& operator=(DevicePc&& o) noexcept {
+        if (this != &o) { if (h_) kryst_pc_destroy(h_); h_ = o.h_; ctx_ = o.ctx_; o.h_ = nullptr; o.ctx_ = nullptr; }
+        return *this;
+    }
     ~DevicePc() override { if (h_) kryst_pc_destroy(h_); }
     void apply(const Vec& r, Vec& z) const override {
         if (!h_ || !ctx_) throw KError(KRYST_SOLVE_ERROR);
