@@ -1,5 +1,5 @@
 // The scalar steps of CG (src/solver/cg.rs:127-284) and PCG (src/solver/pcg.rs:133-218): run by thread 0 of the kernel that ends a fold,
-// on the reduced values.  Shared by the single-vector solvers (solvers.hip) and the batched ones (multi.hip), which bind one instance per
+// on the reduced values.  Shared by the single-vector solvers (cg_pcg.hip) and the batched ones (multi.hip), which bind one instance per
 // column to that column's DevState -- the same code, so the same scalars.
 #pragma once
 #include "solver_common.h"

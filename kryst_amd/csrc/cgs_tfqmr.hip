@@ -6,7 +6,7 @@
 //   CGS    3 fused kernels, 15 words  (reference: 8 loops + 3 clones, 29 words)
 //   TFQMR  3 fused kernels, 16 words  (reference: 12 loops + 1 clone, 40 words; its `w` vector and the residual
 //          r - alpha*A(u+q) are never read again -- only the norm of the latter is -- so neither is stored)
-#include "solver_run.h"
+#include "solvers.h"
 
 namespace kr {
 

@@ -169,6 +169,12 @@ void phase_mark_slow(kryst_ctx_t ctx, int phase);                       // ctx.c
 inline void phase_mark(kryst_ctx_t ctx, int phase) { if (ctx->phase) phase_mark_slow(ctx, phase); }
 inline int64_t ntiles_of(int64_t n) { return (n + KR_TILE - 1) / KR_TILE; }
 inline int64_t nchunks_of(int64_t ntiles) { return ntiles > KR_F ? (ntiles + KR_F - 1) / KR_F : 1; }
+// compile-time dispatch of a launch: f is a generic lambda and gets the matching std::integral_constant / std::bool_constant; by_bool hands
+// back what f returns (a launcher's status, or nothing).  Hidden: an instance named after a lambda is no symbol of the library
+#pragma GCC visibility push(hidden)
+template <int... Vs, class F> inline bool by_int(int v, F&& f) { return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...); }
+template <class F> inline auto by_bool(bool b, F&& f) { if (b) return f(std::true_type{}); return f(std::false_type{}); }
+#pragma GCC visibility pop
 
 // ---- device-side reduction primitives (the association order is part of the ABI contract) ----
 #ifdef __HIPCC__

@@ -695,7 +695,7 @@ int32_t kryst_csr_create_dist(kryst_ctx_t ctx, int64_t n_global, const int64_t* 
     rc = agree_on_status(ctx, rc);
     if (rc == KRYST_OK) rc = agree_on_status(ctx, create_dist_exchange(a));
     if (rc == KRYST_OK) {
-        // An exchange of the solvers' direction vector that is started early (solvers.hip: launch_direction) adds one exchange per
+        // An exchange of the solvers' direction vector that is started early (cg_pcg.hip: launch_direction) adds one exchange per
         // iteration on the rank that starts it: EVERY rank must take that decision alike, so it is taken here, once, from what all ranks
         // report (send lists that are contiguous runs on every rank), never from a rank's own tile counts.
         std::vector<int64_t> all;

@@ -283,7 +283,7 @@ int32_t ipc_reduce_setup(kryst_ctx_t ctx) {
                            hipStreamSynchronize(ctx->s_main) != hipSuccess)) rc = KRYST_ERR_HIP;      // (cannot fail on one rank alone in practice: an 8 P byte copy)
     if (rc != KRYST_OK) { ipc_reduce_destroy(ctx); return rc; }
     ctx->ipc_on = true;
-    return ipc_reduce_selftest(ctx);                                 // (solvers.hip: one checked reduction; agreed verdict)
+    return ipc_reduce_selftest(ctx);                                 // (ipc_selftest.hip: one checked reduction; agreed verdict)
 }
 
 static int owner_of(const int64_t* row_offsets, int nranks, int64_t c) {

@@ -20,7 +20,7 @@ int32_t comm_exchange(kryst_ctx_t ctx, const void* send, const int64_t* send_cou
 // Mailbox path of the scalar all-reduce (see kryst_ctx_s): collective over the context's ranks (one all-gather of the IPC
 // handles).  On success ctx->ipc_on is set on EVERY rank, or on none (the outcome is agreed through an all-gather).
 int32_t ipc_reduce_setup(kryst_ctx_t ctx);
-int32_t ipc_reduce_selftest(kryst_ctx_t ctx);          // solvers.hip: one checked reduction over the fresh mailboxes (KRYST_OK / KRYST_UNSUPPORTED on every rank)
+int32_t ipc_reduce_selftest(kryst_ctx_t ctx);          // ipc_selftest.hip: one checked reduction over the fresh mailboxes (KRYST_OK / KRYST_UNSUPPORTED on every rank)
 // one allocation of every rank mapped into this process (hipIpc between processes, directly between ranks of one process); collective,
 // agreed outcome (KRYST_OK everywhere or KRYST_UNSUPPORTED everywhere); `opened` collects the mappings to close with hipIpcCloseMemHandle
 void ipc_close_shared(void* ptr);                       // closes a mapping ipc_map_peers opened (shared between the ranks of a process, counted)

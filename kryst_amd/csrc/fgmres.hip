@@ -10,6 +10,7 @@
 // j+1 subtractions 8 at a time in one read-modify-write of w (10n words for 8 axpys instead of 24n); the last
 // batch also produces ||w||^2.  Per basis vector the step moves 2.4n words against the reference's 5n.
 #include "restart_common.h"
+#include "solvers.h"
 
 namespace kr {
 
@@ -190,7 +191,7 @@ static int32_t dot_batch(kryst_ctx_t ctx, int64_t n, int64_t nt, double* red, co
         for (int k = 0; k < NB; ++k) op.v[k] = v[i0 + (k < cnt ? k : 0)];
         return fg_launch(ctx, op, n, cyc, bpc);
     };
-    if (keep_in_cache(n)) KR_TRY(go(MultiDotOp<NB, true>{})); else KR_TRY(go(MultiDotOp<NB, false>{}));
+    KR_TRY(by_bool(keep_in_cache(n), [&](auto K) { return go(MultiDotOp<NB, K()>{}); }));
     return reduce_then<NB>(ctx, nt, red, FgHcolLogic<NB>{lc, P, i0, cnt});
 }
 template <int NB>
@@ -201,7 +202,7 @@ static int32_t axpy_batch(kryst_ctx_t ctx, int64_t n, const FgPtrs& P, const Cyc
         for (int k = 0; k < NB; ++k) op.v[k] = v[i0 + k];
         return fg_launch(ctx, op, n, cyc);
     };
-    return keep_in_cache(n) ? go(MultiAxpyOp<NB, true>{}) : go(MultiAxpyOp<NB, false>{});
+    return by_bool(keep_in_cache(n), [&](auto K) { return go(MultiAxpyOp<NB, K()>{}); });
 }
 
 int32_t fgmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32_t orthog, double haptol, int32_t preallocate) {
@@ -275,8 +276,7 @@ int32_t fgmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io, int32_t 
             if (orthog == 1)                                                                      // :239-247
                 for (int i = 0; i <= j; ++i) {
                     KR_TRY((reduce_then<1>(ctx, nt, ws.red, FgCorrLogic{lc, P})));
-                    if (keep_in_cache(n)) KR_TRY(fg_launch(ctx, RefineLinkOp<true>{fs, V[i], i < j ? V[i + 1] : nullptr, w}, n, cyc));
-                    else KR_TRY(fg_launch(ctx, RefineLinkOp<false>{fs, V[i], i < j ? V[i + 1] : nullptr, w}, n, cyc));
+                    KR_TRY(by_bool(keep_in_cache(n), [&](auto K) { return fg_launch(ctx, RefineLinkOp<K()>{fs, V[i], i < j ? V[i + 1] : nullptr, w}, n, cyc); }));
                 }
             KR_TRY((reduce_then<1>(ctx, nt, ws.red, FgNormLogic{lc, P, j, haptol})));
             KR_TRY(fg_launch(ctx, NextBasisOp{fs, w, V[j + 1]}, n, cyc, 4));                   // :255-261 (fp64 divisions: 4 workgroups per CU)

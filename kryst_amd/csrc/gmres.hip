@@ -8,6 +8,7 @@
 // Each link is ONE pass over HBM:  z <- z - h_i B_i  fused with the next link's dot (z, B_{i+1})  (4n words
 // instead of the reference's 5n); the last link fuses ||z||^2.
 #include "gmres_common.h"
+#include "solvers.h"
 
 namespace kr {
 
@@ -121,8 +122,7 @@ int32_t gmres_solve(kryst_vec_t bv, kryst_vec_t xv, const SolveIO& io) {
                     KR_TRY((reduce_then<1>(ctx, nt, ws.red, GmHLogic{lc, P, i, j, sweep})));
                     const bool last = (sweep == 1 && i == j);
                     const double* nxt = last ? nullptr : (i < j ? B[i + 1] : B[0]);                    // last link: ||z||^2 (:97)
-                    if (keep_in_cache(n)) KR_TRY(launch_iter(ctx, MgsLinkOp<true>{&P.gs->hcur, B[i], nxt, zz}, n, cyc));
-                    else KR_TRY(launch_iter(ctx, MgsLinkOp<false>{&P.gs->hcur, B[i], nxt, zz}, n, cyc));
+                    KR_TRY(by_bool(keep_in_cache(n), [&](auto K) { return launch_iter(ctx, MgsLinkOp<K()>{&P.gs->hcur, B[i], nxt, zz}, n, cyc); }));
                 }
             KR_TRY((reduce_then<1>(ctx, nt, ws.red, GmNormLogic{lc, P, j})));
             // v_{j+1} = z / h[j+1][j] (:102-103 / :304-306 / :336-341); skipped once the cycle is left

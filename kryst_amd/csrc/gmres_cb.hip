@@ -14,6 +14,7 @@
 // iteration, against 2(j+1) links).  Side 0 keeps the fused first dot of launch_spmv(a, v, w, 1, v_0): the cycle's first store pass writes its
 // widened copy into a vector of its own, which stays for the cycle.  Side 2 takes that dot in a pass of its own (CbDotOp) and keeps no such copy.
 #include "gmres_common.h"
+#include "solvers.h"
 
 namespace kr {
 
@@ -169,8 +170,7 @@ static int32_t cb_run(RestartRun& run, int side, kryst_pc_t pc) {
                     KR_TRY((reduce_then<1>(ctx, nt, ws.red, GmHLogic{lc, P, i, j, sweep})));
                     const bool last = (sweep == 1 && i == j);
                     const T* nxt = last ? nullptr : (i < j ? V[i + 1] : V[0]);                        // last link: ||z||^2 (:97)
-                    if (keep) KR_TRY(launch_iter(ctx, CbLinkOp<true, T>{&P.gs->hcur, V[i], nxt, zz}, n, cyc, word));
-                    else KR_TRY(launch_iter(ctx, CbLinkOp<false, T>{&P.gs->hcur, V[i], nxt, zz}, n, cyc, word));
+                    KR_TRY(by_bool(keep, [&](auto K) { return launch_iter(ctx, CbLinkOp<K(), T>{&P.gs->hcur, V[i], nxt, zz}, n, cyc, word); }));
                 }
             KR_TRY((reduce_then<1>(ctx, nt, ws.red, GmNormLogic{lc, P, j})));
             // v_{j+1} = store(z / h[j+1][j]) (:102-103) and its widened copy for the next SpMV / apply; skipped once the cycle is left

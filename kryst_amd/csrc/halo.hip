@@ -78,7 +78,7 @@ void halo_peer_destroy(kryst_csr_t a) {
     for (void* q : hp.opened) ipc_close_shared(q);
     hp.opened.clear();
     // A landing buffer that a rank THREAD of this process stores into by raw pointer (no hipIpc mapping keeps the memory alive for it) outlives
-    // the operator: a slower neighbour's last early push (solvers.hip: launch_direction) may still be queued when this rank destroys its
+    // the operator: a slower neighbour's last early push (cg_pcg.hip: launch_direction) may still be queued when this rank destroys its
     // operator.  It is freed with the context (ctx.cpp), after the streams of every rank of a rehearsal have drained.
     if (hp.landing && hp.sibling) { a->ctx->deferred_free.push_back(hp.landing); hp.landing = nullptr; }
     (void)hipFree(hp.landing); (void)hipFree(hp.d_push); (void)hipFree(hp.d_pull); (void)hipFree(hp.d_ticket);

@@ -13,7 +13,7 @@
 //   CGNR as written    3 SpMVs (A p, A(Ap), A r), 2 vector kernels, 3 folds, 9 words
 //   textbook MINRES    1 SpMV, 2 vector kernels, 2 folds, 12 words
 //   textbook CGNR      2 SpMVs (A p, A^T r), 2 vector kernels, 3 folds, 9 words
-#include "solver_run.h"
+#include "solvers.h"
 
 namespace kr {
 

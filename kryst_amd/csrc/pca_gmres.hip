@@ -25,6 +25,7 @@
 // into the first update (pass B), the first Gram matrix into the second update (pass C), the second Gram matrix into the first
 // triangular solve (pass D); pass E writes the new basis vectors.  The scalar work runs in one-thread logic kernels.
 #include "restart_common.h"
+#include "solvers.h"
 
 namespace kr {
 

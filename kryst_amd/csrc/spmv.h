@@ -71,9 +71,7 @@ inline StagedLds staged_lds(kryst_csr_t a, int windows, int entry_bytes, int red
     const size_t red_off = (tab + 15) & ~(size_t)15;
     return StagedLds{red_off, red_off + sizeof(double) * (size_t)red_copies * (size_t)T * (size_t)nq * (KR_T / 64)};
 }
-// compile-time dispatch of a launch: f is a generic lambda and gets the matching std::integral_constant / std::bool_constant
-template <int... Vs, class F> inline bool by_int(int v, F&& f) { return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...); }
-template <class F> inline void by_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+// compile-time dispatch of a launch (common.h: by_int / by_bool)
 template <class F> inline int32_t by_nq(int nq, F&& f) {          // the fused inner products of a tile launch: nq = 0, 1, 2
     if (!by_int<0, 1, 2>(nq, f)) { set_error("spmv: nq=%d", nq); return KRYST_ERR_ARG; }
     KR_HIP(hipGetLastError()); return KRYST_OK;

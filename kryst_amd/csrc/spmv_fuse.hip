@@ -30,7 +30,7 @@ __device__ __forceinline__ unsigned pid_same_word(const SpmvArgs& a, const int32
 //   done: the solve has ended -- only the owed x update happens, nothing else is touched.
 struct FuseArgs { const double* z; const double* p_old; double* p_new; double* xvec; const double* alpha; const double* beta; const long long* xpend; long long it; };
 // NMAX: the line length the instance is built for (the window's pairs per lane are a compile-time count): 512 or 1024
-// XU: the deferred x update rides on this kernel (false: the solver updates x in batches, solvers.hip: XBatchOp -- no registers held for x)
+// XU: the deferred x update rides on this kernel (false: the solver updates x in batches, cg_pcg.hip: XBatchOp -- no registers held for x)
 // (measured and not kept, round 5: runs of 8 tiles -- 166 registers, 3 waves per SIMD: 582-590 against 596 it/s; amdgpu_waves_per_eu(5): four
 // spilled registers, 565 against 596)
 //
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(KR_T) void spmv_pattern_fuse_kernel(const SpmvArgs 
     }
 }
 
-// CG's residual pass WITHOUT a stored A p (KRYST_CG_RECOMPUTE_AP; solvers.hip: CgRun::iterate).  The marching fused kernel above writes A p only to
+// CG's residual pass WITHOUT a stored A p (KRYST_CG_RECOMPUTE_AP; cg_pcg.hip: CgRun::iterate).  The marching fused kernel above writes A p only to
 // carry it across the point where alpha is folded: 8 bytes per row written and 8 read back by CgResidualOp.  This kernel forms A p AGAIN from the
 // direction vector that kernel has just stored -- the very doubles it had in its windows, the same e[0 .. 6], table values, absent-entry selects and
 // un-fused multiply and add from 0.0, so the same bits -- and goes on as CgResidualOp does: r -= alpha Ap (cg.rs:210-212), the tile partial of (r, r)
@@ -605,7 +605,7 @@ static RecomputePlan recompute_plan(kryst_csr_t a) {
     if (!(q.m.eligible && q.m.on)) return q;
     q.lds = staged_lds(a, 3, 8, 2, q.m.T, 1);
     if (q.lds.bytes > ((size_t)(160 << 10) / 2 - 512)) return q;
-    // (8: CG's default batch length in the fused form, solvers.hip: cg_x_batch; the solver also checks the length it really took)
+    // (8: CG's default batch length in the fused form, cg_pcg.hip: cg_x_batch; the solver also checks the length it really took)
     q.on = env_int("KRYST_CG_X_BATCH", 8) > 1 && env_int("KRYST_CG_RECOMPUTE_AP", beyond_fuse_min_bytes(a) ? 1 : 0) != 0;
     return q;
 }

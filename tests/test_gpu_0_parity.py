@@ -1124,7 +1124,7 @@ def _check_solver(res, stats, solver, x, exact=True):
 @pytest.mark.parametrize("N", [4, 12, 24])
 @pytest.mark.parametrize("norm", [K.CgNormType.Unpreconditioned, K.CgNormType.Natural, K.CgNormType.NoNorm])
 def test_cg_bit_exact(ctx, rs, N, norm, defer_x, monkeypatch):
-    """defer_x: x += alpha p riding on the direction pass (the default; solvers.hip) or done where the reference does it -- same bits."""
+    """defer_x: x += alpha p riding on the direction pass (the default; cg_pcg.hip) or done where the reference does it -- same bits."""
     monkeypatch.setenv("KRYST_CG_DEFER_X", defer_x)
     a = O.stencil7(N)
     b = a.spmv(np.ones(a.nrows))
@@ -1256,6 +1256,32 @@ def test_direction_pass_inside_the_spmv_on_every_exit_path(ctx, rs, fuse, xbatch
             sess.step(res.iterations + 7)
             st = sess.end()
         assert st.iterations == res.iterations and st.converged and np.array_equal(xs.to_host(), res.x)
+
+
+def test_knobs_flipped_between_session_steps_on_the_unfused_form(ctx, rs, monkeypatch):
+    """The unfused CG / Jacobi-PCG iteration reads KRYST_CG_DEFER_X and KRYST_KEEP_BYTES again in every step of a session (the A/B tools flip
+    them there): a session of 2 + 3 + 2 iterations whose steps alternate between the deferred and the eager x update, and one whose steps
+    alternate between keeping r / z in cache and streaming it, leave x and the residual history of 7 reference iterations."""
+    monkeypatch.setenv("KRYST_CG_FUSE_P", "0"); monkeypatch.setenv("KRYST_CG_X_BATCH", "1")
+    a = O.stencil7(9, "aniso"); d = to_dev(ctx, a)
+    b = O.splitmix64_uniform(0xD0E, a.nrows)
+
+    def put(knob, value):
+        if value is None: monkeypatch.delenv(knob, raising=False)
+        else: monkeypatch.setenv(knob, value)
+
+    for method, opc, kpc in (("cg", None, None), ("pcg", O.Pc.jacobi(a), K.Jacobi().setup(d))):
+        res = O.solve(method, a, b, pc=opc, tol=1e-30, max_iters=7, rs=rs)
+        for knob, values in (("KRYST_CG_DEFER_X", ("1", "0", "1")), ("KRYST_KEEP_BYTES", (None, "0", None))):
+            xs, bs = K.DeviceVec(ctx, np.zeros(a.nrows)), K.DeviceVec(ctx, b)
+            put(knob, values[0])
+            with K.Session(method, d, kpc, bs, xs, tol=1e-30, max_iters=1000) as sess:
+                for q, value in zip((2, 3, 2), values):
+                    put(knob, value)
+                    sess.step(q)
+                st = sess.end()
+            put(knob, None)
+            assert st.iterations == 7 and np.array_equal(xs.to_host(), res.x) and np.array_equal(np.array(sess.residual_history), res.history), (method, knob)
 
 
 def test_pcg_with_chebyshev_extension_bit_exact(ctx, rs):

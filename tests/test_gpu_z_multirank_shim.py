@@ -36,7 +36,7 @@ def _build_shim():
                                                  # peer-store halo exchange and the mailboxes between five ranks
                                                  (5, 20, "poisson", "0+light"), (5, 3000, "random", "0+light"),
                                                  # "+ring": CG / PCG keep their direction vectors in a ring and pay x in batches of 3 iterations
-                                                 # (solvers.hip: CgDirectionRingOp + XBatchOp; by default only for vectors beyond 32 MiB) -- with the
+                                                 # (cg_pcg.hip: CgDirectionRingOp + XBatchOp; by default only for vectors beyond 32 MiB) -- with the
                                                  # early halo start of the NEW direction vector, on P16 / DIA / general operators
                                                  (2, 12, "poisson", "0+ring"), (4, 48, "poisson", "0+light+ring"), (3, 40, "varcoef", "0+light+ring"),
                                                  (5, 3000, "random", "0+light+ring")])
