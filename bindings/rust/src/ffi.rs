@@ -114,6 +114,7 @@ extern "C" {
     pub fn kryst_csr_pattern_info(a: Csr, info: *mut i64) -> i32;
     pub fn kryst_csr_fuse_march_info(a: Csr, info: *mut i64) -> i32;
     pub fn kryst_csr_pid_reuse_info(a: Csr, info: *mut i64) -> i32;
+    pub fn kryst_csr_leg_values_info(a: Csr, info: *mut i64, values: *mut f64) -> i32;
     pub fn kryst_csr_download(a: Csr, row_ptr: *mut i64, col_idx_local: *mut i32, vals: *mut f64) -> i32;
     pub fn kryst_csr_placement_info(a: Csr, tries: *mut i32, chosen: *mut i32, skeleton_ms8: *mut f64) -> i32;
 

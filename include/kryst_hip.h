@@ -172,6 +172,12 @@ int32_t kryst_csr_fuse_march_info(kryst_csr_t a, int64_t* info);
  * way).  info[0] 1 if a marching launch would be handed the table now, info[1] tiles flagged as repeating, info[2] tiles the table covers
  * (info[1], info[2] 0 for an operator without a table).  info: 3 values */
 int32_t kryst_csr_pid_reuse_info(kryst_csr_t a, int64_t* info);
+/* measurement hook: the step of CG's recompute residual pass.  On an operator whose every leg (table position of the seven-leg base) carries one
+ * value in every row pattern that has it -- a constant-coefficient stencil -- the kernel takes the seven values as kernel arguments and keeps a row
+ * pair's presence masks in registers instead of looking values up per entry (KRYST_SPMV_LEG_VALUES = 0: the table look-ups; the same bits either
+ * way).  info[0] 1 if the operator has one value per leg, info[1] 1 if a recompute residual pass would now take them as arguments (the marching mode
+ * and KRYST_CG_RECOMPUTE_AP on); values[0 .. 6] the leg values (+0.0 throughout when info[0] is 0).  info: 2 values, values: 7 */
+int32_t kryst_csr_leg_values_info(kryst_csr_t a, int64_t* info, double* values);
 int32_t kryst_csr_download(kryst_csr_t a, int64_t* row_ptr, int32_t* col_idx_local, double* vals);
 /* Measurement hook (ABI 5): where the CSR arrays live.  The same plain-CSR stream mix runs at 0.70 .. 0.76 of the HBM peak depending on where
  * the driver put the three arrays (round 4, 512^3), so a single-rank creation may try several homes for (row_ptr, col, val) -- K =

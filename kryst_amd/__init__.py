@@ -632,6 +632,16 @@ class CsrMatrix:
         return {"eligible": bool(info[0]), "on": bool(info[1]), "T": info[2], "strips": info[3], "S": info[4], "segments": info[5],
                 "recompute_ap": bool(info[6]), "pid_reuse": bool(reuse[0]), "pid_same_tiles": reuse[1], "tiles": reuse[2]}
 
+    def leg_values_info(self):
+        """Measurement hook (kryst_csr_leg_values_info): the step of CG's recompute residual pass -- {"eligible": every leg of the seven-leg base
+        carries one value wherever a row pattern has it, "on": a recompute residual pass would now take the seven values as kernel arguments
+        (KRYST_SPMV_LEG_VALUES; the marching mode and KRYST_CG_RECOMPUTE_AP on), "values": the seven leg values (0.0 throughout when not
+        eligible)}."""
+        info = (C.c_int64 * 2)()
+        vals = (C.c_double * 7)()
+        check(lib().kryst_csr_leg_values_info(self.h, info, vals))
+        return {"eligible": bool(info[0]), "on": bool(info[1]), "values": [vals[u] for u in range(7)]}
+
     def placement_info(self):
         """Where the CSR arrays live (kryst_csr_placement_info): {"tries", "chosen", "skeleton_ms": [...]} of the homes tried at creation."""
         t, c = C.c_int32(0), C.c_int32(0)

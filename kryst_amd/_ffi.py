@@ -86,6 +86,7 @@ SIGNATURES = {
     "kryst_csr_pattern_info": (C.c_int32, [Handle, C.POINTER(C.c_int64)]),
     "kryst_csr_fuse_march_info": (C.c_int32, [Handle, C.POINTER(C.c_int64)]),
     "kryst_csr_pid_reuse_info": (C.c_int32, [Handle, C.POINTER(C.c_int64)]),
+    "kryst_csr_leg_values_info": (C.c_int32, [Handle, C.POINTER(C.c_int64), c_dp]),
     "kryst_bench_spmv": (C.c_int32, [Handle, Handle, Handle, C.c_int32, C.c_int32, c_dp]),
     "kryst_bench_streams": (C.c_int32, [Handle, C.c_int64, C.c_int64, C.c_int32, C.c_int32, c_dp]),
     "kryst_bench_csr_skeleton": (C.c_int32, [Handle, Handle, Handle, C.c_int32, c_dp]),

@@ -32,6 +32,10 @@ struct kryst_csr_s {
     bool pat_far_interior = false;  // ... at least in the rows of interior tiles (generator-made distributed operator)
     int32_t pat_far_lo = 0, pat_far_hi = 0; bool pat_far_uniform = false;   // table positions 0 / 6 are the same offsets in every base (a whole box on one rank)
     int32_t pat_stage_n = 0;       // > 0: every base is (far, -n, -1, 0, +1, +n, far) with one even n <= 1024 -- the near operands of a run of tiles can be staged in LDS (spmv_pattern_stage_kernel)
+    // the staged form with ONE value per leg: wherever a pattern has leg u (table position u of its base, mask bit u) the value is pat_leg[u], bit for
+    // bit (+0.0 for a leg no pattern has) -- a constant-coefficient stencil, whose boundary rows are the interior row with entries removed.  The
+    // recompute residual pass then takes the seven values as kernel arguments (csr_create.hip: set_leg_values; spmv_fuse.hip: KRYST_SPMV_LEG_VALUES)
+    bool pat_leg_ok = false; double pat_leg[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     bool pat_diag3 = false;        // stencil generator: every row has its diagonal, at table position 3 of its base   // table entries padded per pattern to a multiple of pat_unroll
     // CSR-DIA: operators with at most KR_DIA_MAX = 32 distinct (col - row) offsets that fill their diagonals (any stencil on a structured
     // grid, variable coefficients included): the values as ONE stream per diagonal in natural row order, absent entries marked by

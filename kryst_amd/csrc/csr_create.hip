@@ -17,6 +17,27 @@ static int32_t h2d(kryst_ctx_t ctx, void* dst, const void* src, size_t bytes) {
     return KRYST_OK;
 }
 
+// CSR-P16, the staged form (pat_stage_n > 0: every base has seven legs): does every leg carry ONE value?  For every pattern of non-zero length and
+// every leg u its mask has, the bits of pval[base + u] must be those of leg[u], which the first pattern that has the leg sets (+0.0: no pattern has
+// it).  Decided once, on the host, from the tables both creation paths hold; sets a->pat_leg_ok and a->pat_leg (csr.h).
+static void set_leg_values(kryst_csr_t a, const std::vector<uint32_t>& meta, const std::vector<double>& pval) {
+    a->pat_leg_ok = false;
+    for (int u = 0; u < 7; ++u) a->pat_leg[u] = 0.0;
+    if (a->pat_stage_n <= 0) return;
+    bool have[7] = {false, false, false, false, false, false, false};
+    for (size_t p = 0; p + 1 < meta.size(); p += 2) {
+        const size_t b = meta[p] & 0xffffu; const int len = (int)(meta[p] >> 16);
+        if (len == 0) continue;
+        if (len != 7 || b + 7 > pval.size() || (meta[p + 1] >> 7)) return;
+        for (int u = 0; u < 7; ++u) {
+            if (!((meta[p + 1] >> u) & 1u)) continue;
+            if (!have[u]) { a->pat_leg[u] = pval[b + u]; have[u] = true; }
+            else if (memcmp(&a->pat_leg[u], &pval[b + u], 8) != 0) { for (int v = 0; v < 7; ++v) a->pat_leg[v] = 0.0; return; }
+        }
+    }
+    a->pat_leg_ok = true;
+}
+
 // CSR-P16: number the distinct rows (as sequences of (col - row, value bits)); give up as soon as the tables outgrow LDS
 static int32_t upload_patterns(kryst_csr_t a, const std::vector<uint16_t>& pid, const std::vector<uint32_t>& meta /* 2 words per pattern */,
                                const std::vector<int32_t>& poff, const std::vector<double>& pval) {
@@ -58,6 +79,7 @@ static int32_t upload_patterns(kryst_csr_t a, const std::vector<uint16_t>& pid, 
             else a->pat_far_uniform = poff[b] == a->pat_far_lo && poff[b + 6] == a->pat_far_hi;
         }
     }
+    set_leg_values(a, meta, pval);
     return KRYST_OK;
 }
 static int32_t build_patterns(kryst_csr_t a, const std::vector<int32_t>& rp, const std::vector<int32_t>& col, const double* val) {
@@ -861,6 +883,7 @@ static int32_t create_stencil7_device(kryst_ctx_t ctx, int32_t N, int32_t kind, 
             a->pat_stage_n = (N >= 8 && N <= 1024 && N % 2 == 0) ? N : 0;
             a->pat_far_uniform = a->pat_stage_n > 0 && !dist; a->pat_far_lo = (int32_t)-N2; a->pat_far_hi = (int32_t)N2;
             a->pat_far_interior = a->pat_stage_n > 0;                // rows of INTERIOR tiles (no halo columns) all have the far offsets -N^2 / +N^2
+            set_leg_values(a, meta, pval);
             (void)hipMemsetAsync(a->d_pid, 0, sizeof(uint16_t) * (size_t)((nloc + KR_TILE - 1) / KR_TILE * KR_TILE + KR_TILE), ctx->s_main);
         }
         (void)hipMemsetAsync(a->d_col + nnz, 0, sizeof(int32_t) * 8, ctx->s_main);

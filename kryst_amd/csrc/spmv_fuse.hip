@@ -414,8 +414,21 @@ __global__ __launch_bounds__(KR_T) void spmv_pattern_fuse_kernel(const SpmvArgs 
 //   621 -> 576 us (26.5 -> 24.5 bytes per row).
 //   a.group: strips per XCD; a.xcd_chunk: S; a.tpw: strips per plane; every strip and every plane is whole, so every row of a strip is a row of the box.
 // KEEP: r is stored temporal (keep_in_cache: the next launch reads it again out of the Infinity Cache), as CgResidualOp<KEEP> does.
-template <int T, bool KEEP>
-__global__ __launch_bounds__(KR_T) void cg_recompute_residual_kernel(const SpmvArgs a, const double* p, double* r, const double* alpha, const int32_t n, const int32_t plane) {
+// LEG (KRYST_SPMV_LEG_VALUES; csr.h: pat_leg_ok, csr_create.hip: set_leg_values).  On an operator with one value per leg the value of entry u is the same
+// double in every pattern that has leg u, so step b. needs no table: the seven values arrive BY VALUE in the kernel arguments (uniform: the compiler keeps
+// them in scalar registers) and a lane keeps, per tile, the two rows' presence masks as one word, ka | kb << 8 (seven legs: a mask fits a byte), IN PLACE
+// of the tile's ids.  The word is formed out of meta when a tile's ids arrive -- a segment's first plane, and the hand-over at a step's end where the
+// pid_same flag is clear (with KRYST_SPMV_PID_REUSE = 0: every plane) -- and carried where the ids repeat.  Per tile step b. then issues its 6 window
+// reads and nothing else: no meta[id] reads with the table reads behind them (2 + 14 LDS reads, 128 of 224 bytes per lane, two dependent LDS latencies
+// in front of the arithmetic).  A present entry multiplies by the same double, an absent one is dropped by the same select, the order is the same: the
+// same bits.  Measured at 512^3 (profiles/march_step/): 152 VGPRs instead of 168 at T = 4, the residual pass 576 -> 554 us at the same 24.5 bytes per row
+// (5.71 -> 5.94 TB/s, the rate of the plain streams), CG 676 -> 690 it/s.  The fused kernel above keeps its table and its two barriers: with the same
+// step it ran at 601 against 599 us and CG lost 10 it/s, and on three windows and one barrier per step (this kernel's schedule) at 626 against 609 us
+// -- neither was kept.  (Its table reads hide behind the window reads only because meta[id] is read FIRST: read behind them, the step costs 100 us.)
+struct LegVals { double v[7]; };
+__device__ __forceinline__ unsigned leg_mask_word(const uint2* meta, const unsigned ids) { return (meta[ids & 0xffffu].y & 0xffu) | ((meta[ids >> 16].y & 0xffu) << 8); }
+template <int T, bool KEEP, bool LEG>
+__global__ __launch_bounds__(KR_T) void cg_recompute_residual_kernel(const SpmvArgs a, const double* p, double* r, const double* alpha, const int32_t n, const int32_t plane, const LegVals lv) {
     if (a.done && *a.done) return;                                           // (GateDone: alpha's logic may have ended the solve)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int XS = T * KR_TILE + 2 * n + 4;                                  // elements of one window (even)
@@ -474,13 +487,17 @@ __global__ __launch_bounds__(KR_T) void cg_recompute_residual_kernel(const SpmvA
 #pragma unroll
     for (int k = 0; k < T; ++k) { prev[k] = far_pair((int64_t)rbeg + k * KR_TILE + 2 * t - plane); hi[k].x = 0.0; hi[k].y = 0.0; }
     for (int i = t; i < a.npat; i += KR_T) meta[i] = reinterpret_cast<const uint2*>(a.pmeta)[i];
-    for (int i = t; i < a.ntab; i += KR_T) pval[i] = a.pval[i];
+    if constexpr (!LEG) for (int i = t; i < a.ntab; i += KR_T) pval[i] = a.pval[i];     // (LEG: no table value is read)
     write_window(w0);
     if (ns > 1) {
         request(rbeg + plane);
         write_window(w1);
     }
     __syncthreads();
+    if constexpr (LEG) {                                                     // the ids of the segment's first plane have arrived: ids[k] is the mask word from here on
+#pragma unroll
+        for (int k = 0; k < T; ++k) ids[k] = leg_mask_word(meta, ids[k]);
+    }
     for (int s = 0; s < ns; ++s) {
         const int32_t r0 = rbeg + s * plane;
         const bool last = s + 1 == ns, fill = s + 2 < ns;                   // (uniform)
@@ -503,7 +520,8 @@ __global__ __launch_bounds__(KR_T) void cg_recompute_residual_kernel(const SpmvA
 #pragma unroll
         for (int k = 0; k < T; ++k) {
             const int32_t row = r0 + k * KR_TILE + 2 * t;
-            const uint2 ma = meta[ids[k] & 0xffffu], mb = meta[ids[k] >> 16];
+            uint2 ma = make_uint2(0u, ids[k] & 0xffu), mb = make_uint2(0u, ids[k] >> 8);     // (LEG: the masks out of the tile's word, no table)
+            if constexpr (!LEG) { ma = meta[ids[k] & 0xffffu]; mb = meta[ids[k] >> 16]; }
             const int j = k * KR_TILE + 2 * t + n + 2;                       // w0[j] = p[row], w1[j] = p[row + plane]
             const v2d A = *reinterpret_cast<const v2d*>(w0 + j - 2), B = *reinterpret_cast<const v2d*>(w0 + j), C = *reinterpret_cast<const v2d*>(w0 + j + 2);
             const v2d M = *reinterpret_cast<const v2d*>(w0 + j - n), P = *reinterpret_cast<const v2d*>(w0 + j + n);
@@ -517,7 +535,8 @@ __global__ __launch_bounds__(KR_T) void cg_recompute_residual_kernel(const SpmvA
             double s0 = 0.0, s1 = 0.0;
 #pragma unroll
             for (int u = 0; u < 7; ++u) {
-                const double ta = s0 + tva[u] * e[u].x, tb = s1 + tvb[u] * e[u].y;
+                const double va = LEG ? lv.v[u] : tva[u], vb = LEG ? lv.v[u] : tvb[u];
+                const double ta = s0 + va * e[u].x, tb = s1 + vb * e[u].y;
                 s0 = ((ka >> u) & 1u) ? ta : s0;
                 s1 = ((kb >> u) & 1u) ? tb : s1;
             }
@@ -540,7 +559,7 @@ __global__ __launch_bounds__(KR_T) void cg_recompute_residual_kernel(const SpmvA
             a.partials[r0 / KR_TILE + t] = sum;
         }
 #pragma unroll
-        for (int k = 0; k < T; ++k) { if (!((sw >> (8 * k)) & 1u)) ids[k] = idn[k]; rr[k] = rn[k]; }
+        for (int k = 0; k < T; ++k) { if (!((sw >> (8 * k)) & 1u)) ids[k] = LEG ? leg_mask_word(meta, idn[k]) : idn[k]; rr[k] = rn[k]; }     // (LEG: the new ids become the mask word)
         same = samen;
         double* w = w0; w0 = w1; w1 = w2; w2 = w;
     }
@@ -614,6 +633,10 @@ bool spmv_can_recompute_ap(kryst_csr_t a) { return spmv_can_fuse_direction(a) &&
 // d_pid_same; on a box with constant coefficients every plane but the first two and the last).  KRYST_SPMV_PID_REUSE (0 / 1, read per launch): 0
 // hands the kernels no table, and every plane loads its ids again.
 static const uint8_t* pid_same_table(kryst_csr_t a) { return env_int("KRYST_SPMV_PID_REUSE", 1) != 0 ? a->d_pid_same : nullptr; }
+// The recompute residual pass takes the seven leg values as kernel arguments where the operator has one value per leg (csr.h: pat_leg_ok) and
+// KRYST_SPMV_LEG_VALUES (0 / 1, read per launch) allows it; every other operator keeps the table look-ups.  In-process A/B inside CG with the fused form
+// forced (tools/cg_step_ab.py, profiles/march_step/): it costs nothing at 384^3 and 256^3 either, so the knob has no size rule.
+static bool leg_values_on(kryst_csr_t a) { return a->pat_leg_ok && env_int("KRYST_SPMV_LEG_VALUES", 1) != 0; }
 // r -= alpha A p with the tile partials of (r, r), A p formed from p on the way (the launch after launch_spmv_fused(.., y = nullptr, ..) and alpha's fold)
 int32_t launch_cg_residual_recompute(kryst_csr_t a, const double* p, double* r, const double* alpha, bool keep, const int* done) {
     kryst_ctx_t ctx = a->ctx;
@@ -630,15 +653,18 @@ int32_t launch_cg_residual_recompute(kryst_csr_t a, const double* p, double* r, 
     const size_t lds = std::max(q.lds.bytes, (size_t)(160 << 10) / 2 - 512);
     static bool raised = false;
     if (!raised) {
-        for (const void* fn : {(const void*)cg_recompute_residual_kernel<2, false>, (const void*)cg_recompute_residual_kernel<2, true>,
-                               (const void*)cg_recompute_residual_kernel<4, false>, (const void*)cg_recompute_residual_kernel<4, true>})
+#define KR_RESID_FNS(T_, K_) (const void*)cg_recompute_residual_kernel<T_, K_, false>, (const void*)cg_recompute_residual_kernel<T_, K_, true>
+        for (const void* fn : {KR_RESID_FNS(2, false), KR_RESID_FNS(2, true), KR_RESID_FNS(4, false), KR_RESID_FNS(4, true)})
             (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 80 << 10);
+#undef KR_RESID_FNS
         raised = true;
     }
     const dim3 grid((unsigned)(8 * spx * q.m.segs)), block(KR_T);
     const int32_t n_ = a->pat_stage_n, plane = a->pat_far_hi;
-    by_int<2, 4>(q.m.T, [&](auto T_) { by_bool(keep, [&](auto KEEP) {
-        hipLaunchKernelGGL((cg_recompute_residual_kernel<T_(), KEEP()>), grid, block, lds, ctx->s_main, args, p, r, alpha, n_, plane); }); });
+    LegVals lv;
+    for (int u = 0; u < 7; ++u) lv.v[u] = a->pat_leg[u];
+    by_int<2, 4>(q.m.T, [&](auto T_) { by_bool(keep, [&](auto KEEP) { by_bool(leg_values_on(a), [&](auto LEG) {
+        hipLaunchKernelGGL((cg_recompute_residual_kernel<T_(), KEEP(), LEG()>), grid, block, lds, ctx->s_main, args, p, r, alpha, n_, plane, lv); }); }); });
     KR_HIP(hipGetLastError());
     phase_mark(ctx, KR_PH_BLAS1_RESIDUAL);
     return KRYST_OK;
@@ -757,6 +783,15 @@ int32_t kryst_csr_pid_reuse_info(kryst_csr_t a, int64_t* info) {
     info[0] = m.eligible && m.on && pid_same_table(a) ? 1 : 0;
     info[1] = a->d_pid_same ? a->pid_same_count : 0;
     info[2] = a->d_pid_same ? a->nrows / KR_TILE : 0;
+    return KRYST_OK;
+}
+// info[0]: the operator has one value per leg (csr.h: pat_leg_ok); info[1]: a recompute residual pass would now take the values as kernel arguments (the
+// marching mode and the recompute-Ap form on, KRYST_SPMV_LEG_VALUES); values[0 .. 6]: the leg values (+0.0 throughout when info[0] is 0)
+int32_t kryst_csr_leg_values_info(kryst_csr_t a, int64_t* info, double* values) {
+    KR_ARG(a && info && values, "csr_leg_values_info");
+    info[0] = a->pat_leg_ok ? 1 : 0;
+    info[1] = fuse_form(a) && recompute_plan(a).on && leg_values_on(a) ? 1 : 0;
+    for (int u = 0; u < 7; ++u) values[u] = a->pat_leg[u];
     return KRYST_OK;
 }
 // Measurement hook: average milliseconds per launch of the fused direction + SpMV kernel of CG / PCG (spmv_pattern_fuse_kernel) on work vectors of its
