@@ -32,7 +32,7 @@ struct CgAlphaLogic {                // cg.rs:164-175
             return;
         }
         st->alpha = st->rsq / p_dot_ap;                                // :175
-        st->alpha_hist[(st->iter + 1) & 15] = st->alpha;               // (x updated in batches: XBatchOp reads it; the ring of direction vectors has <= 16 slots)
+        st->alpha_hist[(st->iter + 1) & 63] = st->alpha;               // (x updated in batches: XBatchOp reads it; a batch has <= 32 iterations)
     }
 };
 struct CgBetaLogic {                 // cg.rs:223-284
@@ -92,7 +92,7 @@ struct PcgAlphaLogic {               // pcg.rs:151-173
             return;
         }
         st->alpha = st->rz / p_dot_ap;                                 // :173
-        st->alpha_hist[(st->iter + 1) & 15] = st->alpha;
+        st->alpha_hist[(st->iter + 1) & 63] = st->alpha;
     }
 };
 struct PcgBetaLogic {                // pcg.rs:188-218

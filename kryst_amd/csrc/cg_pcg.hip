@@ -250,24 +250,28 @@ struct CgFlushOp {                   // x += alpha p (cg.rs:207-209 / pcg.rs:175
 // iterations k - m + 1 .. k are applied in ONE pass -- x = x + alpha_i p_i for i ascending, each the reference's un-fused multiply and add on the
 // reference's operands, so the same bits -- which reads x once and writes it once per m iterations.  Updates beyond `xpend` (the solve ended before
 // them) are not applied; the flush at the end of a solve / session applies what the last partial batch owes.
+constexpr int KR_XB_MAX = 32;      // the longest batch (DevState::alpha_hist holds 64 entries; the ring has KR_XB_MAX + 1 slots at most)
 template <int M>                   // M: the batch's length when every one of its updates happened (the common case), 0: any length, tested per update
 struct XBatchOp {
     static constexpr int NQ = 0; static constexpr const char* TAG = "XBatch"; static constexpr int PHASE = KR_PH_BLAS1_XBATCH; static constexpr int BPC = 2;
-    const DevState* st; const double* p[8]; long long lo; int cnt; double* x;       // p[u]: the direction vector of iteration lo + u
+    static constexpr int ANY = M > 8 ? M : M > 0 ? 8 : KR_XB_MAX;              // the updates the tested form walks
+    const DevState* st; const double* p[KR_XB_MAX]; long long lo; int cnt; double* x;   // p[u]: the direction vector of iteration lo + u
     __device__ __forceinline__ void pair(int64_t i, bool, bool, double (&)[1]) const {
         const long long last = st->xpend;                                     // (uniform) updates of later iterations never happened in the reference
         d2 xx = ld2(x, i);
-        if (M > 0 && lo + M - 1 <= last) {                                    // all M loads in flight together, then the M updates in iteration order
+        // all M loads in flight together, then the M updates in iteration order.  (M = 24 and 32 measured at 512^3 with the loads in chunks of 8 and
+        // 16 under the x pair as well, profiles/handoff/xb_chunk_ab.jsonl: 719.0 / 719.4 / 720.0 it/s at M = 32 -- no difference, so the one form)
+        if (M > 0 && lo + M - 1 <= last) {
             d2 pp[M > 0 ? M : 1]; double al[M > 0 ? M : 1];
 #pragma unroll
-            for (int u = 0; u < M; ++u) { pp[u] = ld2(p[u], i); al[u] = st->alpha_hist[(lo + u) & 15]; }
+            for (int u = 0; u < M; ++u) { pp[u] = ld2(p[u], i); al[u] = st->alpha_hist[(lo + u) & 63]; }
 #pragma unroll
             for (int u = 0; u < M; ++u) { xx.a = xx.a + al[u] * pp[u].a; xx.b = xx.b + al[u] * pp[u].b; }
         } else {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
+            for (int u = 0; u < ANY; ++u) {
                 if (u < cnt && lo + u <= last) {
-                    const double al = st->alpha_hist[(lo + u) & 15];
+                    const double al = st->alpha_hist[(lo + u) & 63];
                     const d2 pp = ld2(p[u], i);
                     xx.a = xx.a + al * pp.a; xx.b = xx.b + al * pp.b;
                 }
@@ -283,30 +287,42 @@ struct GateXBatch {                  // nothing to apply: the solve ended before
 template <int M>
 inline int32_t launch_x_batch_m(kryst_ctx_t ctx, DevState* st, const std::vector<double*>& ring, int xb, long long lo, long long hi, double* x, int64_t n) {
     XBatchOp<M> op; op.st = st; op.lo = lo; op.cnt = (int)(hi - lo + 1); op.x = x;
-    for (int u = 0; u < 8; ++u) op.p[u] = ring[(size_t)((lo + std::min<long long>(u, hi - lo)) % (xb + 1))];
+    for (int u = 0; u < KR_XB_MAX; ++u) op.p[u] = ring[(size_t)((lo + std::min<long long>(u, hi - lo)) % (xb + 1))];
     return launch_ew_gated(ctx, op, n, GateXBatch{st, lo});
 }
-// x += alpha_i p_i for iterations lo .. hi (those that happened), p_i in ring[i % (xb + 1)]
+// x += alpha_i p_i for iterations lo .. hi (those that happened), p_i in ring[i % (xb + 1)].  Every length from 2 to KR_XB_MAX has an instance of its
+// own -- a full batch, and the partial one the flush at the end of a solve or session owes (up to xb - 1 updates: one pass with all its loads in
+// flight, not one dependent load after the other); a single update takes the any-length instance
 inline int32_t launch_x_batch(kryst_ctx_t ctx, DevState* st, const std::vector<double*>& ring, int xb, long long lo, long long hi, double* x, int64_t n) {
     int32_t rc = KRYST_OK;
-    if (!by_int<2, 3, 4, 5, 6, 7, 8>((int)(hi - lo + 1), [&](auto M) { rc = launch_x_batch_m<M()>(ctx, st, ring, xb, lo, hi, x, n); }))
-        rc = launch_x_batch_m<0>(ctx, st, ring, xb, lo, hi, x, n);
-    return rc;
+    const int cnt = (int)(hi - lo + 1);
+    KR_ARG(cnt >= 1 && cnt <= KR_XB_MAX, "launch_x_batch: a batch of more than 32 iterations");
+    auto exact = [&](auto M) { rc = launch_x_batch_m<M()>(ctx, st, ring, xb, lo, hi, x, n); };
+    if (by_int<2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>(cnt, exact) || by_int<17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32>(cnt, exact)) return rc;
+    return launch_x_batch_m<0>(ctx, st, ring, xb, lo, hi, x, n);
 }
-// x-batch length: 1 = every iteration (x rides on the fused pass that reads p_old); KRYST_CG_X_BATCH forces (<= 8).  Measured at 512^3
+// x-batch length: 1 = every iteration (x rides on the fused pass that reads p_old); KRYST_CG_X_BATCH forces (<= 32).  Measured at 512^3
 // (profiles/r05/cg_xbatch_ab.jsonl): CG 545 / 560 / 575 / 579 / 584 / 582 / 588 it/s at m = 1 / 2 / 4 / 5 / 6 / 7 / 8 (unfused 530); PCG 447 / 459 / 487 /
 // 489 / 490 / 490.5 / 472 (unfused 443) -- PCG's thirteen 1 GB work vectors lose at m = 8 what the ninth ring slot costs, so 7 there.
+// Batches beyond 8 (<= KR_XB_MAX; the pass moves (m + 2) * 8 / m bytes per row and iteration: 10 at 8, 8.5 at 32), one operator, one process, 192+
+// timed iterations x 3 rounds (profiles/handoff/xb_chunk_ab.jsonl, pcg_xbatch_ab.jsonl): CG 709.5 / 713.1 / 714.8 / 720.1 / 720.0 it/s at m = 8 / 12 /
+// 16 / 24 / 32, every run of 32 above every run of 8; bench.py alternating with the parent commit 699.8 -> 708.0 it/s (+1.2 %) -- so 32 for CG (a ring of 33 vectors: 33 GiB at 512^3; ring_if_it_fits halves the batch
+// until the device can hold its ring).  PCG 523.0 / 521.4 / 540.3 / 544.2 at m = 7 / 8 / 12 / 16, but its runs at 7 spread over
+// 30 it/s (541 in the first round, 511 and 517 after the longer rings had been allocated): short of the margin, so PCG stays at 7.
 inline int cg_x_batch(bool pcg) {
-    return std::max(1, std::min(8, env_int("KRYST_CG_X_BATCH", pcg ? 7 : 8)));
+    return std::max(1, std::min(KR_XB_MAX, env_int("KRYST_CG_X_BATCH", pcg ? 7 : 32)));
 }
 // the ring costs xb - 1 work vectors more than the two alternating direction vectors: only where the device has the room (what the context's
-// arena already holds counts as room)
-inline int ring_if_it_fits(kryst_ctx_t ctx, int64_t n, int xb, int work_vectors) {
+// arena already holds counts as room).  base: the solver's other work vectors.  A ring that does not fit is halved until one does (32 -> 16 -> 8 ..)
+inline int ring_if_it_fits(kryst_ctx_t ctx, int64_t n, int xb, int base) {
     if (xb <= 1) return 1;
     size_t free_b = 0, total_b = 0;
     if (hipSetDevice(ctx->device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return 1; }
-    const size_t need = padded_bytes(n) * (size_t)(work_vectors + 2);
-    return need <= ctx->arena_bytes || need <= free_b + ctx->arena_bytes ? xb : 1;
+    for (; xb > 1; xb /= 2) {
+        const size_t need = padded_bytes(n) * (size_t)(base + xb + 1 + 2);
+        if (need <= ctx->arena_bytes || need <= free_b + ctx->arena_bytes) return xb;
+    }
+    return 1;
 }
 // ... and in the UNFUSED deferred form (every operator form, every rank of a partition) the same ring is available: the direction pass writes
 // p_new = z + beta p_old out of place (CgDirectionRingOp: 2 reads + 1 write instead of 3 + 2) and XBatchOp pays x -- 34 instead of 40 bytes per row
@@ -314,7 +330,7 @@ inline int ring_if_it_fits(kryst_ctx_t ctx, int64_t n, int xb, int work_vectors)
 // is what the 256 MiB Infinity Cache hands from the direction pass to the SpMV; nine ring slots defeat that), 512^3 on plain CSR +-1 %, 64^3 / 128^3
 // +3 %.  KRYST_CG_X_BATCH = m > 1 turns it on (tests do).
 inline int cg_x_batch_unfused() {
-    return std::max(1, std::min(8, env_int("KRYST_CG_X_BATCH", 1)));
+    return std::max(1, std::min(KR_XB_MAX, env_int("KRYST_CG_X_BATCH", 1)));
 }
 // ---- the direction vector of CG and PCG: where p lives (in place; two alternating vectors; a ring), the form its update p = z + beta p takes
 // (inside the next iteration's SpMV; a ring pass; the in-place pass) and the x updates that ride on it.  One owner for both solvers: what differs
@@ -337,7 +353,7 @@ struct __attribute__((visibility("hidden"))) DirectionVec {
         // the direction pass inside the SpMV (spmv_fuse.hip: spmv_pattern_fuse_kernel) where the operator's form allows it
         fuse = deferred && spmv_can_fuse_direction(s.a);
         xb = fuse ? cg_x_batch(pcg) : deferred ? cg_x_batch_unfused() : 1;
-        xb = ring_if_it_fits(s.ctx, s.n, xb, base + xb + 1);
+        xb = ring_if_it_fits(s.ctx, s.n, xb, base);
         ringdir = !fuse && xb > 1;
         return xb > 1 ? base + xb + 1 : fuse ? 5 : 4;
     }

@@ -624,8 +624,8 @@ static RecomputePlan recompute_plan(kryst_csr_t a) {
     if (!(q.m.eligible && q.m.on)) return q;
     q.lds = staged_lds(a, 3, 8, 2, q.m.T, 1);
     if (q.lds.bytes > ((size_t)(160 << 10) / 2 - 512)) return q;
-    // (8: CG's default batch length in the fused form, cg_pcg.hip: cg_x_batch; the solver also checks the length it really took)
-    q.on = env_int("KRYST_CG_X_BATCH", 8) > 1 && env_int("KRYST_CG_RECOMPUTE_AP", beyond_fuse_min_bytes(a) ? 1 : 0) != 0;
+    // (32: CG's default batch length in the fused form, cg_pcg.hip: cg_x_batch; the solver also checks the length it really took)
+    q.on = env_int("KRYST_CG_X_BATCH", 32) > 1 && env_int("KRYST_CG_RECOMPUTE_AP", beyond_fuse_min_bytes(a) ? 1 : 0) != 0;
     return q;
 }
 bool spmv_can_recompute_ap(kryst_csr_t a) { return spmv_can_fuse_direction(a) && recompute_plan(a).on; }
