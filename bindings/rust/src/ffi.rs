@@ -281,6 +281,16 @@ extern "C" {
 // mixed precision: fp32 as a storage format (fp64 arithmetic and scalars), CG / Jacobi-PCG on it and fp64 iterative refinement around them
 pub type Vec32 = *mut c_void;
 pub type Csr32 = *mut c_void;
+// what the lowered operator keeps beside the plain arrays (kryst_csr32_lower_form); kryst_csr32_encoding reports 0 plain, 1 pattern,
+// 2 pattern-stage, 3 dia
+pub const KRYST_CSR32_PLAIN: i32 = 0;
+pub const KRYST_CSR32_AUTO: i32 = 1;
+pub const KRYST_CSR32_PATTERN: i32 = 2;
+pub const KRYST_CSR32_DIA: i32 = 3;
+pub const KRYST_CSR32_DIA_ABSENT_BITS: u32 = 0x7FD1_A0D1;        // "no entry here" in an fp32 diagonal stream
+#[repr(i32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Csr32Form { Plain = KRYST_CSR32_PLAIN, Auto = KRYST_CSR32_AUTO, Pattern = KRYST_CSR32_PATTERN, Dia = KRYST_CSR32_DIA }
 extern "C" {
     pub fn kryst_reduce_spec32(t: *mut i32, v: *mut i32, f: *mut i32);
     pub fn kryst_vec32_create(ctx: Ctx, n: i64, out: *mut Vec32) -> i32;
@@ -292,7 +302,7 @@ extern "C" {
     pub fn kryst_vec32_to_f64(dst: Vecd, src: Vec32) -> i32;
     pub fn kryst_dot32(x: Vec32, y: Vec32, out: *mut f64) -> i32;
     pub fn kryst_csr32_lower(a: Csr, out: *mut Csr32) -> i32;
-    pub fn kryst_csr32_lower_form(a: Csr, form: i32, out: *mut Csr32) -> i32;        // form: 0 plain, 1 auto, 2 pattern (CSR-P16)
+    pub fn kryst_csr32_lower_form(a: Csr, form: i32, out: *mut Csr32) -> i32;        // form: Csr32Form as i32
     pub fn kryst_csr32_encoding(a: Csr32, kernel: *mut i32) -> i32;
     pub fn kryst_csr32_info(a: Csr32, info: *mut i64) -> i32;
     pub fn kryst_csr32_destroy(a: Csr32) -> i32;

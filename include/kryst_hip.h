@@ -704,7 +704,7 @@ int32_t kryst_pcg_solve_multi(const double* b, double* x, int64_t n, int32_t k, 
  * fp32 is how vector elements and matrix values are STORED.  Every kernel widens what it loads, computes in fp64 in the fixed order of its
  * fp64 twin (separate multiply and add) and rounds once -- (float), round to nearest even, fp32 subnormals kept -- when it stores; every
  * scalar (alpha, beta, the inner products, the residual norms, the exits) is fp64 and is the fp64 solver's own code.  One rank; the plain CSR
- * arrays, or (kryst_csr32_lower_form) the CSR-P16 row-pattern form; nothing here runs unless it is called. */
+ * arrays, or (kryst_csr32_lower_form) the CSR-P16 row-pattern form or the CSR-DIA diagonal form; nothing here runs unless it is called. */
 typedef struct kryst_vec32_s* kryst_vec32_t;
 typedef struct kryst_csr32_s* kryst_csr32_t;
 /* kryst_reduce_spec for fp32-stored vectors: T = 256 threads own V = 4 consecutive elements each (a 1024-element tile, one 16-byte access
@@ -736,15 +736,27 @@ int32_t kryst_csr32_lower(kryst_csr_t a, kryst_csr32_t* out);
  * table's offsets, and its values rounded with the same (float) as the CSR values, so a table value is bit for bit the lowered value of every row
  * that uses it and kryst_spmv32 gives the same bits on either form.  KRYST_UNSUPPORTED, *out untouched: PATTERN on an operator without a CSR-P16
  * form, or whose vectors do not fit 32-bit byte offsets (AUTO keeps the plain arrays alone in both cases); a distributed operator.  An unknown
- * form: KRYST_ERR_ARG. */
+ * form: KRYST_ERR_ARG.
+ * DIA (opt-in: AUTO never chooses it) ALSO keeps its own fp32 copy of the operator's CSR-DIA value streams: one stream of
+ * ceil(nrows / 1024) * 1024 + 1024 floats per diagonal, in the diagonals' stored order, the offsets copied.  A stream entry is (float) of the
+ * fp64 stream entry -- bit for bit the lowered CSR value at that position, so kryst_spmv32 gives the same bits as on the plain arrays -- and an
+ * absent entry (and all padding) carries the bits KRYST_CSR32_DIA_ABSENT_BITS: a quiet NaN whose payload (float) of the canonical NaN never
+ * has.  KRYST_UNSUPPORTED, *out untouched: `a` keeps no CSR-DIA streams; a stored NaN whose rounding has the marker's bits (the fp64 form
+ * refuses a stored value with its own marker's bits the same way); vectors that do not fit 32-bit byte offsets; a distributed operator.
+ * An operator is given CSR-DIA streams at creation only: at most 32 distinct (col - row) offsets, every row in one common diagonal order,
+ * D * nrows <= 1.125 * nnz + 64, and -- by default (KRYST_SPMV_DIA=1) -- no CSR-D16 / CSR-P16 form, which stream fewer bytes in fp64;
+ * KRYST_SPMV_DIA=2 at creation builds the streams whenever the other rules hold, KRYST_SPMV_DIA=0 never. */
 #define KRYST_CSR32_PLAIN 0
 #define KRYST_CSR32_AUTO 1
 #define KRYST_CSR32_PATTERN 2
+#define KRYST_CSR32_DIA 3
+#define KRYST_CSR32_DIA_ABSENT_BITS 0x7FD1A0D1u
 int32_t kryst_csr32_lower_form(kryst_csr_t a, int32_t form, kryst_csr32_t* out);
 /* *kernel: the kernel the next kryst_spmv32 (and every SpMV of the fp32 solvers) takes under the current settings -- 0 the plain wave kernel,
  * 1 the row-pattern kernel, 2 the row-pattern kernel with the near operands staged in LDS (boxes of lines of n points, n % 4 == 0, uniform far
- * offsets).  Settings, read at every launch (once per solve inside one): KRYST_SPMV32_FORM = plain | pattern (default: the most compact form
- * held), KRYST_SPMV32_STAGE = 0 | 1 (default 1). */
+ * offsets), 3 the diagonal-stream kernel of an operator lowered with DIA.  Settings, read at every launch (once per solve inside one):
+ * KRYST_SPMV32_FORM = plain | pattern | dia (default: the most compact form held; `plain` sends every operator to the plain wave kernel, the
+ * other two words mean the default for an operator that holds the form), KRYST_SPMV32_STAGE = 0 | 1 (default 1). */
 int32_t kryst_csr32_encoding(kryst_csr32_t a, int32_t* kernel);
 /* info[0]: values the rounding changed; info[1]: nonzero values that became zero or fp32-subnormal; info[2]: rows */
 int32_t kryst_csr32_info(kryst_csr32_t a, int64_t info[3]);

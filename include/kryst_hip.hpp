@@ -800,10 +800,11 @@ public:
 
 // ---- mixed precision (an extension): fp32 as a storage format, fp64 arithmetic and scalars -------------------------
 // CsrMatrix<f32> lowered from a HipCsrMatrix: copies of its index arrays, its values rounded to fp32 on the device
-// Form: what the lowered operator keeps (kryst_csr32_lower_form) -- the CSR arrays alone, or also the operator's CSR-P16 row-pattern form
+// Form: what the lowered operator keeps (kryst_csr32_lower_form) -- the CSR arrays alone, or also the operator's CSR-P16 row-pattern form, or
+// (Dia, opt-in) its CSR-DIA diagonal streams in fp32
 class HipCsrMatrix32 {
 public:
-    enum Form : int32_t { Plain = KRYST_CSR32_PLAIN, Auto = KRYST_CSR32_AUTO, Pattern = KRYST_CSR32_PATTERN };
+    enum Form : int32_t { Plain = KRYST_CSR32_PLAIN, Auto = KRYST_CSR32_AUTO, Pattern = KRYST_CSR32_PATTERN, Dia = KRYST_CSR32_DIA };
     explicit HipCsrMatrix32(const HipCsrMatrix& a, Form form = Plain) : ctx_(a.context()) { check(kryst_csr32_lower_form(a.handle(), form, &h_)); }
     HipCsrMatrix32(HipCsrMatrix32&& o) noexcept : ctx_(std::move(o.ctx_)), h_(o.h_) { o.h_ = nullptr; }
     HipCsrMatrix32(const HipCsrMatrix32&) = delete; HipCsrMatrix32& operator=(const HipCsrMatrix32&) = delete;
@@ -821,11 +822,11 @@ public:
         if (yv) kryst_vec32_destroy(yv);
         check(rc);
     }
-    // the kernel the next spmv takes (kryst_csr32_encoding): "plain", "pattern" or "pattern-stage"
+    // the kernel the next spmv takes (kryst_csr32_encoding): "plain", "pattern", "pattern-stage" or "dia"
     std::string encoding() const {
         int32_t k = -1;
         check(kryst_csr32_encoding(h_, &k));
-        return k == 2 ? "pattern-stage" : k == 1 ? "pattern" : "plain";
+        return k == 3 ? "dia" : k == 2 ? "pattern-stage" : k == 1 ? "pattern" : "plain";
     }
     kryst_csr32_t handle() const { return h_; }
 private:

@@ -381,16 +381,27 @@ def dot32(x, y):
 class CsrMatrix32:
     """CsrMatrix<f32> lowered from a CsrMatrix (kryst_csr32_lower_form): its own copies of the index arrays, the values rounded to fp32.
     form "plain" keeps the CSR arrays alone; "pattern" also keeps the operator's CSR-P16 row-pattern form with fp32 tables (KError Unsupported
-    when it has none); "auto" keeps it where there is one."""
+    when it has none); "auto" keeps it where there is one; "dia" (opt-in, never chosen by "auto") also keeps the operator's CSR-DIA diagonal
+    streams in fp32 (Unsupported when it has none: an operator gets them at creation, by default only where it has no CSR-D16 / CSR-P16
+    form, under KRYST_SPMV_DIA=2 wherever its diagonals are well filled)."""
     FORMS = {"plain": 0, "auto": 1, "pattern": 2}
     KERNELS = ("plain", "pattern", "pattern-stage")
+    FORMS_EXT = {"dia": 3}              # the forms and kernels added since, kept beside the first three
+    KERNELS_EXT = ("dia",)
+    DIA_ABSENT_BITS = 0x7FD1A0D1        # KRYST_CSR32_DIA_ABSENT_BITS: "no entry here" in an fp32 diagonal stream
+
+    @classmethod
+    def form_code(cls, form):
+        """the KRYST_CSR32_* code of a form's name; KError ERR_ARG for an unknown name"""
+        code = cls.FORMS.get(form, cls.FORMS_EXT.get(form))
+        if code is None:
+            raise KError(102, f"form must be one of {sorted({**cls.FORMS, **cls.FORMS_EXT})}, not {form!r}")
+        return code
 
     def __init__(self, a, form="plain"):
         self.ctx = a.ctx
         self.h = _ffi.Handle()
-        if form not in self.FORMS:
-            raise KError(102, f"form must be one of {sorted(self.FORMS)}, not {form!r}")
-        check(lib().kryst_csr32_lower_form(a.h, self.FORMS[form], C.byref(self.h)))
+        check(lib().kryst_csr32_lower_form(a.h, self.form_code(form), C.byref(self.h)))
         self._nrows, self._ncols, self.nnz = a.nrows(), a.ncols(), a.nnz
 
     def nrows(self):
@@ -408,10 +419,10 @@ class CsrMatrix32:
 
     def encoding(self):
         """The kernel the next spmv (and every SpMV of a solve) takes under the current settings (kryst_csr32_encoding): "plain",
-        "pattern" or "pattern-stage".  KRYST_SPMV32_FORM=plain|pattern and KRYST_SPMV32_STAGE=0|1 steer it."""
+        "pattern", "pattern-stage" or "dia".  KRYST_SPMV32_FORM=plain|pattern|dia and KRYST_SPMV32_STAGE=0|1 steer it."""
         k = C.c_int32(-1)
         check(lib().kryst_csr32_encoding(self.h, C.byref(k)))
-        return self.KERNELS[k.value]
+        return (self.KERNELS + self.KERNELS_EXT)[k.value]
 
     def spmv(self, x, y=None):
         """y <- (float)(A x): the row fold in fp64 over the stored order, rounded once.  DeviceVec32 stays on the device; a host array is
@@ -596,7 +607,8 @@ class CsrMatrix:
 
     def lower(self, form="plain"):
         """This operator with fp32-stored values (CsrMatrix32; an extension): a copy, with no tie to this one's lifetime.  form: "plain"
-        (the CSR arrays), "pattern" (also the CSR-P16 row-pattern form; refused where the operator has none) or "auto"."""
+        (the CSR arrays), "pattern" (also the CSR-P16 row-pattern form; refused where the operator has none), "auto", or "dia" (also
+        the CSR-DIA diagonal streams in fp32; refused where the operator has none)."""
         return CsrMatrix32(self, form)
 
     ENCODINGS = ("csr", "csr-d8", "csr-d16", "csr-p16", "csr-dia")
@@ -1661,9 +1673,8 @@ class RefinementSolver:
         return self
 
     def with_form(self, form):
-        """How lowered(a) lowers: "plain" (the default), "auto" or "pattern" (CsrMatrix.lower)."""
-        if form not in CsrMatrix32.FORMS:
-            raise KError(102, f"form must be one of {sorted(CsrMatrix32.FORMS)}, not {form!r}")
+        """How lowered(a) lowers: "plain" (the default), "auto", "pattern" or "dia" (CsrMatrix.lower)."""
+        CsrMatrix32.form_code(form)
         if form != self.form:
             self._lowered = {}
         self.form = form

@@ -335,11 +335,11 @@ __global__ __launch_bounds__(KR32_T) void spmv32_wave_kernel(const Spmv32Args a)
     }
 }
 
-// KRYST_SPMV32_FORM = plain | pattern: -1 unset (or neither word), 0 plain, 1 pattern.  Read as env_int reads a number: at every launch outside a
+// KRYST_SPMV32_FORM = plain | pattern | dia: -1 unset (or no such word), 0 plain, 1 pattern, 2 dia.  Read as env_int reads a number: at every launch outside a
 // solve, once per solve inside one (EnvFreeze)
 static int spmv32_form_knob() {
     static EnvSlot slot;
-    auto parse = [](const char* v) -> long long { return !v ? -1 : !strcmp(v, "plain") ? 0 : !strcmp(v, "pattern") ? 1 : -1; };
+    auto parse = [](const char* v) -> long long { return !v ? -1 : !strcmp(v, "plain") ? 0 : !strcmp(v, "pattern") ? 1 : !strcmp(v, "dia") ? 2 : -1; };
     if (g_env_frozen > 0) {
         const uint32_t e = g_env_epoch.load(std::memory_order_relaxed);
         if (slot.epoch.load(std::memory_order_acquire) == e) return (int)slot.val.load(std::memory_order_relaxed);
@@ -351,9 +351,12 @@ static int spmv32_form_knob() {
     return (int)parse(getenv("KRYST_SPMV32_FORM"));
 }
 
-// the choice: pattern-stage, then pattern, then plain, from the forms the lowered operator holds and the two settings
+// the choice: the diagonal streams, else pattern-stage, then pattern, then plain, from the form the lowered operator holds and the two settings
+// (a lowered operator holds the diagonal form or the row-pattern form, never both; `pattern` and `dia` both mean "the form held")
 int spmv32_kernel(kryst_csr32_t a) {
-    if (!a->d_pid || spmv32_form_knob() == 0) return 0;
+    if (spmv32_form_knob() == 0) return 0;
+    if (a->d_dia) return 3;
+    if (!a->d_pid) return 0;
     const bool stage = a->pat_stage_n > 0 && a->pat_stage_n % 4 == 0 && a->pat_far_uniform && env_int("KRYST_SPMV32_STAGE", 1) != 0;
     return stage ? 2 : 1;
 }
@@ -364,7 +367,8 @@ int32_t launch_spmv32(kryst_csr32_t a, const float* x, float* y, int nq, const f
     if (nt <= 0) return KRYST_OK;
     if (nq) KR_TRY(ensure_partials(ctx, nt));
     if (const int kernel = spmv32_kernel(a)) {
-        KR_TRY(kernel == 2 ? enqueue_spmv32_pattern_stage(a, x, y, nq, dvec, done) : enqueue_spmv32_pattern(a, x, y, nq, dvec, done));
+        KR_TRY(kernel == 3 ? enqueue_spmv32_dia(a, x, y, nq, dvec, done)
+               : kernel == 2 ? enqueue_spmv32_pattern_stage(a, x, y, nq, dvec, done) : enqueue_spmv32_pattern(a, x, y, nq, dvec, done));
         phase_mark(ctx, KR_PH_SPMV);
         return KRYST_OK;
     }
@@ -409,6 +413,7 @@ static void csr32_free(kryst_csr32_t a) {
     (void)hipStreamSynchronize(a->ctx->s_main);
     (void)hipFree(a->d_row_ptr); (void)hipFree(a->d_col); (void)hipFree(a->d_val);
     (void)hipFree(a->d_pid); (void)hipFree(a->d_pmeta); (void)hipFree(a->d_poff); (void)hipFree(a->d_pval);
+    (void)hipFree(a->d_dia);
     delete a;
 }
 
@@ -709,7 +714,7 @@ int32_t kryst_csr32_lower(kryst_csr_t a, kryst_csr32_t* out) { return kryst_csr3
 
 int32_t kryst_csr32_lower_form(kryst_csr_t a, int32_t form, kryst_csr32_t* out) {
     KR_ARG(a && out, "csr32_lower");
-    KR_ARG(form == KRYST_CSR32_PLAIN || form == KRYST_CSR32_AUTO || form == KRYST_CSR32_PATTERN, "csr32_lower: unknown form");
+    KR_ARG(form == KRYST_CSR32_PLAIN || form == KRYST_CSR32_AUTO || form == KRYST_CSR32_PATTERN || form == KRYST_CSR32_DIA, "csr32_lower: unknown form");
     kryst_ctx_t ctx = a->ctx;
     if (a->dist || ctx->nranks > 1) { set_error("csr32_lower: distributed operators are not supported"); return KRYST_UNSUPPORTED; }
     KR_ARG(a->d_row_ptr && a->d_col && a->d_val, "csr32_lower: the operator keeps no CSR arrays");
@@ -719,12 +724,16 @@ int32_t kryst_csr32_lower_form(kryst_csr_t a, int32_t form, kryst_csr32_t* out) 
     const bool fits = vec32_len(std::max(a->nrows, a->ncols)) * (int64_t)sizeof(float) < (1ll << 31);
     if (form == KRYST_CSR32_PATTERN && !has_p16) { set_error("csr32_lower: the operator has no CSR-P16 form"); return KRYST_UNSUPPORTED; }
     if (form == KRYST_CSR32_PATTERN && !fits) { set_error("csr32_lower: the vectors do not fit 32-bit byte offsets"); return KRYST_UNSUPPORTED; }
-    const bool pattern = form != KRYST_CSR32_PLAIN && has_p16 && fits;
+    const bool pattern = (form == KRYST_CSR32_AUTO || form == KRYST_CSR32_PATTERN) && has_p16 && fits;
+    // the diagonal form: the operator must hold CSR-DIA streams (csr_create.hip: build_dia, at creation only); the same rule for the offsets
+    const bool dia = form == KRYST_CSR32_DIA;
+    if (dia && !(a->d_dia && a->dia_nd > 0 && a->dia_nd <= KR_DIA_MAX)) { set_error("csr32_lower: the operator has no CSR-DIA form"); return KRYST_UNSUPPORTED; }
+    if (dia && !fits) { set_error("csr32_lower: the vectors do not fit 32-bit byte offsets"); return KRYST_UNSUPPORTED; }
     KR_HIP(hipSetDevice(ctx->device));
     kryst_csr32_t m = new kryst_csr32_s();
     m->ctx = ctx; m->nrows = a->nrows; m->ncols = a->ncols; m->nnz = a->nnz;
     unsigned long long* d_count = nullptr;
-    unsigned long long cnt[3] = {0, 0, 0};
+    unsigned long long cnt[4] = {0, 0, 0, 0};                                // lower_values_kernel's three, and the streams' refused entries
     const size_t ne = (size_t)a->nnz + 8;
     hipError_t e = hipMalloc(&m->d_row_ptr, sizeof(int32_t) * (size_t)(a->nrows + 1));
     if (e == hipSuccess) e = hipMalloc(&m->d_col, sizeof(int32_t) * ne);
@@ -757,6 +766,12 @@ int32_t kryst_csr32_lower_form(kryst_csr_t a, int32_t form, kryst_csr32_t* out) 
         m->npat = a->npat; m->ntab = a->ntab; m->pat_unroll = a->pat_unroll; m->pat_single = a->pat_single;
         m->pat_stage_n = a->pat_stage_n; m->pat_far_lo = a->pat_far_lo; m->pat_far_hi = a->pat_far_hi; m->pat_far_uniform = a->pat_far_uniform;
     }
+    if (e == hipSuccess && dia) {
+        m->dia_stride = vec32_len(a->nrows); m->dia_nd = a->dia_nd; m->dia_min = a->dia_min; m->dia_max = a->dia_max;
+        for (int d = 0; d < KR_DIA_MAX; ++d) m->dia_off[d] = a->dia_off[d];
+        e = hipMalloc(&m->d_dia, sizeof(float) * (size_t)m->dia_stride * (size_t)m->dia_nd);
+        if (e == hipSuccess) e = enqueue_lower_dia(a, m, d_count + 3);
+    }
     if (e == hipSuccess) e = hipMemcpyAsync(cnt, d_count, sizeof cnt, hipMemcpyDeviceToHost, ctx->s_main);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->s_main);
     (void)hipFree(d_count);
@@ -764,6 +779,11 @@ int32_t kryst_csr32_lower_form(kryst_csr_t a, int32_t form, kryst_csr32_t* out) 
     if (cnt[2]) {
         csr32_free(m);
         set_error("csr32_lower: %llu finite value(s) would round to +-inf in fp32", cnt[2]);
+        return KRYST_UNSUPPORTED;
+    }
+    if (cnt[3]) {
+        csr32_free(m);
+        set_error("csr32_lower: %llu stored NaN(s) round to the bits of the fp32 absent marker; the diagonal form is refused", cnt[3]);
         return KRYST_UNSUPPORTED;
     }
     m->changed = (int64_t)cnt[0]; m->tiny = (int64_t)cnt[1];

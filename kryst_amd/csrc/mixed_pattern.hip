@@ -11,8 +11,6 @@
 
 namespace kr {
 
-typedef float p_v4f __attribute__((ext_vector_type(4)));
-typedef float p_v4f_a4 __attribute__((ext_vector_type(4), aligned(4)));     // a 16-byte access at 4-byte alignment (gathers at any column)
 typedef unsigned p_v2u __attribute__((ext_vector_type(2)));
 
 struct Spmv32PatArgs {
@@ -22,25 +20,6 @@ struct Spmv32PatArgs {
     int32_t xcap;                   // allocated floats of x (vec32_len(ncols)): a 16-byte gather must end inside it
     int32_t red_off;                // byte offset of the reduction scratch in dynamic LDS
 };
-
-// the lane's four terms in index order from 0.0 (rows at or beyond nrows contribute nothing)
-__device__ __forceinline__ double quad_dot(const p_v4f d, const float (&o)[4], const bool (&valid)[4]) {
-    double acc = 0.0;
-    if (valid[0]) acc = acc + (double)d.x * (double)o[0];
-    if (valid[1]) acc = acc + (double)d.y * (double)o[1];
-    if (valid[2]) acc = acc + (double)d.z * (double)o[2];
-    if (valid[3]) acc = acc + (double)d.w * (double)o[3];
-    return acc;
-}
-__device__ __forceinline__ void quad_store(float* y, int32_t row, int32_t nrows, const float (&o)[4]) {
-    if (row + 3 < nrows) {
-        p_v4f ov; ov.x = o[0]; ov.y = o[1]; ov.z = o[2]; ov.w = o[3];
-        *reinterpret_cast<p_v4f*>(y + row) = ov;
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { if (row + r < nrows) y[row + r] = o[r]; }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------- any CSR-P16 operator
 // The tables go to LDS once per workgroup; the workgroup walks a run of tpw consecutive tiles with the next tile's ids prefetched.  When the lane's

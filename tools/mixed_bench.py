@@ -11,12 +11,20 @@
   mixed_bench.py prate  N                               CG32 / PCG32 it/s on the pattern-lowered and on the plain-lowered operator against fp64 CG /
                                                         Jacobi-PCG on the default encoding (CSR-P16 for the stencil operators)
   mixed_bench.py prefine N [--reps R]                   RefinementSolver.with_form("pattern") and ("plain") against fp64 CG on the default encoding
+  mixed_bench.py dspmv  N [--op varcoef|poisson]        the diagonal lowering (CsrMatrix.lower("dia")): kryst_spmv32 on the plain arrays and on the fp32
+                                                        streams -- as shipped, with plain instead of nontemporal value loads, with 1 / 2 / 4 workgroups
+                                                        per compute unit -- against the fp64 kryst_spmv on CSR-DIA (spmv_dia_kernel).  poisson is created
+                                                        under KRYST_SPMV_DIA=2 so that it keeps streams
+  mixed_bench.py drate  N [--op varcoef]                CG32 / PCG32 it/s on the dia-lowered and on the plain-lowered operator against fp64 CG /
+                                                        Jacobi-PCG on CSR-DIA
+  mixed_bench.py drefine N [--op varcoef] [--reps R]    RefinementSolver.with_form("dia") and ("plain") against fp64 CG / Jacobi-PCG on CSR-DIA
 
 The versions ALTERNATE inside the process after a warm-up; every timed window lasts at least half a second (spmv: a run of launches between
 two hipEvents; rate: the difference of two solves at IT and 3 IT iterations with tol = 0, wall clock, IT sized from a calibration solve so that
 2 IT iterations take >= 0.6 s; refine: whole solves, wall clock, lowering and first-use allocations taken out by a warm-up call).  Medians.
 
-Bytes, from shapes: fp64 plain-CSR SpMV 12 nnz + 4 (n + 1) + 16 n; spmv32 8 nnz + 4 (n + 1) + 8 n; CSR-P16 18 n in fp64 and 10 n in fp32.  `band`: the non-stencil operator of
+Bytes, from shapes: fp64 plain-CSR SpMV 12 nnz + 4 (n + 1) + 16 n; spmv32 8 nnz + 4 (n + 1) + 8 n; CSR-P16 18 n in fp64 and 10 n in fp32; CSR-DIA with D
+diagonals (8 D + 16) n in fp64 and (4 D + 8) n in fp32.  `band`: the non-stencil operator of
 tools/multi_rhs_only.py (seven entries per row at jittered offsets, no two rows alike: no compressed form applies)."""
 import argparse
 import json
@@ -70,8 +78,14 @@ def use(plain):
         os.environ.pop("KRYST_SPMV_COMPRESS", None)
 
 
-def operator(name, N, ctx):
-    return band(N, ctx) if name == "band" else K.CsrMatrix.stencil7(N, name, ctx=ctx)
+def operator(name, N, ctx, dia=False):
+    """dia: created under KRYST_SPMV_DIA=2, so that an operator with a more compact form keeps CSR-DIA streams as well"""
+    if dia:
+        os.environ["KRYST_SPMV_DIA"] = "2"
+    try:
+        return band(N, ctx) if name == "band" else K.CsrMatrix.stencil7(N, name, ctx=ctx)
+    finally:
+        os.environ.pop("KRYST_SPMV_DIA", None)
 
 
 def encoding(a, plain):
@@ -226,10 +240,26 @@ def refine_case(name, N, reps, jacobi):
 
 
 
-# ---------------------------------------------------------------------------------------------------------------- the row-pattern lowering
-SPMV32_KNOBS = ("KRYST_SPMV32_FORM", "KRYST_SPMV32_STAGE", "KRYST_SPMV32_STAGE_T")
-SPMV32_KERNELS = {"fp32_plain": ({"KRYST_SPMV32_FORM": "plain"}, "plain"), "fp32_pattern": ({"KRYST_SPMV32_STAGE": "0"}, "pattern"),
-                  "fp32_stage_t1": ({"KRYST_SPMV32_STAGE_T": "1"}, "pattern-stage"), "fp32_stage_t2": ({"KRYST_SPMV32_STAGE_T": "2"}, "pattern-stage")}
+# ---------------------------------------------------------------------------------------------------------------- the row-pattern and the diagonal lowering
+# form: "pattern" (pspmv / prate / prefine) or "dia" (dspmv / drate / drefine)
+SPMV32_KNOBS = ("KRYST_SPMV32_FORM", "KRYST_SPMV32_STAGE", "KRYST_SPMV32_STAGE_T", "KRYST_SPMV32_DIA_NT", "KRYST_SPMV32_BLOCKS_PER_CU")
+SPMV32_KERNELS = {
+    "pattern": {"fp32_plain": ({"KRYST_SPMV32_FORM": "plain"}, "plain"), "fp32_pattern": ({"KRYST_SPMV32_STAGE": "0"}, "pattern"),
+                "fp32_stage_t1": ({"KRYST_SPMV32_STAGE_T": "1"}, "pattern-stage"), "fp32_stage_t2": ({"KRYST_SPMV32_STAGE_T": "2"}, "pattern-stage")},
+    "dia": {"fp32_plain": ({"KRYST_SPMV32_FORM": "plain"}, "plain"), "fp32_dia": ({}, "dia"),
+            "fp32_dia_plain_loads": ({"KRYST_SPMV32_DIA_NT": "0"}, "dia"), "fp32_dia_nontemporal": ({"KRYST_SPMV32_DIA_NT": "1"}, "dia"),
+            "fp32_dia_bpc1": ({"KRYST_SPMV32_BLOCKS_PER_CU": "1"}, "dia"), "fp32_dia_bpc2": ({"KRYST_SPMV32_BLOCKS_PER_CU": "2"}, "dia"),
+            "fp32_dia_bpc4": ({"KRYST_SPMV32_BLOCKS_PER_CU": "4"}, "dia")}}
+
+
+def yardstick(a, form):
+    """the fp64 encoding the case is measured against, for the whole case: the operator's own, or CSR-DIA (spmv_dia_kernel) for the diagonal form"""
+    if form != "dia":
+        return encoding(a, False)
+    os.environ["KRYST_SPMV_COMPRESS"] = "1"
+    e = a.encoding()[0]
+    assert e == "csr-dia", e
+    return e
 
 
 def knobs32(env):
@@ -238,12 +268,13 @@ def knobs32(env):
     os.environ.update(env)
 
 
-def pspmv_case(name, N, reps):
+def pspmv_case(name, N, reps, form="pattern"):
     ctx = K.Context(0)
-    a = operator(name, N, ctx)
-    a32 = a.lower("pattern")
+    a = operator(name, N, ctx, dia=form == "dia")
+    a32 = a.lower(form)
     n, nnz = a.nrows(), a.nnz
-    enc = encoding(a, False)                               # the fp64 yardstick: the operator's own encoding, for the whole case
+    enc = yardstick(a, form)
+    D = a.encoding()[1] if form == "dia" else 0
     x, y = ctx.vec(n).fill_splitmix(3), ctx.vec(n)
     x32, y32 = K.DeviceVec32.from_f64(x), K.DeviceVec32(ctx, n)
     knobs32({})
@@ -257,7 +288,7 @@ def pspmv_case(name, N, reps):
         return ctx.timer_stop() / launches
 
     sides = {"fp64_default": ((lambda: a.spmv(x, y)), {})}
-    for k, (env, kernel) in SPMV32_KERNELS.items():
+    for k, (env, kernel) in SPMV32_KERNELS[form].items():
         if kernel != "pattern-stage" or staged:
             knobs32(env)
             assert a32.encoding() == kernel, (k, a32.encoding())
@@ -268,11 +299,13 @@ def pspmv_case(name, N, reps):
         count[k] = max(20, int(math.ceil(WINDOW_S * 1.2 / (window(fn, 50, env) * 1e-3))))
     r = alternate({k: (lambda k=k: window(sides[k][0], count[k], sides[k][1])) for k in sides}, reps)
     knobs32({})
-    nbytes = {"fp64_default": 18 * n if enc == "csr-p16" else None, "fp32_plain": 8 * nnz + 4 * (n + 1) + 8 * n}
-    rec = {"case": "pspmv", "op": name, "N": N, "n": n, "nnz": nnz, "windows": reps, "launches_per_window": count, "fp64_encoding": enc,
+    nbytes = {"fp64_default": 18 * n if enc == "csr-p16" else (8 * D + 16) * n if form == "dia" else None, "fp32_plain": 8 * nnz + 4 * (n + 1) + 8 * n}
+    rec = {"case": form[0] + "spmv", "op": name, "N": N, "n": n, "nnz": nnz, "windows": reps, "launches_per_window": count, "fp64_encoding": enc,
            "fp64_pattern_info": a.pattern_info(), "default_kernel": a32.encoding()}
+    if form == "dia":
+        rec["diagonals"] = D
     for k in sides:
-        b = nbytes.get(k, 10 * n)
+        b = nbytes.get(k, (4 * D + 8) * n if form == "dia" else 10 * n)
         rec[k + "_ms"] = round(r[k], 5)
         if b:
             rec[k + "_bytes_per_row"] = round(b / n, 2)
@@ -282,12 +315,13 @@ def pspmv_case(name, N, reps):
     emit(rec)
 
 
-def prate_case(name, N, reps):
+def prate_case(name, N, reps, form="pattern"):
     ctx = K.Context(0)
-    a = operator(name, N, ctx)
-    lowered = {"fp32_pattern": a.lower("pattern"), "fp32_plain": a.lower()}
+    a = operator(name, N, ctx, dia=form == "dia")
+    fp32_form = "fp32_" + form
+    lowered = {fp32_form: a.lower(form), "fp32_plain": a.lower()}
     n = a.nrows()
-    enc = encoding(a, False)
+    enc = yardstick(a, form)
     knobs32({})
     b = a.spmv(ctx.vec(n).fill(1.0))
     b32 = K.DeviceVec32.from_f64(b)
@@ -306,9 +340,9 @@ def prate_case(name, N, reps):
             st = cls64(0.0, iters).solve(a, pc, b, x) if kind == "fp64_default" else cls32(0.0, iters).solve(lowered[kind], pc, b32, x32)
             return time.perf_counter() - t0, st.iterations
 
-        rec = {"case": "prate", "op": name, "N": N, "n": n, "method": method, "windows": reps, "fp64_encoding": enc,
-               "fp32_pattern_kernel": lowered["fp32_pattern"].encoding()}
-        kinds = ("fp32_pattern", "fp32_plain", "fp64_default")
+        rec = {"case": form[0] + "rate", "op": name, "N": N, "n": n, "method": method, "windows": reps, "fp64_encoding": enc,
+               fp32_form + "_kernel": lowered[fp32_form].encoding()}
+        kinds = (fp32_form, "fp32_plain", "fp64_default")
         its, lo, hi = {}, {k: [] for k in kinds}, {k: [] for k in kinds}
         for kind in kinds:
             timed(kind, 10)
@@ -324,26 +358,26 @@ def prate_case(name, N, reps):
             rec[kind + "_iterations"] = [n_lo, n_hi]
             rec[kind + "_window_s"] = round(t_hi - t_lo, 4)
             rec[kind + "_iterations_per_s"] = round((n_hi - n_lo) / (t_hi - t_lo), 2) if n_hi > n_lo and t_hi > t_lo else None
-        for kind in ("fp32_pattern", "fp32_plain"):
+        for kind in (fp32_form, "fp32_plain"):
             if rec[kind + "_iterations_per_s"] and rec["fp64_default_iterations_per_s"]:
                 rec["ratio_" + kind + "_over_fp64_default"] = round(rec[kind + "_iterations_per_s"] / rec["fp64_default_iterations_per_s"], 3)
         emit(rec)
 
 
-def prefine_case(name, N, reps, jacobi):
+def prefine_case(name, N, reps, jacobi, form="pattern"):
     ctx = K.Context(0)
-    a = operator(name, N, ctx)
+    a = operator(name, N, ctx, dia=form == "dia")
     n = a.nrows()
-    enc = encoding(a, False)
+    enc = yardstick(a, form)
     knobs32({})
     b = a.spmv(ctx.vec(n).fill_splitmix(7))
     x = ctx.vec(n)
     cap = 20000
     pc = K.Jacobi().setup(a) if jacobi else None
     fp64 = K.PcgSolver if jacobi else K.CgSolver
-    refs = {form: K.RefinementSolver(1e-10, 40).with_inner(1e-6, cap).with_form(form) for form in ("pattern", "plain")}
-    rec = {"case": "prefine", "op": name, "N": N, "n": n, "inner": "pcg_jacobi" if jacobi else "cg", "outer_tol": 1e-10, "inner_tol": 1e-6,
-           "runs": reps, "fp64_encoding": enc, "kernels": {form: r.lowered(a).encoding() for form, r in refs.items()}}
+    refs = {f: K.RefinementSolver(1e-10, 40).with_inner(1e-6, cap).with_form(f) for f in (form, "plain")}
+    rec = {"case": form[0] + "refine", "op": name, "N": N, "n": n, "inner": "pcg_jacobi" if jacobi else "cg", "outer_tol": 1e-10, "inner_tol": 1e-6,
+           "runs": reps, "fp64_encoding": enc, "kernels": {f: r.lowered(a).encoding() for f, r in refs.items()}}
 
     def run_refine(form):
         ref = refs[form]
@@ -366,22 +400,22 @@ def prefine_case(name, N, reps, jacobi):
         rec["fp64_default"] = {"iterations": st.iterations, "converged": st.converged}
         return ms
 
-    for form, r in refs.items():                           # warm-up: first-use allocations on every path
-        warm = K.RefinementSolver(1e-10, 1).with_inner(1e-6, 5).with_form(form)
+    for f, r in refs.items():                              # warm-up: first-use allocations on every path
+        warm = K.RefinementSolver(1e-10, 1).with_inner(1e-6, 5).with_form(f)
         warm._lowered.update(r._lowered)
         warm.solve(a, pc, b, ctx.vec(n))
     fp64(0.0, 5).solve(a, pc, b, ctx.vec(n))
-    ms = alternate({"refine_pattern": lambda: run_refine("pattern"), "fp64_default": run_fp64, "refine_plain": lambda: run_refine("plain")}, reps)
+    ms = alternate({"refine_" + form: lambda: run_refine(form), "fp64_default": run_fp64, "refine_plain": lambda: run_refine("plain")}, reps)
     for k, v in ms.items():
         rec[k]["ms"] = round(v, 2)
-    for form in ("pattern", "plain"):
-        rec["time_ratio_fp64_over_refine_" + form] = round(ms["fp64_default"] / ms["refine_" + form], 3)
+    for f in (form, "plain"):
+        rec["time_ratio_fp64_over_refine_" + f] = round(ms["fp64_default"] / ms["refine_" + f], 3)
     emit(rec)
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=("spmv", "rate", "refine", "pspmv", "prate", "prefine"))
+    ap.add_argument("mode", choices=("spmv", "rate", "refine", "pspmv", "prate", "prefine", "dspmv", "drate", "drefine"))
     ap.add_argument("N", type=int)
     ap.add_argument("--op", default="poisson", choices=("poisson", "varcoef", "band"))
     ap.add_argument("--reps", type=int, default=3)
@@ -393,11 +427,11 @@ if __name__ == "__main__":
         spmv_case(args.op, args.N, args.reps)
     elif args.mode == "rate":
         rate_case(args.op, args.N, args.reps)
-    elif args.mode == "pspmv":
-        pspmv_case(args.op, args.N, args.reps)
-    elif args.mode == "prate":
-        prate_case(args.op, args.N, args.reps)
-    elif args.mode == "prefine":
-        prefine_case(args.op, args.N, args.reps, args.jacobi or args.op == "varcoef")
+    elif args.mode in ("pspmv", "dspmv"):
+        pspmv_case(args.op, args.N, args.reps, "dia" if args.mode[0] == "d" else "pattern")
+    elif args.mode in ("prate", "drate"):
+        prate_case(args.op, args.N, args.reps, "dia" if args.mode[0] == "d" else "pattern")
+    elif args.mode in ("prefine", "drefine"):
+        prefine_case(args.op, args.N, args.reps, args.jacobi or args.op == "varcoef", "dia" if args.mode[0] == "d" else "pattern")
     else:
         refine_case(args.op, args.N, args.reps, args.jacobi or args.op == "varcoef")
