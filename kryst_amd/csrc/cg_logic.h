@@ -2,11 +2,59 @@
 // on the reduced values.  Shared by the single-vector solvers (cg_pcg.hip) and the batched ones (multi.hip), which bind one instance per
 // column to that column's DevState -- the same code, so the same scalars.
 #pragma once
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+namespace kr {
+
+// ---- x paid in SLICES (cg_pcg.hip: DirectionVec, XBatchOp): which rows owe which x updates.  Host only -- no device type, no HIP call -- so that
+// tests/cpp/test_x_slices.cpp drives it on the CPU (it defines KRYST_X_SLICES_HOST_ONLY, which ends this header after the struct).
+// With a batch length m the NT tiles of the vector are cut into `slices` ranges on tile boundaries, slice j = tiles [j NT / slices, (j + 1) NT / slices)
+// (empty where NT < slices).  slices == 1: the whole vector in one pass every m iterations.  slices == m: iteration `it` pays slice it % m, the
+// updates applied[j] + 1 .. it, which are m of them once the first m iterations are behind (1 .. m before that).  Per row the updates stay
+// x = x + alpha_i p_i for i ascending, each applied once: the bits do not depend on the cut.
+// Ring safety: p_i lives in slot i % (m + 1) and the fused SpMV (or the ring direction pass) that forms p_{it+1} overwrites the slot of p_{it-m}.
+// After advance(it) every slice has applied[j] >= it - m + 1 (slices == m: slice j was paid at one of the last m iterations; slices == 1: at the
+// last multiple of m), so no launch -- neither a later advance nor the flush -- ever reads a slot that has been overwritten.
+struct XSliceLaunch { int64_t tile_lo, tile_hi; long long lo, hi; };          // x += alpha_i p_i for i = lo .. hi on tiles [tile_lo, tile_hi)
+struct XSlices {
+    int m = 1, slices = 1; int64_t nt = 0;
+    std::vector<long long> applied;                                           // per slice: the last iteration whose update its rows have
+    void init(int m_, int64_t nt_, bool sliced) {
+        m = std::max(1, m_); nt = std::max<int64_t>(0, nt_); slices = sliced ? m : 1;
+        applied.assign((size_t)slices, 0);
+    }
+    int64_t tile_at(int j) const { return (int64_t)j * nt / slices; }           // (j <= 32 and nt < 2^53: no overflow)
+    bool launch_of(int j, long long upto, XSliceLaunch* out) {
+        const XSliceLaunch l{tile_at(j), tile_at(j + 1), applied[(size_t)j] + 1, upto};
+        applied[(size_t)j] = std::max(applied[(size_t)j], upto);
+        if (l.hi < l.lo || l.tile_hi <= l.tile_lo) return false;              // nothing owed, or an empty slice
+        *out = l;
+        return true;
+    }
+    // iteration `it` has been enqueued: the launch it pays, if any
+    bool advance(long long it, XSliceLaunch* out) {
+        const int j = (int)(it % m);
+        return j < slices && launch_of(j, it, out);
+    }
+    // no further iteration follows `upto` for now: what every slice still owes.  The bookkeeping stays valid for a session that goes on.
+    void flush(long long upto, std::vector<XSliceLaunch>& out) {
+        out.clear();
+        XSliceLaunch l;
+        for (int j = 0; j < slices; ++j)
+            if (launch_of(j, upto, &l)) out.push_back(l);
+    }
+};
+
+}  // namespace kr
+
+#ifndef KRYST_X_SLICES_HOST_ONLY
 #include "solver_common.h"
 
 namespace kr {
 
-struct CgInitLogic {                 // cg.rs:127-140
+struct CgInitLogic {             // cg.rs:127-140
     static constexpr bool RUN_WHEN_DONE = false;
     LogicCtx c;
     __device__ void run(const double* red) const {
@@ -125,3 +173,4 @@ struct PcgBetaLogic {                // pcg.rs:188-218
 };
 
 }  // namespace kr
+#endif  // KRYST_X_SLICES_HOST_ONLY

@@ -285,21 +285,22 @@ struct GateXBatch {                  // nothing to apply: the solve ended before
     __device__ __forceinline__ bool skip() const { return st->xpend < lo; }
 };
 template <int M>
-inline int32_t launch_x_batch_m(kryst_ctx_t ctx, DevState* st, const std::vector<double*>& ring, int xb, long long lo, long long hi, double* x, int64_t n) {
+inline int32_t launch_x_batch_m(kryst_ctx_t ctx, DevState* st, const std::vector<double*>& ring, int xb, long long lo, long long hi, double* x, int64_t n, int64_t tile_lo, int64_t tile_hi) {
     XBatchOp<M> op; op.st = st; op.lo = lo; op.cnt = (int)(hi - lo + 1); op.x = x;
     for (int u = 0; u < KR_XB_MAX; ++u) op.p[u] = ring[(size_t)((lo + std::min<long long>(u, hi - lo)) % (xb + 1))];
-    return launch_ew_gated(ctx, op, n, GateXBatch{st, lo});
+    return launch_ew_gated(ctx, op, n, GateXBatch{st, lo}, 0, tile_lo, tile_hi);
 }
-// x += alpha_i p_i for iterations lo .. hi (those that happened), p_i in ring[i % (xb + 1)].  Every length from 2 to KR_XB_MAX has an instance of its
+// x += alpha_i p_i for iterations lo .. hi (those that happened) on tiles [tile_lo, tile_hi) (-1: to the end), p_i in ring[i % (xb + 1)].  Every length from 2 to KR_XB_MAX has an instance of its
 // own -- a full batch, and the partial one the flush at the end of a solve or session owes (up to xb - 1 updates: one pass with all its loads in
 // flight, not one dependent load after the other); a single update takes the any-length instance
-inline int32_t launch_x_batch(kryst_ctx_t ctx, DevState* st, const std::vector<double*>& ring, int xb, long long lo, long long hi, double* x, int64_t n) {
+inline int32_t launch_x_batch(kryst_ctx_t ctx, DevState* st, const std::vector<double*>& ring, int xb, long long lo, long long hi, double* x, int64_t n,
+                              int64_t tile_lo = 0, int64_t tile_hi = -1) {
     int32_t rc = KRYST_OK;
     const int cnt = (int)(hi - lo + 1);
     KR_ARG(cnt >= 1 && cnt <= KR_XB_MAX, "launch_x_batch: a batch of more than 32 iterations");
-    auto exact = [&](auto M) { rc = launch_x_batch_m<M()>(ctx, st, ring, xb, lo, hi, x, n); };
+    auto exact = [&](auto M) { rc = launch_x_batch_m<M()>(ctx, st, ring, xb, lo, hi, x, n, tile_lo, tile_hi); };
     if (by_int<2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>(cnt, exact) || by_int<17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32>(cnt, exact)) return rc;
-    return launch_x_batch_m<0>(ctx, st, ring, xb, lo, hi, x, n);
+    return launch_x_batch_m<0>(ctx, st, ring, xb, lo, hi, x, n, tile_lo, tile_hi);
 }
 // x-batch length: 1 = every iteration (x rides on the fused pass that reads p_old); KRYST_CG_X_BATCH forces (<= 32).  Measured at 512^3
 // (profiles/r05/cg_xbatch_ab.jsonl): CG 545 / 560 / 575 / 579 / 584 / 582 / 588 it/s at m = 1 / 2 / 4 / 5 / 6 / 7 / 8 (unfused 530); PCG 447 / 459 / 487 /
@@ -311,6 +312,19 @@ inline int32_t launch_x_batch(kryst_ctx_t ctx, DevState* st, const std::vector<d
 // 30 it/s (541 in the first round, 511 and 517 after the longer rings had been allocated): short of the margin, so PCG stays at 7.
 inline int cg_x_batch(bool pcg) {
     return std::max(1, std::min(KR_XB_MAX, env_int("KRYST_CG_X_BATCH", pcg ? 7 : 32)));
+}
+// how a batch is paid (read in plan(): once per solve or session).  0: all rows in one pass every m-th iteration.  1: the rows cut into m slices,
+// iteration it pays slice it % m -- the same bytes, spread evenly: no iteration carries the whole pass (6.6 ms at 512^3 and m = 32 beside 1.2 ms
+// for every other iteration, so a short solve or a timing window of 20 iterations used to see one pass more or less).
+// Measured at 512^3 (profiles/x_slices/): the slice launch of m = 32 takes 193 us (34 streams over 32 MiB each at 5.90 TB/s) where the whole pass took
+// 6610 us = 206.6 per iteration (5.55 TB/s), and the fused SpMV behind it 596 instead of 612 us.  In one process, whole rounds timed, three rounds:
+// CG m = 32 718.7 -> 730.6 it/s, PCG m = 7 539.5 -> 540.9, every run in slices above every run of the whole pass, the means apart by more than
+// twice the larger spread -- so slices for both.  bench.py alternating with the parent commit: 710.1 -> 730.8 it/s (+2.9 %, every
+// run above every run), 675.4 -> 749.5 at --steps 20 --warmup 5, where the parent's windows held the whole pass or not.
+// The slices on a low-priority stream of their own beside the dependent chain (ordered by events) were built, measured and taken out again:
+// beside a slice the fused SpMV takes 786 us and the slice 462, together what they take one after the other (596 + 193), and CG ran 695.1 it/s.
+inline int cg_x_slice() {
+    return env_int("KRYST_CG_X_SLICE", 1) != 0 ? 1 : 0;
 }
 // the ring costs xb - 1 work vectors more than the two alternating direction vectors: only where the device has the room (what the context's
 // arena already holds counts as room).  base: the solver's other work vectors.  A ring that does not fit is halved until one does (32 -> 16 -> 8 ..)
@@ -343,9 +357,9 @@ struct __attribute__((visibility("hidden"))) DirectionVec {
     bool fuse = false; long long fused_upto = 0;     // fused_upto: the last iteration enqueued in the fused form (its x update rides on the next one)
     int xb = 1; std::vector<double*> ring;           // xb > 1: x in batches of xb iterations, direction vector of iteration k in ring[k % (xb + 1)]
     bool ringdir = false;                            // the unfused deferred form with the ring (CgDirectionRingOp)
-    int32_t x_batch(long long lo, long long hi) {    // apply the x updates of iterations lo .. hi (those that happened)
-        if (hi < lo) return KRYST_OK;
-        return launch_x_batch(s.ctx, s.ws.st, ring, xb, lo, hi, s.xw, s.n);
+    XSlices xs;                                      // xb > 1: which rows owe which x updates (cg_logic.h)
+    int32_t x_batch(const XSliceLaunch& l) {         // apply the x updates of iterations l.lo .. l.hi (those that happened) to the rows of l's tiles
+        return launch_x_batch(s.ctx, s.ws.st, ring, xb, l.lo, l.hi, s.xw, s.n, l.tile_lo, l.tile_hi);
     }
     // begin(), first: the form of this solve.  deferred: x += alpha p may ride on the direction pass; base: the solver's work vectors besides x and the
     // ring (CG 3, PCG 4).  -> the work vectors to reserve
@@ -355,6 +369,7 @@ struct __attribute__((visibility("hidden"))) DirectionVec {
         xb = fuse ? cg_x_batch(pcg) : deferred ? cg_x_batch_unfused() : 1;
         xb = ring_if_it_fits(s.ctx, s.n, xb, base);
         ringdir = !fuse && xb > 1;
+        xs.init(xb, ntiles_of(s.n), cg_x_slice() != 0);
         return xb > 1 ? base + xb + 1 : fuse ? 5 : 4;
     }
     // begin(), once pp has been taken from the workspace: the other vectors p needs
@@ -396,12 +411,18 @@ struct __attribute__((visibility("hidden"))) DirectionVec {
             pp = p_new;
         }
         fused_upto = it;
-        if (xb > 1 && it % xb == 0) KR_TRY(x_batch(it - xb + 1, it));                              // the x updates of the last xb iterations, one pass
+        XSliceLaunch l;
+        if (xb > 1 && xs.advance(it, &l)) KR_TRY(x_batch(l));                                     // the x updates this iteration pays: the last xb on one slice of the rows, or on all rows every xb-th iteration
         return KRYST_OK;
     }
     int32_t flush() {
         if ((!fuse && !ringdir) || fused_upto == 0) return KRYST_OK;
-        if (xb > 1) return x_batch(fused_upto / xb * xb + 1, fused_upto);                         // what the last partial batch owes
+        if (xb > 1) {                                                                             // what every slice still owes (one slice: the last partial batch)
+            std::vector<XSliceLaunch> owed;
+            xs.flush(fused_upto, owed);
+            for (const XSliceLaunch& l : owed) KR_TRY(x_batch(l));
+            return KRYST_OK;
+        }
         return launch_ew_gated(s.ctx, CgFlushOp{s.ws.st, pp, s.xw}, s.n, GateXOwed{s.ws.st, fused_upto});
     }
 };

@@ -1,7 +1,8 @@
 """CG / PCG iterations per second with x updated in BATCHES (KRYST_CG_X_BATCH = m <= 32: x += alpha_i p_i for m iterations in one pass, XBatchOp) against
 the fused form that updates x every iteration (m = 1) and the unfused form, interleaved in ONE process on one operator instance.  Every form is
 timed over whole batches: the warm-up and the timed stretch are multiples of its m, the timed stretch at least 4 m iterations.
-usage: [XB_LIST=1,8,12,16,24,32] [SOLVERS=cg,pcg] cg_xbatch_ab.py [grid=512] [steps=192] [rounds=3]"""
+XS_LIST: the ways a batch is paid (KRYST_CG_X_SLICE: 0 = all rows every m-th iteration, 1 = one slice of the rows per iteration), each m > 1 with each.
+usage: [XB_LIST=1,8,12,16,24,32] [XS_LIST=0,1] [SOLVERS=cg,pcg] cg_xbatch_ab.py [grid=512] [steps=192] [rounds=3]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import kryst_amd as K
@@ -9,14 +10,16 @@ grid = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 192
 rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 3
 MS = [int(v) for v in os.environ.get("XB_LIST", "1,8,12,16,24,32").split(",")]
+XS = [int(v) for v in os.environ.get("XS_LIST", "0,1").split(",")]
 SOLVERS = os.environ.get("SOLVERS", "cg,pcg").split(",")
 ctx = K.Context(0)
 a = K.CsrMatrix.stencil7(grid, "poisson", ctx=ctx)
 n = a.nrows()
 b = a.spmv(ctx.vec(n).fill(1.0))
 pcj = K.Jacobi().setup(a)
-forms = [("unfused", 1, {"KRYST_CG_FUSE_P": "0", "KRYST_CG_X_BATCH": "1"})] + \
-        [(f"fused x-batch {m}", m, {"KRYST_CG_FUSE_P": "1", "KRYST_SPMV_FUSE_T": "4", "KRYST_CG_X_BATCH": str(m)}) for m in MS]
+forms = [("unfused", 1, {"KRYST_CG_FUSE_P": "0", "KRYST_CG_X_BATCH": "1", "KRYST_CG_X_SLICE": "0"})] + \
+        [(f"fused x-batch {m}" + (" in slices" if xs else ""), m, {"KRYST_CG_FUSE_P": "1", "KRYST_SPMV_FUSE_T": "4", "KRYST_CG_X_BATCH": str(m), "KRYST_CG_X_SLICE": str(xs)})
+         for m in MS for xs in (XS if m > 1 else [0])]
 res = {}
 for method, pc in (("cg", None), ("pcg", pcj)):
     if method not in SOLVERS:
