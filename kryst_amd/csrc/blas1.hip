@@ -142,6 +142,14 @@ int32_t launch_final_fold(kryst_ctx_t ctx, int nq, int64_t ntiles, double* d_out
     return KRYST_OK;
 }
 
+int32_t fold_to_host(kryst_ctx_t ctx, int64_t ntiles, double* out) {
+    KR_TRY(launch_final_fold(ctx, 1, ntiles, dot_slot(ctx)));
+    KR_HIP(hipMemcpyAsync(ctx->h_pinned, dot_slot(ctx), sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
+    KR_HIP(hipStreamSynchronize(ctx->s_main));
+    *out = ctx->h_pinned[0];
+    return *out != *out && fold_gave_up(ctx) ? KRYST_ERR_HIP : KRYST_OK;
+}
+
 int32_t vec_check2(kryst_vec_t a, kryst_vec_t b) {
     KR_ARG(a && b, "null vector");
     KR_ARG(a->ctx == b->ctx, "vectors belong to different contexts");
@@ -224,17 +232,8 @@ int32_t kryst_dot(kryst_vec_t x, kryst_vec_t y, double* out) {
     kryst_ctx_t ctx = x->ctx;
     KR_HIP(hipSetDevice(ctx->device));
     KR_TRY(launch_ew(ctx, DotOp{x->d, y->d}, x->n));
-    // result slot of its own (d_scal[1024]): d_scal[0..512) is the scalar state of an open solve / stepping session, and the
-    // partials / chunk / ticket scratch is consumed in stream order, so a dot between two session steps disturbs nothing
-    double* slot = ctx->d_scal + 1024;
-    if (!use_collectives(ctx)) {
-        KR_TRY(launch_final_fold(ctx, 1, ntiles_of(x->n), slot));
-        KR_HIP(hipMemcpyAsync(ctx->h_pinned, slot, sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
-        KR_HIP(hipStreamSynchronize(ctx->s_main));
-        *out = ctx->h_pinned[0];
-        if (*out != *out && fold_gave_up(ctx)) return KRYST_ERR_HIP;
-        return KRYST_OK;
-    }
+    if (!use_collectives(ctx)) return fold_to_host(ctx, ntiles_of(x->n), out);
+    double* slot = dot_slot(ctx);
     // several ranks: local fold -> all-gather of one double per rank -> the result goes to the host anyway, so the rank-ordered
     // fold (total = r0; total = total + r_p: the same bits on every rank) runs there: two launches and one collective per dot,
     // like the solvers' reduce_then (whose rank-ordered fold shares a launch with the scalar step that consumes it)

@@ -210,7 +210,7 @@ static int32_t make_checked_w(kryst_csr_t a, double** out) {
     double* w = nullptr;
     KR_TRY(alloc_vec(ctx, &w, a->nrows));
     int32_t rc = jacobi_inv_diag_dev(a, w);
-    unsigned long long* d_bad = reinterpret_cast<unsigned long long*>(ctx->d_scal + 1024);   // kryst_dot's result slot: nothing is in flight between calls
+    unsigned long long* d_bad = reinterpret_cast<unsigned long long*>(dot_slot(ctx));   // kryst_dot's result slot: nothing is in flight between calls
     unsigned long long bad = ~0ull;
     if (rc == KRYST_OK && a->nrows > 0) {
         hipError_t e = hipMemcpyAsync(d_bad, &bad, sizeof bad, hipMemcpyHostToDevice, ctx->s_main);
@@ -335,7 +335,7 @@ int32_t kryst_spectrum_estimate(kryst_csr_t a, int32_t scaling, int32_t steps, u
     }
     // Gershgorin bound of W A
     {
-        unsigned long long* d_g = reinterpret_cast<unsigned long long*>(ctx->d_scal + 1024);
+        unsigned long long* d_g = reinterpret_cast<unsigned long long*>(dot_slot(ctx));
         KR_HIP(hipMemsetAsync(d_g, 0, sizeof(unsigned long long), ctx->s_main));
         hipLaunchKernelGGL(cheb_gershgorin_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->s_main, a->d_row_ptr, a->d_val, L.w, (int32_t)n, d_g);
         KR_HIP(hipGetLastError());

@@ -29,18 +29,21 @@ namespace kr {
 struct EnvSlot { std::atomic<uint32_t> epoch{0}; std::atomic<int> has{0}; std::atomic<long long> val{0}; };
 extern std::atomic<uint32_t> g_env_epoch;        // ctx.cpp
 extern thread_local int g_env_frozen;
-inline long long env_ll_cached(EnvSlot& s, const char* name, long long dflt) {
+// `parse` turns the text of a knob that is set into its value (a number: atoll; a word: the site's own); unset gives dflt
+inline long long env_parsed_cached(EnvSlot& s, const char* name, long long dflt, long long (*parse)(const char*)) {
     if (g_env_frozen > 0) {
         const uint32_t e = g_env_epoch.load(std::memory_order_relaxed);
         if (s.epoch.load(std::memory_order_acquire) == e) return s.has.load(std::memory_order_relaxed) ? s.val.load(std::memory_order_relaxed) : dflt;
         const char* v = getenv(name);
-        s.has.store(v ? 1 : 0, std::memory_order_relaxed); s.val.store(v ? atoll(v) : 0, std::memory_order_relaxed);
+        const long long x = v ? parse(v) : dflt;
+        s.has.store(v ? 1 : 0, std::memory_order_relaxed); s.val.store(x, std::memory_order_relaxed);
         s.epoch.store(e, std::memory_order_release);
-        return v ? atoll(v) : dflt;
+        return x;
     }
     const char* v = getenv(name);
-    return v ? atoll(v) : dflt;
+    return v ? parse(v) : dflt;
 }
+inline long long env_ll_cached(EnvSlot& s, const char* name, long long dflt) { return env_parsed_cached(s, name, dflt, atoll); }
 struct EnvFreeze {                               // RAII around a solver's enqueue loop
     EnvFreeze() { if (g_env_frozen++ == 0) g_env_epoch.fetch_add(1, std::memory_order_relaxed); }
     ~EnvFreeze() { --g_env_frozen; }
@@ -353,6 +356,11 @@ int32_t launch_final_fold(kryst_ctx_t ctx, int nq, int64_t ntiles, double* d_out
 // reads and clears the polling hand-off's error word; when it was raised: sets the error text, switches the context to the ticket form
 // and returns true (blas1.hip)
 bool fold_gave_up(kryst_ctx_t ctx);
+// kryst_dot's result slot: d_scal[0..512) is the scalar state of an open solve / stepping session, and the partials / chunk / ticket scratch is
+// consumed in stream order, so a dot between two session steps disturbs nothing
+inline double* dot_slot(kryst_ctx_t ctx) { return ctx->d_scal + 1024; }
+// single rank: partial array 0 -> the final fold into dot_slot -> *out on the host; a NaN that stands for a fold that gave up is KRYST_ERR_HIP (blas1.hip)
+int32_t fold_to_host(kryst_ctx_t ctx, int64_t ntiles, double* out);
 int32_t vec_check2(kryst_vec_t a, kryst_vec_t b);
 bool use_collectives(kryst_ctx_t ctx);
 

@@ -1,8 +1,12 @@
-// Mixed precision: fp32 as a STORAGE format.  Vectors and matrix values are kept as floats; every kernel widens what
-// it loads, computes in fp64 in the fixed order of its fp64 twin and rounds once -- (float), round to nearest even -- when it stores.  Scalars,
-// inner products, DevState and the logic structs of cg_logic.h stay fp64 and are the fp64 solvers' own code.
+// Mixed precision (with the map of the family's units): the two handles and what crosses the units.
+// The arithmetic contract -- a LABELLED DEVIATION from the reference's CgSolver<f32>, which would round every operation: fp32 is how numbers are
+// STORED.  A kernel widens what it loads (exact), computes in fp64 in the fixed order of its fp64 twin with separate multiply and add, and rounds
+// once, (float) = round to nearest even with fp32 subnormals kept, when it stores.  An inner-product term (double)a * (double)b is exact; the fold
+// is the published tree at T = 256, V = 4 (kryst_reduce_spec32): the thread's 4 terms in index order from 0.0, the 64-lane xor butterfly, the 4
+// waves serially -> one partial per 1024-element tile, then fold2, DevState and the logic structs of cg_logic.h, the fp64 solvers' own code.
 #pragma once
 #include "csr.h"
+#include <cfloat>
 
 // ---- the fp32 inner-product tree (kryst_reduce_spec32): a tile is 256 threads x 4 consecutive elements, one 16-byte access per array and lane ----
 #define KR32_T 256
@@ -41,22 +45,56 @@ namespace kr {
 
 inline int64_t ntiles32_of(int64_t n) { return (n + KR32_TILE - 1) / KR32_TILE; }
 inline int64_t vec32_len(int64_t n) { return ntiles32_of(n) * KR32_TILE + KR32_TILE; }      // allocated floats
+inline int64_t ws_len32(int64_t n) { return vec32_len(n) / 2 - KR_TILE; }                   // the Workspace length whose vectors are one fp32 vector each
+static inline unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 4096)); }   // 256-thread grid-stride passes (static: multi.hip has its own, with another cap)
 
-// y <- (float)(A x) on ctx->s_main; nq = 1: also the tile partials of sum_i d[i] * y[i] (y as stored) in the fp32 tree into partial array 0.
-// `done` (device flag) makes the launch a no-op when set.
+// ---- mixed_vec.hip: the vector handle and the conversions
+int32_t vec32_check(kryst_vec32_t v);
+int32_t vec32_alloc(kryst_ctx_t ctx, int64_t n, kryst_vec32_t* out);
+void vec32_free(kryst_vec32_t v);
+// dst[i] = (float)src[i], or (float)(src[i] / den) when `divide` is set (refinement: r32 = (float)(r / rho)); n > 0
+hipError_t enqueue_round32(kryst_ctx_t ctx, float* dst, const double* src, int64_t n, int divide, double den);
+
+// ---- mixed_lower.hip: the lowered operator.  Each form lowers itself beside its kernels: *_refusal says why the operator cannot take the form (nullptr: it
+// can; asked before anything is allocated), enqueue_lower_* allocates the form's arrays on m (csr32_free releases them), copies, rounds and sets the fields
+int32_t csr32_check(kryst_csr32_t a);
+inline bool offsets_fit32(kryst_csr_t a) { return vec32_len(std::max(a->nrows, a->ncols)) * (int64_t)sizeof(float) < (1ll << 31); }   // the form kernels address x and y with 32-bit byte offsets
+const char* lower_pattern_refusal(kryst_csr_t a);
+hipError_t enqueue_lower_pattern(kryst_csr_t a, kryst_csr32_t m);
+const char* lower_dia_refusal(kryst_csr_t a);
+hipError_t enqueue_lower_dia(kryst_csr_t a, kryst_csr32_t m, unsigned long long* d_refused);   // *d_refused: stored NaNs whose rounding has the marker's bits
+
+// ---- mixed_spmv.hip: y <- (float)(A x) on ctx->s_main; nq = 1: also the tile partials of sum_i d[i] * y[i] (y as stored) in the fp32 tree into
+// partial array 0.  `done` (device flag) makes the launch a no-op when set.
 int32_t launch_spmv32(kryst_csr32_t a, const float* x, float* y, int nq, const float* dvec, const int* done);
-// the kernel that launch takes under the current settings (KRYST_SPMV32_FORM, KRYST_SPMV32_STAGE): 0 spmv32_wave_kernel on the plain arrays,
-// 1 spmv32_pattern_kernel, 2 spmv32_pattern_stage_kernel, 3 spmv32_dia_kernel.  The ONE place that decides; kryst_csr32_encoding reports it.
-int spmv32_kernel(kryst_csr32_t a);
-// mixed_pattern.hip: the two kernels of the row-pattern form
-int32_t enqueue_spmv32_pattern(kryst_csr32_t a, const float* x, float* y, int nq, const float* dvec, const int* done);
+// the kernel that launch takes under the current settings (KRYST_SPMV32_FORM, KRYST_SPMV32_STAGE): the ONE place that decides; kryst_csr32_encoding reports the value
+enum class Spmv32Kernel : int32_t { Plain = 0, Pattern = 1, PatternStage = 2, Dia = 3 };     // spmv32_wave_ / _pattern_ / _pattern_stage_ / _dia_kernel
+Spmv32Kernel spmv32_kernel(kryst_csr32_t a);
+int32_t enqueue_spmv32_pattern(kryst_csr32_t a, const float* x, float* y, int nq, const float* dvec, const int* done);          // mixed_pattern.hip
 int32_t enqueue_spmv32_pattern_stage(kryst_csr32_t a, const float* x, float* y, int nq, const float* dvec, const int* done);
-// mixed_dia.hip: the kernel of the diagonal form, and the conversion of the fp64 streams (*refused: stored NaNs whose rounding has the marker's bits)
-int32_t enqueue_spmv32_dia(kryst_csr32_t a, const float* x, float* y, int nq, const float* dvec, const int* done);
-hipError_t enqueue_lower_dia(kryst_csr_t a, kryst_csr32_t m, unsigned long long* d_refused);
+int32_t enqueue_spmv32_dia(kryst_csr32_t a, const float* x, float* y, int nq, const float* dvec, const int* done);              // mixed_dia.hip
+
+// ---- mixed_cg.hip: CG (pcg = false) / PCG with Identity or Jacobi on fp32 storage; refinement is the second caller
+struct Solve32IO { kryst_pc_t pc; const kryst_params_t* params; kryst_stats_t* stats; double* hist; int64_t hist_cap; int64_t* hist_len; };
+int32_t solve32_check(kryst_vec32_t b, kryst_vec32_t x, kryst_csr32_t a, const Solve32IO& io, bool pcg);     // what is refused before anything is launched or written
+int32_t solve32(kryst_vec32_t b, kryst_vec32_t x, kryst_csr32_t a, const Solve32IO& io, bool pcg);
+int32_t launch_dot32(kryst_ctx_t ctx, const float* a, const float* b, int64_t n);               // the tile partials of (a, b) into partial array 0
+
+// the verdict of one rounding, shared by the device pass (lower_values_kernel) and its host twin (kryst_host_round_f32)
+__host__ __device__ __forceinline__ float round_count(double v, unsigned long long (&cnt)[3]) {
+    const float f = (float)v;
+    const float af = f < 0.0f ? -f : f;
+    if (v == v) {                                                     // (a NaN stays a NaN and counts as nothing)
+        if ((double)f != v) ++cnt[0];                                 // changed by the rounding
+        if (v != 0.0 && af < FLT_MIN) ++cnt[1];                       // became zero or fp32-subnormal
+        const double av = v < 0.0 ? -v : v;
+        if (av <= DBL_MAX && af > FLT_MAX) ++cnt[2];                  // a finite value that rounds to +-inf
+    }
+    return f;
+}
 
 #ifdef __HIPCC__
-// ---- what the kernels of mixed_pattern.hip and mixed_dia.hip share: thread t of a tile owns rows 4t .. 4t+3 ----
+// ---- what the SpMV kernels share: thread t of a tile owns rows 4t .. 4t+3 ----
 typedef float p_v4f __attribute__((ext_vector_type(4)));
 typedef float p_v4f_a4 __attribute__((ext_vector_type(4), aligned(4)));     // a 16-byte access at 4-byte alignment (gathers at any column)
 
@@ -76,6 +114,22 @@ __device__ __forceinline__ void quad_store(float* y, int32_t row, int32_t nrows,
     } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r) { if (row + r < nrows) y[row + r] = o[r]; }
+    }
+}
+// the end of tile q in the kernels that finish one tile at a time: y = (float)s, one 16-byte store; under NQ the tile partial of (d, y) with y as
+// stored -- the lane's four products, the butterfly, the 4 waves (red: KR32_T / 64 doubles of LDS).  Called by all threads of the workgroup.
+template <int NQ>
+__device__ __forceinline__ void quad_finish(const double (&s)[4], float* y, const float* dvec, double* partials, int32_t q, int32_t row, int32_t nrows, double* red) {
+    float o[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[r] = (float)s[r];
+    quad_store(y, row, nrows, o);
+    if constexpr (NQ > 0) {
+        const p_v4f dd = *reinterpret_cast<const p_v4f*>(dvec + row);       // (rows behind n lie in the padding: read, never used)
+        const bool valid[4] = {row < nrows, row + 1 < nrows, row + 2 < nrows, row + 3 < nrows};
+        double acc[1] = {quad_dot(dd, o, valid)};
+        block_reduce<1, KR32_T / 64>(acc, red);
+        if (threadIdx.x == 0) partials[q] = acc[0];
     }
 }
 #endif

@@ -1,6 +1,7 @@
 // Mixed precision on the diagonal encoding: spmv32_dia_kernel, the SpMV of a lowered operator that keeps fp32 CSR-DIA
-// streams (kryst_csr32_lower_form DIA), its enqueue function, and the kernel that converts the fp64 streams.  mixed.hip has the lowering, the
-// choice (spmv32_kernel) and the solvers; spmv_stream.hip has the fp64 twin, spmv_dia_kernel.
+// streams (kryst_csr32_lower_form DIA), its enqueue function, and the lowering of the form (when an operator can take it, the kernel that converts
+// the fp64 streams, the fields).  mixed_lower.hip has the skeleton of the lowering, mixed_spmv.hip the choice (spmv32_kernel), mixed_cg.hip the
+// solvers; spmv_stream.hip has the fp64 twin, spmv_dia_kernel.
 //
 // The contract is the other fp32 kernels': the fp32 tile of 1024 rows, thread t owns rows 4t .. 4t+3.  y_i = (float) of the fold from 0.0, in
 // diagonal (= stored) order, of (double)v * (double)x[row + off] with separate multiply and add; an absent entry is skipped by a select on its
@@ -85,17 +86,7 @@ __global__ __launch_bounds__(KR32_T) void spmv32_dia_kernel(const Spmv32DiaArgs 
         } else {                                                   // the lowest diagonal would start before x[0]
             for (int d0 = 0; d0 < (EXACT ? 1 : nd); d0 += DB) dia32_batch<DB, EXACT, false, NT>(a, row, d0, nd, s);
         }
-        float o[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] = (float)s[r];
-        quad_store(a.y, row, a.nrows, o);
-        if constexpr (NQ > 0) {
-            const p_v4f dd = *reinterpret_cast<const p_v4f*>(a.dvec + row);             // (rows behind n lie in the padding: read, never used)
-            const bool valid[4] = {row < a.nrows, row + 1 < a.nrows, row + 2 < a.nrows, row + 3 < a.nrows};
-            double acc[1] = {quad_dot(dd, o, valid)};
-            block_reduce<1, KR32_T / 64>(acc, red);
-            if (t == 0) a.partials[q] = acc[0];
-        }
+        quad_finish<NQ>(s, a.y, a.dvec, a.partials, q, row, a.nrows, red);
     }
 }
 
@@ -147,10 +138,19 @@ __global__ void lower_dia_kernel(float* dst, int64_t dstride, const double* src,
     if (mine) atomicAdd(refused, mine);
 }
 
+// the operator must hold CSR-DIA streams (csr_create.hip: build_dia, at creation only); the pattern form's rule for the offsets
+const char* lower_dia_refusal(kryst_csr_t a) {
+    if (!(a->d_dia && a->dia_nd > 0 && a->dia_nd <= KR_DIA_MAX)) return "the operator has no CSR-DIA form";
+    return offsets_fit32(a) ? nullptr : "the vectors do not fit 32-bit byte offsets";
+}
+
 hipError_t enqueue_lower_dia(kryst_csr_t a, kryst_csr32_t m, unsigned long long* d_refused) {
+    m->dia_stride = vec32_len(a->nrows); m->dia_nd = a->dia_nd; m->dia_min = a->dia_min; m->dia_max = a->dia_max;
+    for (int d = 0; d < KR_DIA_MAX; ++d) m->dia_off[d] = a->dia_off[d];
     const int64_t count = m->dia_stride * m->dia_nd;
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((count + 255) / 256, 4096));
-    hipLaunchKernelGGL(lower_dia_kernel, dim3(grid), dim3(256), 0, a->ctx->s_main, m->d_dia, m->dia_stride, a->d_dia, a->dia_stride, m->dia_nd, a->nrows, d_refused);
+    const hipError_t e = hipMalloc(&m->d_dia, sizeof(float) * (size_t)count);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(lower_dia_kernel, dim3(grid_for(count)), dim3(256), 0, a->ctx->s_main, m->d_dia, m->dia_stride, a->d_dia, a->dia_stride, m->dia_nd, a->nrows, d_refused);
     return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 // Mixed precision on the row-pattern encoding: the two SpMV kernels of a lowered operator that keeps a CSR-P16 form --
 // spmv32_pattern_kernel (any CSR-P16 operator) and spmv32_pattern_stage_kernel (boxes of lines: the near operands staged in LDS) -- and their
-// enqueue functions.  mixed.hip has the lowering, the choice (spmv32_kernel) and the solvers; spmv_pattern.hip has the fp64 twins.
+// enqueue functions, and the lowering of the form (when an operator can take it, its arrays and fields).  mixed_lower.hip has the skeleton of the
+// lowering, mixed_spmv.hip the choice (spmv32_kernel), mixed_cg.hip the solvers; spmv_pattern.hip has the fp64 twins.
 //
 // The contract of both: the fp32 tile of 1024 rows, thread t owns rows 4t .. 4t+3 (ids: one 8-byte load; y: one 16-byte store).  y_i = (float) of
 // the fold from 0.0, in stored order, of (double)tableval * (double)x[col] with separate multiply and add; an absent entry is skipped by a select,
@@ -118,16 +119,7 @@ __global__ __launch_bounds__(KR32_T) void spmv32_pattern_kernel(const Spmv32PatA
                 }
             }
         }
-        float o[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] = (float)s[r];
-        quad_store(a.y, row, a.nrows, o);
-        if constexpr (NQ > 0) {
-            const p_v4f dd = *reinterpret_cast<const p_v4f*>(a.dvec + row);             // (rows behind n lie in the padding: read, never used)
-            double acc[1] = {quad_dot(dd, o, valid)};
-            block_reduce<1, KR32_T / 64>(acc, red);
-            if (t == 0) a.partials[q] = acc[0];
-        }
+        quad_finish<NQ>(s, a.y, a.dvec, a.partials, q, row, a.nrows, red);
         ids = ids_n;
     }
 }
@@ -144,13 +136,7 @@ int32_t enqueue_spmv32_pattern(kryst_csr32_t a, const float* x, float* y, int nq
     g.red_off = (int32_t)((tab + 15) & ~(size_t)15);
     const size_t lds = (size_t)g.red_off + sizeof(double) * (KR32_T / 64);
     const dim3 grid((unsigned)((nt + g.tpw - 1) / g.tpw)), block(KR32_T);
-    if (nq) {
-        if (U == 7) hipLaunchKernelGGL((spmv32_pattern_kernel<1, 7>), grid, block, lds, ctx->s_main, g);
-        else hipLaunchKernelGGL((spmv32_pattern_kernel<1, 8>), grid, block, lds, ctx->s_main, g);
-    } else {
-        if (U == 7) hipLaunchKernelGGL((spmv32_pattern_kernel<0, 7>), grid, block, lds, ctx->s_main, g);
-        else hipLaunchKernelGGL((spmv32_pattern_kernel<0, 8>), grid, block, lds, ctx->s_main, g);
-    }
+    by_bool(nq != 0, [&](auto Q) { by_int<7, 8>(U, [&](auto U_) { hipLaunchKernelGGL((spmv32_pattern_kernel<Q() ? 1 : 0, U_()>), grid, block, lds, ctx->s_main, g); }); });
     KR_HIP(hipGetLastError());
     return KRYST_OK;
 }
@@ -298,15 +284,35 @@ int32_t enqueue_spmv32_pattern_stage(kryst_csr32_t a, const float* x, float* y, 
     g.red_off = (int32_t)((head + 15) & ~(size_t)15);
     const size_t lds = (size_t)g.red_off + sizeof(double) * T * (KR32_T / 64);
     const dim3 grid((unsigned)((nt + T - 1) / T)), block(KR32_T);
-    if (nq) {
-        if (T == 2) hipLaunchKernelGGL((spmv32_pattern_stage_kernel<1, 2>), grid, block, lds, ctx->s_main, g, n, a->pat_far_lo, a->pat_far_hi);
-        else hipLaunchKernelGGL((spmv32_pattern_stage_kernel<1, 1>), grid, block, lds, ctx->s_main, g, n, a->pat_far_lo, a->pat_far_hi);
-    } else {
-        if (T == 2) hipLaunchKernelGGL((spmv32_pattern_stage_kernel<0, 2>), grid, block, lds, ctx->s_main, g, n, a->pat_far_lo, a->pat_far_hi);
-        else hipLaunchKernelGGL((spmv32_pattern_stage_kernel<0, 1>), grid, block, lds, ctx->s_main, g, n, a->pat_far_lo, a->pat_far_hi);
-    }
+    auto launch = [&](auto Q, auto T_) { hipLaunchKernelGGL((spmv32_pattern_stage_kernel<Q() ? 1 : 0, T_()>), grid, block, lds, ctx->s_main, g, n, a->pat_far_lo, a->pat_far_hi); };
+    by_bool(nq != 0, [&](auto Q) { by_int<1, 2>(T, [&](auto T_) { launch(Q, T_); }); });
     KR_HIP(hipGetLastError());
     return KRYST_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- the lowering of the form
+// the operator must have a CSR-P16 form, and the kernels address x and y with 32-bit byte offsets
+const char* lower_pattern_refusal(kryst_csr_t a) {
+    if (!(a->d_pid && a->d_pmeta && a->d_poff && a->d_pval && a->npat > 0)) return "the operator has no CSR-P16 form";
+    return offsets_fit32(a) ? nullptr : "the vectors do not fit 32-bit byte offsets";
+}
+
+// ids re-padded to the fp32 tile (the fp64 array is padded to a 512-row tile only); the tables as they are, the values rounded as the CSR values are
+hipError_t enqueue_lower_pattern(kryst_csr_t a, kryst_csr32_t m) {
+    hipStream_t s = a->ctx->s_main;
+    const size_t nid = (size_t)ntiles32_of(a->nrows) * KR32_TILE + KR32_TILE;
+    hipError_t e = hipMalloc(&m->d_pid, sizeof(uint16_t) * nid);
+    if (e == hipSuccess) e = hipMalloc(&m->d_pmeta, sizeof(uint32_t) * 2 * (size_t)a->npat);
+    if (e == hipSuccess) e = hipMalloc(&m->d_poff, sizeof(int32_t) * (size_t)std::max(a->ntab, 1));
+    if (e == hipSuccess) e = hipMalloc(&m->d_pval, sizeof(float) * (size_t)std::max(a->ntab, 1));
+    if (e == hipSuccess) e = hipMemsetAsync(m->d_pid, 0, sizeof(uint16_t) * nid, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->d_pid, a->d_pid, sizeof(uint16_t) * (size_t)a->nrows, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->d_pmeta, a->d_pmeta, sizeof(uint32_t) * 2 * (size_t)a->npat, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && a->ntab > 0) e = hipMemcpyAsync(m->d_poff, a->d_poff, sizeof(int32_t) * (size_t)a->ntab, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && a->ntab > 0) e = enqueue_round32(a->ctx, m->d_pval, a->d_pval, (int64_t)a->ntab, 0, 1.0);
+    m->npat = a->npat; m->ntab = a->ntab; m->pat_unroll = a->pat_unroll; m->pat_single = a->pat_single;
+    m->pat_stage_n = a->pat_stage_n; m->pat_far_lo = a->pat_far_lo; m->pat_far_hi = a->pat_far_hi; m->pat_far_uniform = a->pat_far_uniform;
+    return e;
 }
 
 }  // namespace kr

@@ -391,19 +391,24 @@ struct LiveMonitor {
     void poll() { if (io && io->monitor) upto(ws->ctx->h_prog->hist_len); }
 };
 
+// the end of a solve that needs no operator (mixed_cg.hip ends here too): the state into *h, stats and history out whatever the status, the preconditioner's verdict
+inline int32_t finish_state(Workspace& ws, kryst_pc_t pc, kryst_stats_t* stats, double* hist, int64_t hist_cap, int64_t* hist_len, DevState* h) {
+    KR_HIP(read_state(ws, h));
+    if (stats) { stats->iterations = h->iterations; stats->final_residual = h->final_residual; stats->converged = h->converged; }
+    if (hist_len) *hist_len = h->hist_len;
+    for (int64_t k = 0; k < h->hist_len && k < ws.hist_cap; ++k) {
+        if (hist && k < hist_cap) hist[k] = ws.h_hist[k];
+    }
+    // a preconditioner apply abandoned by the device (pc.h: pc_health) voids the whole solve, whatever the recurrences made of it
+    if (pc && pc_health(pc) != KRYST_OK) return KRYST_SOLVE_ERROR;
+    return KRYST_OK;
+}
+
 // copy stats / history out and run the monitor callbacks (in order, on the calling thread)
 inline int32_t finish_solve(Workspace& ws, const SolveIO& io) {
     kryst_ctx_t ctx = ws.ctx;
     DevState h;
-    KR_HIP(read_state(ws, &h));
-    if (io.stats) { io.stats->iterations = h.iterations; io.stats->final_residual = h.final_residual; io.stats->converged = h.converged; }
-    const int64_t len = h.hist_len;
-    if (io.hist_len) *io.hist_len = len;
-    for (int64_t k = 0; k < len && k < ws.hist_cap; ++k) {
-        if (io.hist && k < io.hist_cap) io.hist[k] = ws.h_hist[k];
-    }
-    // a preconditioner apply abandoned by the device (pc.h: pc_health) voids the whole solve, whatever the recurrences made of it
-    if (io.pc && pc_health(io.pc) != KRYST_OK) return KRYST_SOLVE_ERROR;
+    KR_TRY(finish_state(ws, io.pc, io.stats, io.hist, io.hist_cap, io.hist_len, &h));
     // a fold's polling hand-off (status raised by the device) or a halo pull (NaNs in the halo, no status) that ran out of patience
     if ((h.status == KRYST_ERR_HIP || (ctx->nranks > 1 && io.a->plan.peer.on)) && fold_gave_up(ctx)) return h.status != KRYST_OK ? h.status : KRYST_ERR_RCCL;
     return h.status;
