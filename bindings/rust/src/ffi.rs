@@ -268,6 +268,7 @@ extern "C" {
     pub fn kryst_mvec_get_column(mv: MVec, j: i32, v: Vecd) -> i32;
     pub fn kryst_bench_mvec_padding(mv: MVec, fill: *const f64, dirty: *mut i64) -> i32;
     pub fn kryst_spmm(a: Csr, x: MVec, y: MVec) -> i32;
+    pub fn kryst_spmm_kernel(a: Csr, k: i32, kernel: *mut i32) -> i32;
     pub fn kryst_cg_solve_multi_dev(b: MVec, x: MVec, a: Csr, pc: Pc, params: *const Params, stats: *mut Stats, status: *mut i32,
                                     hist: *mut f64, hist_cap: i64, hist_len: *mut i64) -> i32;
     pub fn kryst_pcg_solve_multi_dev(b: MVec, x: MVec, a: Csr, pc: Pc, params: *const Params, stats: *mut Stats, status: *mut i32,

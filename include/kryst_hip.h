@@ -676,9 +676,15 @@ int32_t kryst_mvec_get_column(kryst_mvec_t mv, int32_t j, kryst_vec_t v);
  * are not +0.0, before any fill; fill != NULL then sets every one of them -- (ceil(n / 512) * 512 + 512 - n) * k elements -- to *fill */
 int32_t kryst_bench_mvec_padding(kryst_mvec_t mv, const double* fill, int64_t* dirty);
 /* SparseMatrix::spmv (sparse.rs:56-67) on k columns: Y <- A X, Y overwritten; column j is kryst_spmv on column j, whatever storage form
- * kryst_spmv streams for the operator (this kernel reads the plain CSR arrays).  REFUSED like kryst_spmv: X and Y the same multivector
+ * kryst_spmv streams for the operator.  The kernel reads the operator's CSR-DIA value streams where kryst_spmm_kernel says so, else the plain
+ * CSR arrays; the bits are the same.  REFUSED like kryst_spmv: X and Y the same multivector
  * (KRYST_ERR_ARG before any launch, Y unchanged); a row count or k that does not match: KRYST_ERR_ARG; distributed operators: KRYST_UNSUPPORTED. */
 int32_t kryst_spmm(kryst_csr_t a, kryst_mvec_t x, kryst_mvec_t y);
+/* which kernel kryst_spmm and the batched solvers take for this operator and k columns under the current KRYST_SPMM_FORM setting (auto | plain |
+ * dia, read at every launch): *kernel = 0 the plain-CSR rows kernel, 1 the diagonal (CSR-DIA) kernel.  `dia` takes the diagonal kernel wherever
+ * the operator holds the streams and falls back to the plain one silently elsewhere; `auto` (the default) takes it where kryst_spmv itself
+ * streams CSR-DIA, for the widths at which it measured no slower.  k outside {2, 4, 8}: KRYST_ERR_ARG. */
+int32_t kryst_spmm_kernel(kryst_csr_t a, int32_t k, int32_t* kernel);
 /* CgSolver::solve (cg.rs:114-288) / PcgSolver::solve (pcg.rs:114-222) on every column of B with the initial guesses in X: one SpMM per
  * iteration, every column's scalars on the device in a state of its own; a column that has ended -- converged, the cap (converged = true
  * at max_iters like the reference), IndefiniteMatrix, IndefinitePreconditioner, max_iters <= 0 -- is frozen while the others go on.

@@ -143,6 +143,12 @@ public:
     }
     void matvec(const Vec& x, Vec& y) const override { spmv(x, y); }
     void spmm(const MultiVec& x, MultiVec& y) const { check(kryst_spmm(h_, x.handle(), y.handle())); }      // column j = spmv on column j
+    // the kernel spmm and solve_many take for k columns under the current KRYST_SPMM_FORM: "plain" or "dia" (kryst_spmm_kernel)
+    std::string spmm_kernel(int k) const {
+        int32_t kernel = 0;
+        check(kryst_spmm_kernel(h_, (int32_t)k, &kernel));
+        return kernel == 1 ? "dia" : "plain";
+    }
     // MatTransVec::mattransvec: y <- A^T x through kryst_spmv_transpose (A^T built on the first call, cached on the operator)
     void mattransvec(const Vec& x, Vec& y) const {
         if (x.size() != nrows_ || y.size() != ncols_) throw KError(KRYST_ERR_ARG);

@@ -605,6 +605,15 @@ class CsrMatrix:
             at += w
         return out
 
+    SPMM_KERNELS = ("plain", "dia")
+
+    def spmm_kernel(self, k):
+        """The kernel spmm and solve_many take for k columns (2, 4 or 8) under the current KRYST_SPMM_FORM (auto | plain | dia): "plain"
+        (the CSR arrays) or "dia" (the CSR-DIA value streams)."""
+        kernel = C.c_int32()
+        check(lib().kryst_spmm_kernel(self.h, int(k), C.byref(kernel)))
+        return self.SPMM_KERNELS[kernel.value]
+
     def lower(self, form="plain"):
         """This operator with fp32-stored values (CsrMatrix32; an extension): a copy, with no tie to this one's lifetime.  form: "plain"
         (the CSR arrays), "pattern" (also the CSR-P16 row-pattern form; refused where the operator has none), "auto", or "dia" (also

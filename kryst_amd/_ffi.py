@@ -206,6 +206,7 @@ SIGNATURES = {
     "kryst_mvec_get_column": (C.c_int32, [Handle, C.c_int32, Handle]),
     "kryst_bench_mvec_padding": (C.c_int32, [Handle, c_dp, c_i64p]),
     "kryst_spmm": (C.c_int32, [Handle, Handle, Handle]),
+    "kryst_spmm_kernel": (C.c_int32, [Handle, C.c_int32, c_i32p]),
     "kryst_cg_solve_multi_dev": (C.c_int32, [Handle, Handle] + _MULTI_TAIL),
     "kryst_pcg_solve_multi_dev": (C.c_int32, [Handle, Handle] + _MULTI_TAIL),
     "kryst_cg_solve_multi": (C.c_int32, [c_dp, c_dp, C.c_int64, C.c_int32, C.c_int64] + _MULTI_TAIL),

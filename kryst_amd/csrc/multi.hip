@@ -1,4 +1,5 @@
-// Several right-hand sides at once: kryst_mvec_t, Y <- A X on plain CSR (spmm_rows_kernel) and batched CG / Jacobi-PCG.
+// Several right-hand sides at once: kryst_mvec_t, Y <- A X (spmm_rows_kernel on plain CSR here, spmm_dia_kernel on the diagonal streams in
+// multi_dia.hip; launch_spmm decides) and batched CG / Jacobi-PCG.
 //
 // The contract is one sentence: column j of a batched call is, bit for bit, what the single-vector call returns for column j -- y, x,
 // the iteration count, every residual-history entry, final_residual, converged and the status.  It holds because nothing here re-associates:
@@ -8,6 +9,7 @@
 // What changes is where bytes move: the matrix is read once for K columns.
 #include "multi.h"
 #include "cg_logic.h"
+#include "spmv.h"
 
 namespace kr {
 
@@ -218,7 +220,25 @@ static int32_t launch_spmm_k(kryst_ctx_t ctx, const SpmmArgs& args, int nq) {
     return KRYST_OK;
 }
 
+// KRYST_SPMM_FORM = auto | plain | dia: 0 auto (also unset, or no such word), 1 plain, 2 dia; read as env_int reads a number (once per EnvFreeze)
+static int spmm_form_knob() {
+    static EnvSlot slot;
+    return (int)env_parsed_cached(slot, "KRYST_SPMM_FORM", 0, [](const char* v) -> long long { return !strcmp(v, "plain") ? 1 : !strcmp(v, "dia") ? 2 : 0; });
+}
+// The choice: which SpMM kernel a launch takes is decided HERE; launch_spmm and kryst_spmm_kernel both ask.  `dia`: spmm_dia_kernel wherever the
+// operator holds the streams, else (silently) the plain kernel.  `auto`: spmm_dia_kernel where the operator's own SpMV streams CSR-DIA, for the
+// widths at which it measured no slower than spmm_rows_kernel on the same operator at 256^3 and 512^3.
+constexpr bool SPMM_DIA_AUTO[3] = {true, true, true};                   // K = 2, 4, 8
+bool spmm_takes_dia(kryst_csr_t a, int k) {
+    const int form = spmm_form_knob();
+    if (form == 1 || !mvec_width_ok(k)) return false;
+    if (!a->d_dia || a->dist || a->dia_nd <= 0 || a->dia_nd > KR_DIA_MAX) return false;
+    if (form == 2) return true;
+    return SPMM_DIA_AUTO[k == 2 ? 0 : k == 4 ? 1 : 2] && tile_kernel(a, false, TileRange::Whole) == TileKernel::Dia;
+}
+
 int32_t launch_spmm(kryst_csr_t a, int k, const double* x, double* y, int nq, const double* dvec, double* partials, int64_t pstride, const int* done) {
+    if (spmm_takes_dia(a, k)) return launch_spmm_dia(a, k, x, y, nq, dvec, partials, pstride, done);
     KR_ARG(a->d_row_ptr && a->d_col && a->d_val, "spmm: the operator keeps no CSR arrays");
     KR_ARG(a->nrows < (1ll << 31) - KR_TILE, "spmm: too many rows");
     SpmmArgs args{a->d_row_ptr, a->d_col, a->d_val, x, y, dvec, partials, pstride, (int)a->nrows, (int)ntiles_of(a->nrows), done};
@@ -684,6 +704,13 @@ int32_t kryst_spmm(kryst_csr_t a, kryst_mvec_t x, kryst_mvec_t y) {
     if (a->dist || a->ctx->nranks > 1) { set_error("spmm: distributed operators are not supported"); return KRYST_UNSUPPORTED; }
     KR_HIP(hipSetDevice(a->ctx->device));
     return launch_spmm(a, x->k, x->d, y->d, 0, nullptr, nullptr, 0, nullptr);
+}
+
+int32_t kryst_spmm_kernel(kryst_csr_t a, int32_t k, int32_t* kernel) {
+    KR_ARG(a && kernel, "spmm_kernel");
+    KR_ARG(mvec_width_ok(k), "spmm_kernel: k must be 2, 4 or 8");
+    *kernel = spmm_takes_dia(a, k) ? 1 : 0;
+    return KRYST_OK;
 }
 
 #define KRYST_MULTI_TAIL kryst_csr_t a, kryst_pc_t pc, const kryst_params_t* params, kryst_stats_t* stats, int32_t* status, \
