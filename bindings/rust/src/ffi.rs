@@ -279,6 +279,16 @@ extern "C" {
                                  stats: *mut Stats, status: *mut i32, hist: *mut f64, hist_cap: i64, hist_len: *mut i64) -> i32;
 }
 
+// block CG: one Krylov space for the k columns of a multivector (declared, not wrapped: an extension like the batched solvers above)
+extern "C" {
+    pub fn kryst_bcg_solve_multi_dev(b: MVec, x: MVec, a: Csr, pc: Pc, params: *const Params, stats: *mut Stats, status: *mut i32,
+                                     hist: *mut f64, hist_cap: i64, hist_len: *mut i64) -> i32;
+    pub fn kryst_bcg_solve_multi(b: *const f64, x: *mut f64, n: i64, k: i32, ld: i64, a: Csr, pc: Pc, params: *const Params,
+                                 stats: *mut Stats, status: *mut i32, hist: *mut f64, hist_cap: i64, hist_len: *mut i64) -> i32;
+    pub fn kryst_host_bcg_step(step: i32, k: i32, g: *const f64, c: *mut f64, out1: *mut f64, out2: *mut f64, res: *mut f64) -> i32;
+    pub fn kryst_bench_mvec_gram(u: MVec, v: MVec, inv_diag: Vecd, out_kk: *mut f64) -> i32;
+}
+
 // mixed precision: fp32 as a storage format (fp64 arithmetic and scalars), CG / Jacobi-PCG on it and fp64 iterative refinement around them
 pub type Vec32 = *mut c_void;
 pub type Csr32 = *mut c_void;

@@ -705,6 +705,40 @@ int32_t kryst_pcg_solve_multi(const double* b, double* x, int64_t n, int32_t k, 
                               const kryst_params_t* params, kryst_stats_t* stats, int32_t* status, double* hist, int64_t hist_cap,
                               int64_t* hist_len);
 
+/* ---- block CG: ONE Krylov space for the k columns (a labelled extension beside the batched solvers above, whose behaviour it does not change) ----
+ * Dubrulle's retooled block CG (BCGrQ) with the thin QR done as a Cholesky-QR of a k x k Gram matrix; Jacobi enters through the symmetrically
+ * preconditioned form.  Every column is minimised over the union of all k Krylov spaces, so k right-hand sides can take fewer iterations than
+ * k solves; the columns are NOT independent any more (there is no per-column rule here: the reference is the restatement of the operation
+ * order in kryst_amd/csrc/bcg_logic.h, which the tests pin bit for bit).  fp64, one rank, k in {2, 4, 8}.
+ * Argument lists, NULL rules and the history layout are those of kryst_pcg_solve_multi*: pc may be NULL, Identity or Jacobi; other kinds,
+ * norm_type outside {0, 1}, has_radius, has_obj_target and distributed operators are KRYST_UNSUPPORTED, k outside {2, 4, 8} or mismatched shapes
+ * KRYST_ERR_ARG, and nothing is written then.  B and X may be the same multivector.
+ * The history entry of column j is res_j = the 2-norm of column j of the k x k residual factor: in exact arithmetic ||r_j||_2 with no
+ * preconditioner and ||r_j|| in the M^-1 norm, sqrt(r_j^T D^-1 r_j), with Jacobi (whatever norm_type says).  Per column converged =
+ * res_j / res0_j <= tol || it >= max_iters; the solve stops when every column has res_j <= tol * res0_j or at max_iters; all columns report the
+ * same `iterations`; final_residual is res_j; max_iters <= 0 ends after the initial residual as the batched solvers do.
+ * Breakdowns end the whole block with ONE code for every column, iterations = the iteration it happened in (0: at the start), the history kept
+ * up to there and X untouched (X is written only when the solve ends with KRYST_OK): KRYST_INDEFINITE_MATRIX (the Gram matrix of the directions
+ * against their images is not positive definite, or holds a NaN), KRYST_INDEFINITE_PRECONDITIONER (a weighted residual Gram matrix with a negative
+ * diagonal entry), KRYST_SOLVE_ERROR (rank loss: a pivot s of a k x k Cholesky factor with !(s > KRYST_BCG_RANK_TOL * G[j][j]),
+ * KRYST_BCG_RANK_TOL = 2^-26 -- dependent or zero right-hand sides, n < k, a column that converged exactly).  There is no deflation: for
+ * right-hand sides that may be dependent use kryst_cg_solve_multi* / kryst_pcg_solve_multi* (solve_many). */
+#define KRYST_BCG_RANK_TOL 0x1p-26   /* 2^-26: the smallest s / G[j][j] a pivot of block CG's k x k Cholesky factors may have (kryst_amd/csrc/bcg_logic.h) */
+int32_t kryst_bcg_solve_multi_dev(kryst_mvec_t b, kryst_mvec_t x, kryst_csr_t a, kryst_pc_t pc, const kryst_params_t* params,
+                                  kryst_stats_t* stats, int32_t* status, double* hist, int64_t hist_cap, int64_t* hist_len);
+int32_t kryst_bcg_solve_multi(const double* b, double* x, int64_t n, int32_t k, int64_t ld, kryst_csr_t a, kryst_pc_t pc,
+                              const kryst_params_t* params, kryst_stats_t* stats, int32_t* status, double* hist, int64_t hist_cap,
+                              int64_t* hist_len);
+/* One k x k scalar step of block CG on the HOST, no GPU involved: the code the device runs between two passes (bcg_logic.h), for tests.
+ * Matrices are k x k, row major.  g: the Gram matrix (its upper triangle is read).  step 0 (start): c <- chol(g), out1 <- c^-1, res <- res0.
+ * step 1: out1 <- Gamma = U^-1 U^-T with U = chol(g), out2 <- Gamma c.  step 2: out1 <- Phi = chol(g), out2 <- Phi^-1, c <- Phi c, res.
+ * Returns KRYST_OK or the breakdown code of the pivot rule above; KRYST_ERR_ARG for a null pointer, another step or k outside {2, 4, 8}. */
+int32_t kryst_host_bcg_step(int32_t step, int32_t k, const double* g, double* c, double* out1, double* out2, double* res);
+/* test hook: out_kk (host, k x k row major, the lower triangle the mirror of the upper) <- the Gram matrix of U against V as block CG reduces
+ * it: entry (a, b), a <= b, is the inner product of DESIGN.md section 4.2 over U(i, a) * V(i, b), or U(i, a) * (d_i * V(i, b)) with weights
+ * inv_diag (may be NULL).  U and V may be the same multivector. */
+int32_t kryst_bench_mvec_gram(kryst_mvec_t u, kryst_mvec_t v, kryst_vec_t inv_diag, double* out_kk);
+
 /* ---- mixed precision: fp32 as a STORAGE format, and fp64 iterative refinement on top of it ----
  * A LABELLED DEVIATION from the reference at T = f32 (CsrMatrix<f32>, CgSolver<f32>, `T: Float`), which would round every operation: here
  * fp32 is how vector elements and matrix values are STORED.  Every kernel widens what it loads, computes in fp64 in the fixed order of its

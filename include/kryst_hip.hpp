@@ -519,6 +519,23 @@ protected:
         return kryst_pcg_solve_multi_dev(b, x, a, pc, params, stats, status, hist, hist_cap, hist_len);
     }
 };
+// Block CG (an extension: kryst_bcg_solve_multi_dev): one Krylov space for the columns of a multivector.  solve_block returns the block's code per
+// column (one code for all of them) and fills stats and residual_histories like solve_many; X is written only when the code is KRYST_OK.  A single
+// right-hand side has no block form: solve() throws KRYST_UNSUPPORTED.  For right-hand sides that may be dependent use CgSolver / PcgSolver::solve_many.
+struct BlockCgSolver : SolverBase {
+    BlockCgSolver(double tol, size_t max_iters) : SolverBase(tol, max_iters) {}
+    std::vector<int32_t> solve_block(const HipCsrMatrix& a, const Preconditioner<HipCsrMatrix, Vec>* pc, const MultiVec& b, MultiVec& x,
+                                     std::vector<SolveStats<double>>& stats) { return solve_many(a, pc, b, x, stats); }
+protected:
+    int32_t call(const double*, double*, int64_t, KRYST_SOLVE_ARGS) override {
+        (void)a; (void)pc; (void)params; (void)stats; (void)hist; (void)hist_cap; (void)hist_len; (void)monitor; (void)user;
+        return KRYST_UNSUPPORTED;
+    }
+    int32_t call_many(kryst_mvec_t b, kryst_mvec_t x, kryst_csr_t a, kryst_pc_t pc, const kryst_params_t* params, kryst_stats_t* stats, int32_t* status,
+                      double* hist, int64_t hist_cap, int64_t* hist_len) override {
+        return kryst_bcg_solve_multi_dev(b, x, a, pc, params, stats, status, hist, hist_cap, hist_len);
+    }
+};
 struct GmresSolver : SolverBase {                            // gmres.rs:38-60
     size_t restart; Preconditioning preconditioning = Preconditioning::Left;
     GmresSolver(size_t restart, double tol, size_t max_iters) : SolverBase(tol, max_iters), restart(restart) { restart_ = (int)restart; }

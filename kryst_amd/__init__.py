@@ -31,7 +31,7 @@ __all__ = ["Context", "DeviceVec", "CsrMatrix", "dot", "norm", "Jacobi", "Ilu0",
            "Preconditioning", "CgSolver", "PcgSolver", "GmresSolver", "FgmresSolver", "PcaGmresSolver", "CbGmresSolver", "Orthog", "CgsSolver", "TfqmrSolver", "MinresSolver", "QmrSolver", "CgnrSolver", "CgneSolver", "BiCgStabSolver", "BiCgStabRightPcSolver", "Session", "KspContext", "SolverKind", "PC", "KError", "reduce_spec",
            "host_stencil7", "partition_rows", "halo_recv_plan", "read_matrix_market", "read_petsc_binary", "host_ilup", "host_ilut", "host_amg", "host_levels", "color_graph", "build_blocks_from_colors",
            "DenseMatrix", "LuSolver", "QrSolver", "host_dense_lu", "host_dense_lu_solve", "host_dense_qr_solve",
-           "MultiVec", "split_widths",
+           "MultiVec", "split_widths", "BlockCgSolver", "mvec_gram", "host_bcg_step",
            "DeviceVec32", "CsrMatrix32", "dot32", "Cg32Solver", "Pcg32Solver", "RefinementSolver", "reduce_spec32", "host_round_f32"]
 
 
@@ -1547,32 +1547,38 @@ class _Solver:
         that ended in an error, the KError (carrying .stats) in its place; self.residual_histories holds one history per column."""
         if self._MULTI_DEV is None:
             raise KError(6, "solve_many: CG and PCG only")
+        return self._solve_columns(a, pc, B, X, "solve_many", lambda _pc: self)
+
+    def _solve_columns(self, a, pc, B, X, what, single):
+        """the body of solve_many and BlockCgSolver.solve_block: groups of 8, 4 and 2 columns through _solve_group, a leftover column through
+        single(pc).solve; a column of X is written where its code is 0 (block CG reports one code for a whole group)"""
         pch = pc.h if pc is not None else None
         if pc is not None and pch is None:
             raise KError(2, "preconditioner used before setup")
         if isinstance(B, MultiVec) or isinstance(X, MultiVec):
             if not (isinstance(B, MultiVec) and isinstance(X, MultiVec)):
-                raise KError(102, "solve_many: B and X must both be MultiVec or both be arrays")
+                raise KError(102, f"{what}: B and X must both be MultiVec or both be arrays")
             res = self._solve_group(a, pch, B, X)
         else:
             ba = np.asarray(B, dtype=np.float64)
             if ba.ndim != 2 or not isinstance(X, np.ndarray) or X.dtype != np.float64 or X.shape != ba.shape:
-                raise KError(102, "solve_many: B and X must be float64 arrays of the same shape (n, m)")
+                raise KError(102, f"{what}: B and X must be float64 arrays of the same shape (n, m)")
             res, at = [], 0
             for w in split_widths(ba.shape[1]):
                 if w == 1:
-                    saved, self.residual_history = self.residual_history, []
+                    one = single(pc)
+                    saved, one.residual_history = one.residual_history, []
                     xj = np.ascontiguousarray(X[:, at])
                     try:
-                        stats = self.solve(a, pc, np.ascontiguousarray(ba[:, at]), xj)
-                        res.append((0, stats, self.residual_history))
+                        stats = one.solve(a, pc, np.ascontiguousarray(ba[:, at]), xj)
+                        res.append((0, stats, one.residual_history))
                         X[:, at] = xj
                     except KError as e:
                         if e.stats is None:
                             raise
-                        res.append((e.code, e.stats, self.residual_history))
+                        res.append((e.code, e.stats, one.residual_history))
                     finally:
-                        self.residual_history = saved
+                        one.residual_history = saved
                 else:
                     bm = MultiVec.from_numpy(ba[:, at:at + w], ctx=a.ctx)
                     xm = MultiVec.from_numpy(X[:, at:at + w], ctx=a.ctx)
@@ -1624,6 +1630,54 @@ class PcgSolver(_Solver):
     """PcgSolver::new(tol, max_iters)  src/solver/pcg.rs:31-91,114-222."""
     _HOST, _DEV = "kryst_pcg_solve", "kryst_pcg_solve_dev"
     _MULTI_DEV = "kryst_pcg_solve_multi_dev"
+
+
+class BlockCgSolver(_Solver):
+    """Block CG (kryst_bcg_solve_multi_dev; an extension beside solve_many): ONE Krylov space for the columns of a block, so that K right-hand
+    sides can take fewer iterations than K solves.  Dubrulle's retooled block CG with a Cholesky-QR of a K x K Gram matrix; pc may be None,
+    IdentityPc or Jacobi.  The columns of a block are not independent: a breakdown (dependent or zero right-hand sides, an indefinite matrix or
+    preconditioner) ends the whole block with one code and leaves its X untouched -- for right-hand sides that may be dependent use solve_many."""
+    _MULTI_DEV = "kryst_bcg_solve_multi_dev"
+
+    def solve(self, a, pc, b, x):
+        raise KError(6, "BlockCgSolver: solve_block only (a single right-hand side goes through CgSolver / PcgSolver)")
+
+    def solve_many(self, a, pc, B, X):
+        raise KError(6, "BlockCgSolver: solve_block only")
+
+    def solve_block(self, a, pc, B, X):
+        """B, X: MultiVec (2, 4 or 8 columns: one block, X in/out on the device) or float64 arrays of shape (n, m) with any m -- the columns are cut
+        by split_widths, each group of 8, 4 or 2 is one block, a leftover single column goes through CgSolver (pc None) or PcgSolver; X is
+        written in place where the block's solve succeeded.  Returns what solve_many returns: per column a SolveStats or, after an error, the
+        KError (carrying .stats) in its place; self.residual_histories holds one history per column."""
+        def single(pc_):
+            one = (CgSolver if pc_ is None else PcgSolver)(self.conv.tol, self.conv.max_iters)
+            one.check_every = self.check_every
+            return one
+        return self._solve_columns(a, pc, B, X, "solve_block", single)
+
+
+def mvec_gram(u, v, inv_diag=None):
+    """Test hook (kryst_bench_mvec_gram): the K x K Gram matrix of the multivectors u against v as block CG reduces it -- entry (a, b), a <= b, is
+    the library's inner product over u(i, a) * v(i, b), or u(i, a) * (d_i * v(i, b)) with weights inv_diag (a DeviceVec); the lower triangle
+    mirrors the upper."""
+    out = np.zeros((u.k, u.k))
+    check(lib().kryst_bench_mvec_gram(u.h, v.h, inv_diag.h if inv_diag is not None else None, _dp(out)))
+    return out
+
+
+def host_bcg_step(step, g, c=None):
+    """kryst_host_bcg_step: one K x K scalar step of block CG on the host (no GPU).  step 0 (start), 1 (after the Gram matrix of S against T) or
+    2 (after the Gram matrix of the new Q); g the Gram matrix, c the residual factor C (steps 1 and 2).  Returns (code, c, out1, out2, res) as the
+    header describes them; after a breakdown code != 0 and the matrices hold whatever the step had written."""
+    g = np.ascontiguousarray(g, dtype=np.float64)
+    k = g.shape[0]
+    cc = np.zeros((k, k)) if c is None else np.array(c, dtype=np.float64, order="C")
+    o1, o2, res = np.zeros((k, k)), np.zeros((k, k)), np.zeros(k)
+    code = lib().kryst_host_bcg_step(int(step), k, _dp(g), _dp(cc), _dp(o1), _dp(o2), _dp(res))
+    if code == 102:
+        check(code)
+    return code, cc, o1, o2, res
 
 
 class _Solver32(_Solver):

@@ -211,6 +211,10 @@ SIGNATURES = {
     "kryst_pcg_solve_multi_dev": (C.c_int32, [Handle, Handle] + _MULTI_TAIL),
     "kryst_cg_solve_multi": (C.c_int32, [c_dp, c_dp, C.c_int64, C.c_int32, C.c_int64] + _MULTI_TAIL),
     "kryst_pcg_solve_multi": (C.c_int32, [c_dp, c_dp, C.c_int64, C.c_int32, C.c_int64] + _MULTI_TAIL),
+    "kryst_bcg_solve_multi_dev": (C.c_int32, [Handle, Handle] + _MULTI_TAIL),
+    "kryst_bcg_solve_multi": (C.c_int32, [c_dp, c_dp, C.c_int64, C.c_int32, C.c_int64] + _MULTI_TAIL),
+    "kryst_host_bcg_step": (C.c_int32, [C.c_int32, C.c_int32, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "kryst_bench_mvec_gram": (C.c_int32, [Handle, Handle, Handle, c_dp]),
     "kryst_reduce_spec32": (None, [c_i32p, c_i32p, c_i32p]),
     "kryst_vec32_create": (C.c_int32, [Handle, C.c_int64, C.POINTER(Handle)]),
     "kryst_vec32_destroy": (C.c_int32, [Handle]),

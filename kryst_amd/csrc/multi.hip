@@ -44,7 +44,7 @@ __global__ void mvec_padding_kernel(double* d, int64_t n, int64_t rows, int k, i
 
 inline unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 2048)); }
 
-static int32_t mvec_check(kryst_mvec_t mv) {
+int32_t mvec_check(kryst_mvec_t mv) {
     KR_ARG(mv && mv->d && mv->ctx, "multivector: null handle");
     return KRYST_OK;
 }
@@ -95,7 +95,7 @@ struct SpmmArgs {
 template <int K, int NQ>
 __global__ __launch_bounds__(KR_T) void spmm_rows_kernel(const SpmmArgs a) {
     static_assert(K == 2 || K == 4 || K == 8, "K");
-    static_assert(NQ == 0 || NQ == 1, "NQ");
+    static_assert(NQ == 0 || NQ == 1 || NQ == 2, "NQ");
     if (a.done && *a.done) return;
     constexpr int SLOTS = 4;
     constexpr int WCAP = SLOTS * 128;                       // entries per wave window
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(KR_T) void spmm_rows_kernel(const SpmmArgs a) {
     constexpr int H = K / 2;
     __shared__ __attribute__((aligned(16))) double val_all[4 * WCAP];
     __shared__ __attribute__((aligned(16))) int32_t col_all[4 * WCAP];
-    __shared__ double red[(NQ > 0 ? NQ * K : 1) * (KR_T / 64)];
+    __shared__ double red[(NQ == 2 ? BcgShape<K>::RG : NQ == 1 ? K : 1) * (KR_T / 64)];
     const int t = threadIdx.x, l = t & 63;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
     double* lval = val_all + w * WCAP;
@@ -187,7 +187,8 @@ __global__ __launch_bounds__(KR_T) void spmm_rows_kernel(const SpmmArgs a) {
 #pragma unroll
             for (int h = 0; h < H; ++h) { kr_v2d o; o.x = s1[2 * h]; o.y = s1[2 * h + 1]; yp[H + h] = o; }
         }
-        if constexpr (NQ > 0) {
+        if constexpr (NQ == 2) spmm_gram_epilogue<K>(a.x, row, row < r1, row + 1 < r1, s0, s1, red, a.partials, a.pstride, q);
+        if constexpr (NQ == 1) {
             // (D_j, Y_j) per column: the lane's two products in index order, the 64-lane butterfly, the serial fold over the 4 waves
             const kr_v2d* dp = reinterpret_cast<const kr_v2d*>(a.dvec + (int64_t)row * K);     // (rows behind n lie in the padding: read, never used)
             double acc[K];
@@ -213,7 +214,8 @@ static int32_t launch_spmm_k(kryst_ctx_t ctx, const SpmmArgs& args, int nq) {
     const int bpc = std::max(1, env_int("KRYST_SPMM_BLOCKS_PER_CU", 4));
     const int64_t grid = std::min<int64_t>(args.ntiles, (int64_t)ctx->num_cu * bpc);
     if (grid <= 0) return KRYST_OK;
-    if (nq) hipLaunchKernelGGL((spmm_rows_kernel<K, 1>), dim3((unsigned)grid), dim3(KR_T), 0, ctx->s_main, args);
+    if (nq == 2) hipLaunchKernelGGL((spmm_rows_kernel<K, 2>), dim3((unsigned)grid), dim3(KR_T), 0, ctx->s_main, args);
+    else if (nq) hipLaunchKernelGGL((spmm_rows_kernel<K, 1>), dim3((unsigned)grid), dim3(KR_T), 0, ctx->s_main, args);
     else hipLaunchKernelGGL((spmm_rows_kernel<K, 0>), dim3((unsigned)grid), dim3(KR_T), 0, ctx->s_main, args);
     KR_HIP(hipGetLastError());
     phase_mark(ctx, KR_PH_SPMV);
@@ -238,6 +240,7 @@ bool spmm_takes_dia(kryst_csr_t a, int k) {
 }
 
 int32_t launch_spmm(kryst_csr_t a, int k, const double* x, double* y, int nq, const double* dvec, double* partials, int64_t pstride, const int* done) {
+    KR_ARG(nq != 2 || a->nrows == a->xlen, "spmm: the Gram epilogue needs a square operator");
     if (spmm_takes_dia(a, k)) return launch_spmm_dia(a, k, x, y, nq, dvec, partials, pstride, done);
     KR_ARG(a->d_row_ptr && a->d_col && a->d_val, "spmm: the operator keeps no CSR arrays");
     KR_ARG(a->nrows < (1ll << 31) - KR_TILE, "spmm: too many rows");
@@ -251,17 +254,7 @@ int32_t launch_spmm(kryst_csr_t a, int k, const double* x, double* y, int nq, co
 }
 
 // ---------------------------------------------------------------------------------------------------- pointwise passes over interleaved rows
-// A lane's two rows are 2 K contiguous doubles; element e of them belongs to column e % K and to the lane's row e / K.
-template <int K> __device__ __forceinline__ void ld_rows(const double* p, int64_t row, double (&v)[2 * K]) {
-    const kr_v2d* q = reinterpret_cast<const kr_v2d*>(p + row * K);
-#pragma unroll
-    for (int h = 0; h < K; ++h) { const kr_v2d t = q[h]; v[2 * h] = t.x; v[2 * h + 1] = t.y; }
-}
-template <int K> __device__ __forceinline__ void st_rows(double* p, int64_t row, const double (&v)[2 * K]) {
-    kr_v2d* q = reinterpret_cast<kr_v2d*>(p + row * K);
-#pragma unroll
-    for (int h = 0; h < K; ++h) { kr_v2d t; t.x = v[2 * h]; t.y = v[2 * h + 1]; q[h] = t; }
-}
+// (ld_rows / st_rows, a lane's two rows as 2 K contiguous doubles: multi.h)
 
 struct GateAllDone {
     const int* all_done;
@@ -466,13 +459,10 @@ __global__ __launch_bounds__(KR_F) void fold_multi_kernel(const double* partials
 }
 
 // ---------------------------------------------------------------------------------------------------- batched CG / PCG
-struct MultiIO {
-    kryst_mvec_t b, x; kryst_csr_t a; kryst_pc_t pc; const kryst_params_t* params;
-    kryst_stats_t* stats; int32_t* status; double* hist; int64_t hist_cap; int64_t* hist_len;
-};
+// (MultiIO: multi.h)
 
 // what is refused before anything is launched or written
-static int32_t multi_args_check(const MultiIO& io, bool pcg) {
+int32_t multi_args_check(const MultiIO& io, bool pcg) {
     KR_ARG(io.b && io.x && io.a && io.params, "solve_multi: null argument");
     KR_TRY(mvec_check(io.b)); KR_TRY(mvec_check(io.x));
     KR_ARG(io.b->ctx == io.a->ctx && io.x->ctx == io.a->ctx, "solve_multi: context mismatch");

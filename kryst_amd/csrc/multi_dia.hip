@@ -93,12 +93,12 @@ __device__ __forceinline__ void spmm_dia_rows(const SpmmDiaArgs& a, int row, dou
 // EXACT: the operator's number of diagonals where the launcher has an instantiation for it (3, 5, 7, 9), else 0: batches of DB at run-time indices.
 // A capped grid strides over the tiles in natural order, so consecutive tiles go round-robin over the 8 XCDs as in spmv_dia_kernel.
 template <int K, int NQ, int DB, int EXACT, bool NT>
-__global__ __launch_bounds__(KR_T, 4) void spmm_dia_kernel(const SpmmDiaArgs a) {
+__global__ __launch_bounds__(KR_T, NQ == 2 ? 2 : 4) void spmm_dia_kernel(const SpmmDiaArgs a) {
     static_assert(K == 2 || K == 4 || K == 8, "K");
-    static_assert(NQ == 0 || NQ == 1, "NQ");
+    static_assert(NQ == 0 || NQ == 1 || NQ == 2, "NQ");
     if (a.done && *a.done) return;
     constexpr int H = K / 2;
-    __shared__ double red[(NQ > 0 ? NQ * K : 1) * (KR_T / 64)];
+    __shared__ double red[(NQ == 2 ? BcgShape<K>::RG : NQ == 1 ? K : 1) * (KR_T / 64)];
     const int t = threadIdx.x;
     for (int q = blockIdx.x; q < a.ntiles; q += gridDim.x) {
         const int r0 = q * KR_TILE;
@@ -119,7 +119,9 @@ __global__ __launch_bounds__(KR_T, 4) void spmm_dia_kernel(const SpmmDiaArgs a) 
 #pragma unroll
             for (int h = 0; h < H; ++h) { kr_v2d o; o.x = s1[2 * h]; o.y = s1[2 * h + 1]; yp[H + h] = o; }
         }
-        if constexpr (NQ > 0) {
+        // NQ = 2 (block CG): Gram(X, Y) instead; this arm alone is held to 2 waves per SIMD, its 36 running sums at K = 8 do not fit 128 VGPRs
+        if constexpr (NQ == 2) spmm_gram_epilogue<K>(a.x, row, row < r1, row + 1 < r1, s0, s1, red, a.partials, a.pstride, q);
+        if constexpr (NQ == 1) {
             // (D_j, Y_j) per column, formed as in spmm_rows_kernel: the lane's two products in index order, the 64-lane butterfly, the 4 waves
             const kr_v2d* dp = reinterpret_cast<const kr_v2d*>(a.dvec + (int64_t)row * K);     // (rows behind n lie in the padding: read, never used)
             double acc[K];
@@ -158,8 +160,8 @@ static int32_t launch_spmm_dia_k(kryst_csr_t a, const SpmmDiaArgs& g, int nq) {
     // or DB8 at run-time indices.  K = 8 has no exact instantiations: with every index known the compiler moves the next batch's loads above
     // this batch's fold, and the 5 / 7 / 9-diagonal kernels with the fused dot spilled 28 - 60 bytes per lane at 128 VGPRs.
     const int nd = g.nd, exact = K < 8 && (nd == 3 || nd == 5 || nd == 7 || nd == 9) ? nd : 0;
-    by_bool(nq != 0, [&](auto Q) { by_bool(nontemporal, [&](auto NT) {
-        constexpr int NQ = Q() ? 1 : 0;
+    by_int<0, 1, 2>(nq, [&](auto Q) { by_bool(nontemporal, [&](auto NT) {
+        constexpr int NQ = Q();
         bool launched = false;
         if constexpr (K < 8)
             launched = by_int<3, 5, 7, 9>(exact, [&](auto ND) { hipLaunchKernelGGL((spmm_dia_kernel<K, NQ, DB8, ND(), NT()>), grid, block, 0, s, g); });
