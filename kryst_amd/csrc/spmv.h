@@ -63,11 +63,12 @@ inline void spmv_args_fill(SpmvArgs& g, kryst_csr_t a, const double* x, double* 
     g.ntiles = (int32_t)a->ntiles; g.nrows = (int32_t)a->nrows; g.nloc = (int32_t)a->nrows;
     g.pid = a->d_pid; g.pmeta = a->d_pmeta; g.poff = a->d_poff; g.pval = a->d_pval; g.npat = a->npat; g.ntab = a->ntab;
 }
-// dynamic LDS of the staged-window kernels: `windows` windows of 512 T + 2 n + 4 doubles, 8 bytes per pattern, entry_bytes per table entry (12: values
-// and offsets, 8: values), then -- 16-byte aligned, at red_off -- red_copies x T x nq partials per wave
+// dynamic LDS of the staged-window kernels: `windows` windows of 512 T + 2 n + pad doubles (pad 4: a pair beyond the lines below and above, the
+// un-marched kernels; 0: the marching kernels, march_window.h), 8 bytes per pattern, entry_bytes per table entry (12: values and offsets, 8: values),
+// then -- 16-byte aligned, at red_off -- red_copies x T x nq partials per wave
 struct StagedLds { size_t red_off, bytes; };
-inline StagedLds staged_lds(kryst_csr_t a, int windows, int entry_bytes, int red_copies, int T, int nq) {
-    const size_t tab = (size_t)windows * sizeof(double) * (size_t)((int64_t)T * KR_TILE + 2 * a->pat_stage_n + 4) + (size_t)a->npat * 8 + (size_t)a->ntab * (size_t)entry_bytes;
+inline StagedLds staged_lds(kryst_csr_t a, int windows, int entry_bytes, int red_copies, int T, int nq, int pad = 4) {
+    const size_t tab = (size_t)windows * sizeof(double) * (size_t)((int64_t)T * KR_TILE + 2 * a->pat_stage_n + pad) + (size_t)a->npat * 8 + (size_t)a->ntab * (size_t)entry_bytes;
     const size_t red_off = (tab + 15) & ~(size_t)15;
     return StagedLds{red_off, red_off + sizeof(double) * (size_t)red_copies * (size_t)T * (size_t)nq * (KR_T / 64)};
 }

@@ -1,6 +1,7 @@
 // The staged-window CSR-P16 kernels fused with CG's vector passes -- spmv_pattern_fuse_kernel (the direction pass inside the SpMV; fuse_march: its marching
 // mode), cg_recompute_residual_kernel (the residual pass forms A p again) -- their plans, launches and hooks.  spmv.hip: the contract, the staged form's predicates.
 #include "spmv.h"
+#include "march_window.h"
 
 namespace kr {
 // KRYST_SPMV_PID_REUSE (the marching kernels; csr_create.hip: build_pid_same): the pid_same flags of a strip's T tiles in the plane whose strip starts
@@ -38,9 +39,9 @@ struct FuseArgs { const double* z; const double* p_old; double* p_new; double* x
 // above, so a workgroup that keeps its strip of R = 512 T consecutive rows of a plane and walks a segment of S planes along k holds them itself:
 // e[6] is read from the window of plane s + 1 at the LDS index of B, and e[0] is the lane's own B pair of plane s - 1, carried in registers (the
 // lane-to-row mapping is the same in every step).  Only the first and the last plane of a segment form a far operand from z and p_old in memory
-// (clamped at the ends of the box), as the un-marched kernel does for every tile: per own line 1 + (2 n + 4) / R + 2 / S lines of z and p_old are
+// (clamped at the ends of the box), as the un-marched kernel does for every tile: per own line 1 + 2 n / R + 2 / S lines of z and p_old are
 // requested instead of 3 + (2 n + 4) / R, and the halo lines are a neighbouring strip's own lines on the same XCD.
-//   LDS: TWO windows of R + 2 n + 4 doubles, W(s) and W(s + 1).  A step is
+//   LDS: TWO windows of R + 2 n doubles (march_window.h: from row r0 - n; a lane requests its own pairs first, then its share of the halo), W(s) and W(s + 1).  A step is
 //     a. request W(s + 2): z, p_old (and the owed x) of the whole window into REGISTERS, and the ids of plane s + 1 -- of those tiles whose pid_same
 //        flag is clear: the others repeat the plane below and stay in ids[k], KRYST_SPMV_PID_REUSE -- in flight under b.  (Not by
 //        LDS-DMA as the un-marched fill: beside a pending DMA the compiler drains vmcnt(0) before the first LDS read of b. and before every use of
@@ -58,13 +59,13 @@ struct FuseArgs { const double* z; const double* p_old; double* p_new; double* x
 //   the same planes (contiguous in memory at every step, halo lines shared in that XCD's L2), and a strip is on the same XCD in every segment.
 //   Which workgroup computes a tile changes and nothing else: per-element arithmetic, entry order, absent-entry selects and the per-tile partials
 //   (thread, wave butterfly, the four waves in turn, partials[tile]) are the un-marched kernel's -- the same bits.
-//   Registers: 164 at T = 4 without the x update (the un-marched instance: 98) -- a whole window of z and p_old is held across b. -- i.e. three waves per
+//   Registers: 156 at T = 4 without the x update (164 with windows of R + 2 n + 4 doubles in plain lane order; the un-marched instance: 98) -- a whole window of z and p_old is held across b. -- i.e. three waves per
 //   SIMD, one more than the two workgroups per CU the launch keeps resident need.  Measured at 512^3 (profiles/march/): HBM traffic 39.9 -> 35.4 bytes
 //   per row (model 34), the kernel 879 -> 843 us, CG 601 -> 628 it/s.
 //   a.group: strips per XCD; a.xcd_chunk: S; a.tpw: strips per plane; far_hi == -far_lo == the plane; every strip and every plane is whole.
 template <int NQ, int T, int NMAX, bool XU, bool YS>
 __device__ __forceinline__ void fuse_march(const SpmvArgs& a, const FuseArgs& f, const int32_t n, const int32_t plane, unsigned char* smem, const bool ended, const bool owed) {
-    const int XS = T * KR_TILE + 2 * n + 4;                                  // elements of one window (even)
+    const int XS = march_window_elems(n, T);                                 // elements of one window (even)
     double* win = reinterpret_cast<double*>(smem);
     uint2* meta = reinterpret_cast<uint2*>(win + 2 * XS);
     double* pval = reinterpret_cast<double*>(meta + a.npat);
@@ -89,38 +90,36 @@ __device__ __forceinline__ void fuse_march(const SpmvArgs& a, const FuseArgs& f,
         }
         return;
     }
-    constexpr int NP = (T * KR_TILE + 2 * NMAX + 4 + 2 * KR_T - 1) / (2 * KR_T);   // pairs per lane at most (n <= NMAX)
-    const int npairs = XS / 2;
+    constexpr int NP = march_window_requests(NMAX, T, KR_T);                 // requests per lane at most (n <= NMAX)
     const int32_t xsafe = (int32_t)a.xsafe;
-    const int own_lo = (n + 2) / 2, own_hi = own_lo + T * (KR_TILE / 2);    // window pairs that are rows of the strip
-    v2d zz[NP], po[NP], xo[XU ? NP : 1];
-    // a window's requests (r0: the strip's first row in that plane).  Every lane loads NP pairs: pairs past the window's end are clamped into it (and
-    // dropped by write_window) -- no branch around a load
+    v2d zz[NP], po[NP], xo[XU ? T : 1];
+    // a window's requests (r0: the strip's first row in that plane; march_window.h: requests 0 .. T - 1 are the lane's own pairs, the others its
+    // share of the halo).  Every lane loads NP pairs: a request without a pair repeats the lane's first own pair (and is dropped by write_window) -- no
+    // branch around a load
     auto request = [&](const int32_t r0) {
-        const int32_t e0 = r0 - n - 2;                                       // element at the window's [0] (even)
+        const int32_t e0 = r0 - n;                                           // element at the window's [0] (even)
         const bool inside = e0 >= 0 && e0 + XS <= xsafe;
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
-            const int pi = min(t + i * KR_T, npairs - 1);
-            const int32_t e = inside ? e0 + 2 * pi : min(max(e0 + 2 * pi, 0), xsafe);     // outside x: any valid pair (those operands are absent entries)
+            const int q = march_window_request(t, i, n, T, KR_T).lds, o = q < 0 ? march_window_request(t, 0, n, T, KR_T).lds : q;
+            const int32_t e = inside ? e0 + o : min(max(e0 + o, 0), xsafe);  // outside x: any valid pair (those operands are absent entries)
             po[i] = *reinterpret_cast<const v2d*>(f.p_old + e);
             zz[i] = *reinterpret_cast<const v2d*>(f.z + e);
-            if constexpr (XU) { xo[i].x = 0.0; xo[i].y = 0.0; if (owed && pi >= own_lo && pi < own_hi) xo[i] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(f.xvec + e)); }     // (own rows are never clamped; read once)
+            if constexpr (XU) { if (i < T) { xo[i].x = 0.0; xo[i].y = 0.0; if (owed) xo[i] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(f.xvec + e)); } }     // (own rows are never clamped; read once)
         }
     };
     // p_new = z + beta p_old (cg.rs:274-276 / pcg.rs:215-217, un-fused multiply and add) into the window; own rows also to memory, with their x update
     auto write_window = [&](const int32_t r0, double* xs) {
-        const int32_t e0 = r0 - n - 2;
+        const int32_t e0 = r0 - n;
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
-            const int pi = t + i * KR_T;
-            if (pi < npairs) {
+            const int q = march_window_request(t, i, n, T, KR_T).lds;
+            if (q >= 0) {
                 v2d pn; pn.x = zz[i].x + be * po[i].x; pn.y = zz[i].y + be * po[i].y;
-                *reinterpret_cast<v2d*>(xs + 2 * pi) = pn;
-                if (pi >= own_lo && pi < own_hi) {
-                    const int32_t row = e0 + 2 * pi;
-                    st2(f.p_new, row, pn.x, pn.y);
-                    if constexpr (XU) { if (owed) st2(f.xvec, row, xo[i].x + al * po[i].x, xo[i].y + al * po[i].y); }
+                *reinterpret_cast<v2d*>(xs + q) = pn;
+                if (i < T) {                                                // (an own pair)
+                    st2(f.p_new, e0 + q, pn.x, pn.y);
+                    if constexpr (XU) { if (owed) st2(f.xvec, e0 + q, xo[i].x + al * po[i].x, xo[i].y + al * po[i].y); }
                 }
             }
         }
@@ -173,7 +172,7 @@ __device__ __forceinline__ void fuse_march(const SpmvArgs& a, const FuseArgs& f,
         for (int k = 0; k < T; ++k) {
             const int32_t row = r0 + k * KR_TILE + 2 * t;
             const uint2 ma = meta[ids[k] & 0xffffu], mb = meta[ids[k] >> 16];
-            const int j = k * KR_TILE + 2 * t + n + 2;                       // w0[j] = p_new[row], w1[j] = p_new[row + plane]
+            const int j = march_window_tile_offset(n, k) + 2 * t;            // w0[j] = p_new[row], w1[j] = p_new[row + plane]
             const v2d A = *reinterpret_cast<const v2d*>(w0 + j - 2), B = *reinterpret_cast<const v2d*>(w0 + j), C = *reinterpret_cast<const v2d*>(w0 + j + 2);
             const v2d M = *reinterpret_cast<const v2d*>(w0 + j - n), P = *reinterpret_cast<const v2d*>(w0 + j + n);
             const v2d U = *reinterpret_cast<const v2d*>(w1 + j);             // (the segment's last plane: not used)
@@ -218,7 +217,7 @@ __device__ __forceinline__ void fuse_march(const SpmvArgs& a, const FuseArgs& f,
         if (fill) write_window(r0 + 2 * plane, w0);
         __syncthreads();                                                     // barrier 2
 #pragma unroll
-        for (int k = 0; k < T; ++k) if (!((sw >> (8 * k)) & 1u)) ids[k] = idn[k];       // (a hand-over, not a copy back and forth: the compiler gathers T plain copies into one register tuple)
+        for (int k = 0; k < T; ++k) if (!((sw >> (8 * k)) & 1u)) ids[k] = idn[k];       // (a hand-over, not a copy back and forth: the compiler gathers the plain copies into one register tuple)
         same = samen;
         double* w = w0; w0 = w1; w1 = w;
     }
@@ -389,13 +388,13 @@ __global__ __launch_bounds__(KR_T) void spmv_pattern_fuse_kernel(const SpmvArgs 
 // direction vector that kernel has just stored -- the very doubles it had in its windows, the same e[0 .. 6], table values, absent-entry selects and
 // un-fused multiply and add from 0.0, so the same bits -- and goes on as CgResidualOp does: r -= alpha Ap (cg.rs:210-212), the tile partial of (r, r)
 // (:223) in ew_kernel's order (thread: 0 + r0 r0 + r1 r1; wave butterfly; the four waves in turn; partials[tile]).  Per row: p (own rows once, the
-// window's halo (2 n + 4) / R and 2 / S far lines besides), r and the pattern id read, r written: 26 + halo instead of 24, and the fused kernel
+// window's halo 2 n / R and 2 / S far lines besides), r and the pattern id read, r written: 26 + halo instead of 24, and the fused kernel
 // writes 8 bytes per row less (p_new and nothing else).
 //   Mapping: fuse_march's -- the same T, S, strips per XCD and grid (fuse_march_plan), so a strip is on the same XCD in both kernels of an iteration and
 //   the halo lines are a neighbouring strip's own lines in that L2.  The window holds plain p: no z / p_old staging, e[0] is the lane's own B pair of
 //   the plane below carried in registers, e[6] comes out of the next plane's window, and only a segment's first and last plane load a far pair of p
 //   from memory (clamped at the ends of the box: only absent entries point there).
-//   LDS: THREE windows of R + 2 n + 4 doubles, W(s), W(s + 1) and the one being filled, and two copies of red.  A step is
+//   LDS: THREE windows of R + 2 n doubles (march_window.h), W(s), W(s + 1) and the one being filled, and two copies of red.  A step is
 //     a. request W(s + 2) of p into registers, and r's own rows and the ids of plane s + 1 (nontemporal: read once) -- in flight under b.  (Plain loads,
 //        not LDS-DMA, for fuse_march's reason: r and the ids are in flight beside the window, and beside a pending DMA the compiler drains vmcnt(0)
 //        before every use of an ordinary load.)
@@ -408,7 +407,7 @@ __global__ __launch_bounds__(KR_T) void spmv_pattern_fuse_kernel(const SpmvArgs 
 //   and written again in b. of step s + 2, which its writers reach only through the barrier of step s + 1, behind d. of step s in every wave.  The
 //   barrier is executed in every step by every wave (the branches around the fills depend on s and the segment's length alone).
 //   Resources (gfx950, T = 4, n = 512): 165 VGPRs, no scratch (the compiler keeps a tile's LDS reads and the window in flight side by side: three waves
-//   per SIMD would fit, two are resident); LDS 3 x 24 608 B of windows + 8 B per pattern and table entry + 256 B of red, padded to 81 408 B (half a CU's LDS less 512).  Measured at
+//   per SIMD would fit, two are resident); LDS 3 x 24 576 B of windows + 8 B per pattern and table entry + 256 B of red, padded to 81 408 B (half a CU's LDS less 512).  Measured at
 //   512^3 (profiles/recompute/): the fused kernel 810 -> 632 us (35.3 -> 27.2 bytes per row), the residual pass 507 -> 620 us (24.1 -> 26.5), CG 628 ->
 //   674 it/s.  With the ids kept where they repeat (KRYST_SPMV_PID_REUSE, fuse_march's step a.; profiles/pid_reuse/): 168 VGPRs, the residual pass
 //   621 -> 576 us (26.5 -> 24.5 bytes per row).
@@ -431,7 +430,7 @@ template <int T, bool KEEP, bool LEG>
 __global__ __launch_bounds__(KR_T) void cg_recompute_residual_kernel(const SpmvArgs a, const double* p, double* r, const double* alpha, const int32_t n, const int32_t plane, const LegVals lv) {
     if (a.done && *a.done) return;                                           // (GateDone: alpha's logic may have ended the solve)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int XS = T * KR_TILE + 2 * n + 4;                                  // elements of one window (even)
+    const int XS = march_window_elems(n, T);                                 // elements of one window (even)
     double* win = reinterpret_cast<double*>(smem);
     uint2* meta = reinterpret_cast<uint2*>(win + 3 * XS);
     double* pval = reinterpret_cast<double*>(meta + a.npat);
@@ -445,27 +444,26 @@ __global__ __launch_bounds__(KR_T) void cg_recompute_residual_kernel(const SpmvA
     const int ns = min(S, nplanes - k0);                                     // planes of this segment (the last one may be shorter)
     const int32_t rbeg = k0 * plane + strip * (T * KR_TILE);                 // first row of the strip in the segment's first plane
     const double al = *alpha;
-    constexpr int NP = (T * KR_TILE + 2 * 512 + 4 + 2 * KR_T - 1) / (2 * KR_T);     // pairs per lane at most (n <= 512)
-    const int npairs = XS / 2;
+    constexpr int NP = march_window_requests(512, T, KR_T);                  // requests per lane at most (n <= 512)
     const int32_t xsafe = (int32_t)a.xsafe;
     v2d wp[NP];
-    // a window's requests (r0: the strip's first row in that plane).  Every lane loads NP pairs: pairs past the window's end are clamped into it (and
-    // dropped by write_window) -- no branch around a load
+    // a window's requests (r0: the strip's first row in that plane; march_window.h: the lane's own pairs first, then its share of the halo).  Every lane
+    // loads NP pairs: a request without a pair repeats the lane's first own pair (and is dropped by write_window) -- no branch around a load
     auto request = [&](const int32_t r0) {
-        const int32_t e0 = r0 - n - 2;                                       // element at the window's [0] (even)
+        const int32_t e0 = r0 - n;                                           // element at the window's [0] (even)
         const bool inside = e0 >= 0 && e0 + XS <= xsafe;
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
-            const int pi = min(t + i * KR_T, npairs - 1);
-            const int32_t e = inside ? e0 + 2 * pi : min(max(e0 + 2 * pi, 0), xsafe);     // outside p: any valid pair (those operands are absent entries)
+            const int q = march_window_request(t, i, n, T, KR_T).lds, o = q < 0 ? march_window_request(t, 0, n, T, KR_T).lds : q;
+            const int32_t e = inside ? e0 + o : min(max(e0 + o, 0), xsafe);  // outside p: any valid pair (those operands are absent entries)
             wp[i] = *reinterpret_cast<const v2d*>(p + e);
         }
     };
     auto write_window = [&](double* xs) {
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
-            const int pi = t + i * KR_T;
-            if (pi < npairs) *reinterpret_cast<v2d*>(xs + 2 * pi) = wp[i];
+            const int q = march_window_request(t, i, n, T, KR_T).lds;
+            if (q >= 0) *reinterpret_cast<v2d*>(xs + q) = wp[i];
         }
     };
     // a far operand the segment does not hold (below its first plane, above its last)
@@ -522,7 +520,7 @@ __global__ __launch_bounds__(KR_T) void cg_recompute_residual_kernel(const SpmvA
             const int32_t row = r0 + k * KR_TILE + 2 * t;
             uint2 ma = make_uint2(0u, ids[k] & 0xffu), mb = make_uint2(0u, ids[k] >> 8);     // (LEG: the masks out of the tile's word, no table)
             if constexpr (!LEG) { ma = meta[ids[k] & 0xffffu]; mb = meta[ids[k] >> 16]; }
-            const int j = k * KR_TILE + 2 * t + n + 2;                       // w0[j] = p[row], w1[j] = p[row + plane]
+            const int j = march_window_tile_offset(n, k) + 2 * t;            // w0[j] = p[row], w1[j] = p[row + plane]
             const v2d A = *reinterpret_cast<const v2d*>(w0 + j - 2), B = *reinterpret_cast<const v2d*>(w0 + j), C = *reinterpret_cast<const v2d*>(w0 + j + 2);
             const v2d M = *reinterpret_cast<const v2d*>(w0 + j - n), P = *reinterpret_cast<const v2d*>(w0 + j + n);
             const v2d U = *reinterpret_cast<const v2d*>(w1 + j);             // (the segment's last plane: not used)
@@ -583,6 +581,8 @@ bool spmv_can_fuse_direction(kryst_csr_t a) {
 // a plane of 1 600 rows; 16^3: a tile spans two planes) takes the un-marched path untouched.  KRYST_SPMV_FUSE_MARCH (0 / 1), KRYST_SPMV_FUSE_SEG
 // (S) and KRYST_SPMV_FUSE_T are read per launch.
 struct FuseMarchPlan { bool eligible, on; int T, strips, S, segs; StagedLds lds; };
+// (strips of 8 tiles walked by workgroups of 512 threads, one per CU -- 1.25 instead of 1.5 window requests per own row -- were built and measured:
+// CG 714 against 768 it/s at 512^3, 0.70 at 384^3, 0.93 at 256^3 of the rate at T = 4; not in the tree, profiles/march_t8/)
 static FuseMarchPlan fuse_march_plan(kryst_csr_t a, int nq) {
     FuseMarchPlan m;
     memset(&m, 0, sizeof m);
@@ -590,7 +590,7 @@ static FuseMarchPlan fuse_march_plan(kryst_csr_t a, int nq) {
     const int64_t plane = a->pat_far_uniform ? (int64_t)a->pat_far_hi : 0, R = (int64_t)m.T * KR_TILE;
     const int32_t n_ = a->pat_stage_n;
     if (!(a->d_pid && n_ > 0 && n_ <= 512 && plane > 0 && (int64_t)a->pat_far_lo == -plane && plane % R == 0 && a->nrows % plane == 0 && a->nrows == a->xlen)) return m;
-    m.lds = staged_lds(a, 2, 8, 1, m.T, nq);
+    m.lds = staged_lds(a, 2, 8, 1, m.T, nq, 0);
     if (m.lds.bytes > ((size_t)80 << 10)) return m;
     const int64_t nplanes = a->nrows / plane;
     m.eligible = true;
@@ -622,7 +622,7 @@ static RecomputePlan recompute_plan(kryst_csr_t a) {
     memset(&q, 0, sizeof q);
     q.m = fuse_march_plan(a, 2);
     if (!(q.m.eligible && q.m.on)) return q;
-    q.lds = staged_lds(a, 3, 8, 2, q.m.T, 1);
+    q.lds = staged_lds(a, 3, 8, 2, q.m.T, 1, 0);
     if (q.lds.bytes > ((size_t)(160 << 10) / 2 - 512)) return q;
     // (32: CG's default batch length in the fused form, cg_pcg.hip: cg_x_batch; the solver also checks the length it really took)
     q.on = env_int("KRYST_CG_X_BATCH", 32) > 1 && env_int("KRYST_CG_RECOMPUTE_AP", beyond_fuse_min_bytes(a) ? 1 : 0) != 0;
@@ -725,9 +725,9 @@ static int32_t launch_spmv_fused_impl(kryst_csr_t a, const double* z, const doub
             hipLaunchKernelGGL((spmv_pattern_fuse_kernel<NQ(), T_(), 512, XU(), true, YS()>), mgrid, block, lds_m, ctx->s_main, args, f, n_, a->pat_far_lo, a->pat_far_hi); };
         if (!y) {                                      // no y store: the residual pass forms A p again (launch_cg_residual_recompute)
             KR_ARG(nq == 1 && !xvec, "launch_spmv_fused: the form without y is CG's with x in batches");
-            by_int<2, 4>(T, [&](auto T_) { march(std::integral_constant<int, 1>{}, T_, std::false_type{}, std::false_type{}); });
+            by_int<2, 4>(m.T, [&](auto T_) { march(std::integral_constant<int, 1>{}, T_, std::false_type{}, std::false_type{}); });
         } else {
-            by_int<1, 2>(nq, [&](auto NQ) { by_int<2, 4>(T, [&](auto T_) { by_bool(xvec != nullptr, [&](auto XU) { march(NQ, T_, XU, std::true_type{}); }); }); });
+            by_int<1, 2>(nq, [&](auto NQ) { by_int<2, 4>(m.T, [&](auto T_) { by_bool(xvec != nullptr, [&](auto XU) { march(NQ, T_, XU, std::true_type{}); }); }); });
         }
         KR_HIP(hipGetLastError());
         phase_mark(ctx, KR_PH_SPMV);
