@@ -387,8 +387,8 @@ int32_t kryst_pc_spai_export(kryst_pc_t pc, int64_t* nnz, int64_t* row_ptr, int3
  * extension, textbook smoothed aggregation set up on the device (threshold = theta of |a_ij| > theta sqrt(|a_ii a_jj|); distance-2 MIS
  * aggregates; P = (I - 4/(3 rho) D^-1 A) P0; R = P^T; A_c = R (A P); stop at <= 64 rows, max_levels >= 1 levels or n_c > 0.8 n; block
  * Jacobi of 64 rows on the coarsest level); its apply starts from z = 0 with nu_pre / nu_post damped Jacobi sweeps, and a zero diagonal
- * is KRYST_ZERO_PIVOT.  Export which 3 then gives omega D^-1, which 4 the aggregates (col).  Errors: KRYST_ERR_ARG (non-square or distributed operator,
- * rows not strictly ascending, max_levels / nu_pre / nu_post < 0), KRYST_FACTOR_ERROR (a level over the fill budget of kryst_host_amg).
+ * is KRYST_ZERO_PIVOT.  Export which 3 then gives omega D^-1, which 4 the aggregates (col).  Errors: KRYST_ERR_ARG (non-square operator,
+ * rows not strictly ascending, max_levels / nu_pre / nu_post < 0), KRYST_UNSUPPORTED (a distributed operator), KRYST_FACTOR_ERROR (a level over the fill budget of kryst_host_amg).
  * a is borrowed (must outlive the preconditioner); the coarse levels are owned. */
 enum { KRYST_AMG_AS_WRITTEN = 0, KRYST_AMG_SMOOTHED = 1, KRYST_AMG_DIRECT_MAX = 4096 };
 int32_t kryst_pc_amg(kryst_csr_t a, int32_t max_levels, double threshold, int32_t variant, int32_t nu_pre, int32_t nu_post, kryst_pc_t* out);

@@ -544,7 +544,7 @@ extern "C" {
 int32_t kryst_pc_amg(kryst_csr_t a, int32_t max_levels, double threshold, int32_t variant, int32_t nu_pre, int32_t nu_post, kryst_pc_t* out) {
     KR_ARG(a && out, "pc_amg");
     *out = nullptr;
-    KR_ARG(!a->dist, "pc_amg: distributed operators are not supported");
+    if (a->dist) { set_error("pc_amg: distributed operators are not supported"); return KRYST_UNSUPPORTED; }
     KR_ARG(a->nrows == a->xlen && a->nrows == a->ncols, "pc_amg: square operator required");
     KR_ARG(max_levels >= 0 && nu_pre >= 0 && nu_post >= 0, "pc_amg: max_levels, nu_pre and nu_post must be >= 0");
     KR_ARG(variant == KRYST_AMG_AS_WRITTEN || variant == KRYST_AMG_SMOOTHED, "pc_amg: unknown variant");

@@ -223,7 +223,7 @@ static int32_t make_checked_w(kryst_csr_t a, double** out) {
         if (e != hipSuccess) { set_error("chebyshev_poly: checking the diagonal failed: %s", hipGetErrorString(e)); rc = KRYST_ERR_HIP; }
     }
     if (rc == KRYST_OK && bad != ~0ull) {
-        const int64_t row = (a->dist && !a->row_offsets.empty() ? a->row_offsets[a->ctx->rank] : 0) + (int64_t)bad;
+        const int64_t row = (int64_t)bad;          // (the only caller has refused a distributed operator: local rows are global rows)
         set_error("chebyshev_poly: Jacobi scaling needs a finite positive diagonal; row %lld has none", (long long)row);
         set_error_row(row);
         rc = KRYST_INDEFINITE_PRECONDITIONER;

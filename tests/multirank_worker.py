@@ -79,8 +79,8 @@ def main():
         sys.exit(3)
 
 
-def run_rank(rank, P, outdir, N, kind):
-    stage(rank, "start")
+def make_context(rank, P, outdir):
+    """The rendezvous: rank 0 publishes the communicator id in <outdir>/uid.bin, the others wait for the file; -> the rank's context"""
     idfile = os.path.join(outdir, "uid.bin")
     if rank == 0:
         uid = K.Context.unique_id()
@@ -94,7 +94,18 @@ def run_rank(rank, P, outdir, N, kind):
             time.sleep(0.01)
         uid = open(idfile, "rb").read()
     stage(rank, "ctx_create_dist")
-    ctx = K.Context(0, rank, P, uid)
+    return K.Context(0, rank, P, uid)
+
+
+def save_rank(outdir, rank, out):
+    """the rank's results, <outdir>/rank<r>.npz, and the line that says it got there"""
+    np.savez(os.path.join(outdir, f"rank{rank}.npz"), **out)
+    print(f"RANK_OK {rank}")
+
+
+def run_rank(rank, P, outdir, N, kind):
+    stage(rank, "start")
+    ctx = make_context(rank, P, outdir)
     # what the library chose by itself (mailboxes when they work on every rank), then the RCCL all-gather path: the reference results below
     # are made with RCCL + RCCL, the hipIpc forms are compared with them further down
     default_scalar = ctx.scalar_reduce("query")
@@ -247,8 +258,7 @@ def run_rank(rank, P, outdir, N, kind):
         assert a.halo_mode("rccl") == "rccl"
     stage(rank, "barrier")
     ctx.barrier()
-    np.savez(os.path.join(outdir, f"rank{rank}.npz"), **out)
-    print(f"RANK_OK {rank}")
+    save_rank(outdir, rank, out)
 
 
 if __name__ == "__main__":
