@@ -12,6 +12,8 @@
  *     across the ABI.
  *   - handles are opaque, created and destroyed by the library; host arrays are borrowed only for the
  *     duration of a call; one host thread per context; contexts are independent.
+ *   - all handles of one call belong to ONE context: a call that is handed handles of two contexts returns KRYST_ERR_ARG before any
+ *     launch and writes nothing -- a preconditioner the solver ignores included.
  *   - all arithmetic is IEEE fp64 with no FMA contraction; row sums run over ascending stored columns.
  *   - inner products use ONE fixed association tree (kryst_reduce_spec): results are run-to-run and
  *     launch-configuration independent; with nranks > 1 rank results are folded in rank order.

@@ -21,6 +21,7 @@ There is no CPU fallback and no torch dependency.
 """
 import ctypes as C
 import enum
+import weakref
 import numpy as np
 
 from . import _ffi
@@ -51,11 +52,18 @@ def reduce_spec():
 
 
 class Context:
-    """One GPU (one rank).  Replaces the Comm objects of src/parallel (RayonComm / MpiComm)."""
+    """One GPU (one rank).  Replaces the Comm objects of src/parallel (RayonComm / MpiComm).
+
+    Lifetime: a context of ONE rank is destroyed when it is dropped (`__del__` calls `close()`); every handle made on it keeps it alive, so
+    that happens after its last vector, operator and preconditioner has gone.  `close()` may also be called while such objects are alive: it
+    destroys them first -- sessions, preconditioners, lowered operators, operators, vectors, in this order -- and leaves each with `h = None`
+    (its methods then raise KError).  A DISTRIBUTED context (nranks > 1) is never destroyed by the garbage collector: tearing it down tears
+    down its communicator, which every rank has to do at a point of its own choosing, so it keeps the explicit `close()`."""
 
     _default = None
 
     def __init__(self, device=0, rank=0, nranks=1, unique_id=None):
+        self._children = {}                          # id -> weak reference of every live object that holds a handle of this context
         self.h = _ffi.Handle()
         if nranks == 1 and unique_id is None:
             check(lib().kryst_ctx_create(device, C.byref(self.h)))
@@ -133,14 +141,53 @@ class Context:
     def vec(self, n_or_array):
         return DeviceVec(self, n_or_array)
 
+    def _adopt(self, child):
+        """remember `child` (weakly): close() destroys it before the context"""
+        key = id(child)
+        self._children[key] = weakref.ref(child, lambda _r, k=key, c=self._children: c.pop(k, None))
+
     def close(self):
-        if self.h:
-            lib().kryst_ctx_destroy(self.h)
-            self.h = None
+        """Destroy the context and, first, whatever still lives on it (see the class docstring).  Safe to call twice."""
+        if not getattr(self, "h", None):
+            return
+        alive = [c for c in (r() for r in list(self._children.values())) if c is not None]
+        for c in sorted(alive, key=lambda c: c._CLOSE_ORDER):       # (stable: creation order within a kind)
+            c._release()
+        self._children.clear()
+        lib().kryst_ctx_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            if self.nranks == 1:
+                self.close()
+        except Exception:
+            pass
 
 
-class DeviceVec:
+class _Owned:
+    """What every object with a handle of a context shares: the context knows it (weakly), `_release()` destroys the handle once and leaves
+    `h = None`; dropping the object releases it."""
+    _CLOSE_ORDER = 4                                 # Context.close(): 0 sessions, 1 preconditioners, 2 lowered operators, 3 operators, 4 vectors
+    _DESTROY = None                                  # the kryst_*_destroy symbol
+    h = None
+    ctx = None
+
+    def _release(self):
+        h, self.h = self.h, None
+        if h and self.ctx is not None and self.ctx.h:
+            getattr(lib(), self._DESTROY)(h)
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+
+class DeviceVec(_Owned):
     """A Vec<f64> resident in HBM."""
+    _DESTROY = "kryst_vec_destroy"
 
     def __init__(self, ctx, n_or_array):
         self.ctx = ctx
@@ -148,10 +195,12 @@ class DeviceVec:
         if np.isscalar(n_or_array):
             self.n = int(n_or_array)
             check(lib().kryst_vec_create(ctx.h, self.n, C.byref(self.h)))
+            ctx._adopt(self)
         else:
             a = _f64(n_or_array)
             self.n = len(a)
             check(lib().kryst_vec_create(ctx.h, self.n, C.byref(self.h)))
+            ctx._adopt(self)
             self.upload(a)
 
     def __len__(self):
@@ -194,13 +243,6 @@ class DeviceVec:
         check(lib().kryst_bench_vec_padding(self.h, None, C.byref(dirty)))
         return dirty.value
 
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                lib().kryst_vec_destroy(self.h)
-        except Exception:
-            pass
-
 
 MVEC_WIDTHS = (8, 4, 2)
 
@@ -221,13 +263,15 @@ def split_widths(m):
     return out
 
 
-class MultiVec:
+class MultiVec(_Owned):
     """n x k device multivector, k in {2, 4, 8} (kryst_mvec_t): the k values of a row are contiguous in HBM."""
+    _DESTROY = "kryst_mvec_destroy"
 
     def __init__(self, ctx, n, k):
         self.ctx, self.n, self.k = ctx, int(n), int(k)
         self.h = _ffi.Handle()
         check(lib().kryst_mvec_create(ctx.h, self.n, self.k, C.byref(self.h)))
+        ctx._adopt(self)
 
     @staticmethod
     def from_numpy(a, ctx=None):
@@ -277,13 +321,6 @@ class MultiVec:
         check(lib().kryst_bench_mvec_padding(self.h, None, C.byref(dirty)))
         return dirty.value
 
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                lib().kryst_mvec_destroy(self.h)
-        except Exception:
-            pass
-
 
 def _fp(a):
     return a.ctypes.data_as(_ffi.c_fp)
@@ -307,8 +344,9 @@ def host_round_f32(values):
     return out, info[0], info[1]
 
 
-class DeviceVec32:
+class DeviceVec32(_Owned):
     """A Vec<f32> resident in HBM (kryst_vec32_t): fp32 is how the elements are stored, every kernel computes in fp64."""
+    _DESTROY = "kryst_vec32_destroy"
 
     def __init__(self, ctx, n_or_array):
         self.ctx = ctx
@@ -316,10 +354,12 @@ class DeviceVec32:
         if np.isscalar(n_or_array):
             self.n = int(n_or_array)
             check(lib().kryst_vec32_create(ctx.h, self.n, C.byref(self.h)))
+            ctx._adopt(self)
         else:
             a = np.ascontiguousarray(n_or_array, dtype=np.float32)
             self.n = len(a)
             check(lib().kryst_vec32_create(ctx.h, self.n, C.byref(self.h)))
+            ctx._adopt(self)
             self.upload(a)
 
     def __len__(self):
@@ -363,13 +403,6 @@ class DeviceVec32:
         check(lib().kryst_bench_vec32_padding(self.h, None, C.byref(dirty)))
         return dirty.value
 
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                lib().kryst_vec32_destroy(self.h)
-        except Exception:
-            pass
-
 
 def dot32(x, y):
     """InnerProduct::dot on fp32-stored device vectors: exact fp64 terms folded in the tree of reduce_spec32()."""
@@ -378,7 +411,7 @@ def dot32(x, y):
     return out.value
 
 
-class CsrMatrix32:
+class CsrMatrix32(_Owned):
     """CsrMatrix<f32> lowered from a CsrMatrix (kryst_csr32_lower_form): its own copies of the index arrays, the values rounded to fp32.
     form "plain" keeps the CSR arrays alone; "pattern" also keeps the operator's CSR-P16 row-pattern form with fp32 tables (KError Unsupported
     when it has none); "auto" keeps it where there is one; "dia" (opt-in, never chosen by "auto") also keeps the operator's CSR-DIA diagonal
@@ -389,6 +422,7 @@ class CsrMatrix32:
     FORMS_EXT = {"dia": 3}              # the forms and kernels added since, kept beside the first three
     KERNELS_EXT = ("dia",)
     DIA_ABSENT_BITS = 0x7FD1A0D1        # KRYST_CSR32_DIA_ABSENT_BITS: "no entry here" in an fp32 diagonal stream
+    _DESTROY, _CLOSE_ORDER = "kryst_csr32_destroy", 2
 
     @classmethod
     def form_code(cls, form):
@@ -402,6 +436,7 @@ class CsrMatrix32:
         self.ctx = a.ctx
         self.h = _ffi.Handle()
         check(lib().kryst_csr32_lower_form(a.h, self.form_code(form), C.byref(self.h)))
+        self.ctx._adopt(self)
         self._nrows, self._ncols, self.nnz = a.nrows(), a.ncols(), a.nnz
 
     def nrows(self):
@@ -436,13 +471,6 @@ class CsrMatrix32:
         check(lib().kryst_spmv32(self.h, xv.h, yv.h))
         return yv.to_host()
 
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                lib().kryst_csr32_destroy(self.h)
-        except Exception:
-            pass
-
 
 def dot(x, y):
     """InnerProduct::dot (wrappers.rs:90-108) on device vectors."""
@@ -475,11 +503,13 @@ def sub(a, b, out):
 STENCIL_KINDS = {"poisson": 0, "aniso": 1, "convdiff": 2, "varcoef": 3}   # kryst_csr_create_stencil7 / kryst_host_stencil7
 
 
-class CsrMatrix:
+class CsrMatrix(_Owned):
     """CsrMatrix<f64> (src/matrix/sparse.rs:22-46) living on the GPU; implements SparseMatrix::spmv and MatVec."""
+    _DESTROY, _CLOSE_ORDER = "kryst_csr_destroy", 3
 
     def __init__(self, ctx, handle):
         self.ctx, self.h = ctx, handle
+        ctx._adopt(self)
         nr, nc, nz = C.c_int64(), C.c_int64(), C.c_int64()
         check(lib().kryst_csr_shape(self.h, C.byref(nr), C.byref(nc), C.byref(nz)))
         self._nrows, self._ncols, self.nnz = nr.value, nc.value, nz.value
@@ -714,17 +744,11 @@ class CsrMatrix:
         check(lib().kryst_csr_download(self.h, rp.ctypes.data_as(_ffi.c_i64p), ci.ctypes.data_as(_ffi.c_i32p), _dp(va)))
         return rp, ci, va
 
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                lib().kryst_csr_destroy(self.h)
-        except Exception:
-            pass
-
 
 # ----------------------------------------------------------------------------- preconditioners
-class _Pc:
+class _Pc(_Owned):
     """Preconditioner<M, V> (src/preconditioner/mod.rs:8-13): setup(&mut self, a), apply(&self, r, z)."""
+    _DESTROY, _CLOSE_ORDER = "kryst_pc_destroy", 1
 
     def __init__(self):
         self.h, self.ctx = None, None
@@ -732,6 +756,7 @@ class _Pc:
     def _set(self, ctx, handle):
         self._free()
         self.ctx, self.h = ctx, handle
+        ctx._adopt(self)
 
     def apply(self, r, z=None):
         if self.h is None:
@@ -769,14 +794,10 @@ class _Pc:
 
     def _free(self):
         try:
-            if self.h and self.ctx and self.ctx.h:
-                lib().kryst_pc_destroy(self.h)
+            self._release()
         except Exception:
             pass
         self.h = None
-
-    def __del__(self):
-        self._free()
 
 
 class Jacobi(_Pc):
@@ -1955,11 +1976,13 @@ class BiCgStabRightPcSolver(_Solver):
     _HOST, _DEV = None, "kryst_bicgstab_rpc_solve_dev"
 
 
-class DenseMatrix:
+class DenseMatrix(_Owned):
     """DenseMatrix<f64> (src/matrix/dense.rs) living on the GPU, column-major; implements MatVec (core/wrappers.rs:27-38)."""
+    _DESTROY, _CLOSE_ORDER = "kryst_dense_destroy", 3
 
     def __init__(self, ctx, handle):
         self.ctx, self.h = ctx, handle
+        ctx._adopt(self)
         nr, nc = C.c_int64(), C.c_int64()
         check(lib().kryst_dense_shape(self.h, C.byref(nr), C.byref(nc)))
         self._nrows, self._ncols = nr.value, nc.value
@@ -2019,13 +2042,6 @@ class DenseMatrix:
             return y
         return out
 
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                lib().kryst_dense_destroy(self.h)
-        except Exception:
-            pass
-
 
 def _direct_solve(host_fn, dev_fn, head, a, pc, b, x):
     """The call shape shared by LuSolver::solve and QrSolver::solve: pc is accepted and ignored (direct_lu.rs:70, :123)."""
@@ -2045,14 +2061,16 @@ def _direct_solve(host_fn, dev_fn, head, a, pc, b, x):
     return stats
 
 
-class LuSolver:
+class LuSolver(_Owned):
     """LuSolver (src/solver/direct_lu.rs:14-90) on a DenseMatrix: LU with full pivoting in the operation order of DESIGN.md section 4.12
     (a labelled deviation from faer's FullPivLu)."""
+    _DESTROY, _CLOSE_ORDER = "kryst_lu_destroy", 3
 
     def __init__(self, ctx=None):
         self.ctx = ctx or Context.default()
         self.h = _ffi.Handle()
         check(lib().kryst_lu_create(self.ctx.h, C.byref(self.h)))
+        self.ctx._adopt(self)
 
     def solve(self, a, pc, b, x):
         """LinearSolver::solve (direct_lu.rs:64-90): factor, cache, solve.  b is x is allowed for DeviceVec arguments."""
@@ -2086,13 +2104,6 @@ class LuSolver:
         rp = np.zeros(max(n, 1), dtype=np.int64); cp = np.zeros(max(n, 1), dtype=np.int64); f = np.zeros(max(n * n, 1))
         check(lib().kryst_lu_export(self.h, n, rp.ctypes.data_as(_ffi.c_i64p), cp.ctypes.data_as(_ffi.c_i64p), _dp(f)))
         return rp[:n], cp[:n], f[:n * n].reshape((n, n), order="F")
-
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                lib().kryst_lu_destroy(self.h)
-        except Exception:
-            pass
 
 
 class QrSolver:
@@ -2297,9 +2308,11 @@ class Session:
         self.a, self.pc, self.b, self.x = a, pc, b, x
         self.max_iters = max_iters
         prm = _ffi.Params(tol, max_iters, 0, 1, int(norm_type), 0, 0, 0.0, 0, 0.0, 0)
+        self.ctx = a.ctx
         self.h = _ffi.Handle()
         check(lib().kryst_session_begin(self.METHODS[method], b.h, x.h, a.h, pc.h if pc is not None else None,
                                         C.byref(prm), C.byref(self.h)))
+        self.ctx._adopt(self)
 
     def step(self, k):
         check(lib().kryst_session_step(self.h, k))
@@ -2313,14 +2326,16 @@ class Session:
         self.close()
         return False
 
+    _CLOSE_ORDER = 0                             # Context.close() ends open sessions before it destroys anything they use
+
     def close(self):
-        if getattr(self, "h", None):
+        h, self.h = getattr(self, "h", None), None
+        if h and self.ctx.h:
             st = _ffi.Stats()
             hlen = C.c_int64(0)
-            try:
-                lib().kryst_session_end(self.h, C.byref(st), None, 0, C.byref(hlen))
-            finally:
-                self.h = None
+            lib().kryst_session_end(h, C.byref(st), None, 0, C.byref(hlen))
+
+    _release = close
 
     def __del__(self):
         try:

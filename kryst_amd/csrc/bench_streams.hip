@@ -385,6 +385,7 @@ extern "C" int32_t kryst_bench_vec_padding(kryst_vec_t v, const double* fill, in
 extern "C" int32_t kryst_bench_csr_skeleton(kryst_csr_t a, kryst_vec_t x, kryst_vec_t y, int32_t reps, double* avg_ms) {
     KR_ARG(a && x && y && avg_ms && reps >= 1, "bench_csr_skeleton");
     KR_ARG(x->n == a->xlen && y->n == a->nrows && a->nrows == a->xlen && !a->dist, "bench_csr_skeleton: a square single-rank operator and vectors of its size");
+    KR_ARG(x->ctx == a->ctx && y->ctx == a->ctx, "bench_csr_skeleton: context mismatch");
     KR_ARG(a->nrows >= 1 && a->d_row_ptr && a->d_col && a->d_val, "bench_csr_skeleton: the operator keeps no CSR arrays");
     kryst_ctx_t ctx = a->ctx;
     KR_HIP(hipSetDevice(ctx->device));

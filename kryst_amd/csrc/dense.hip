@@ -13,6 +13,7 @@
 // s + 1 also leaves that column and its sum of squares for the next step; the last KR_DENSE_TAIL steps run in one workgroup's LDS too.
 #include "dense.h"
 #include "csr.h"
+#include "pc.h"
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -452,6 +453,12 @@ static int32_t dense_check_vecs(kryst_dense_t a, kryst_vec_t b, kryst_vec_t x) {
     return KRYST_OK;
 }
 
+// the preconditioner is accepted and ignored (direct_lu.rs:70, :123), but a handle of another context is still an argument error
+static int32_t dense_check_pc(kryst_dense_t a, kryst_pc_t pc) {
+    KR_ARG(!pc || pc->ctx == a->ctx, "dense solve: preconditioner belongs to another context");
+    return KRYST_OK;
+}
+
 static void direct_stats(kryst_stats_t* stats) {                    // direct_lu.rs:84-88
     if (stats) { stats->iterations = 1; stats->final_residual = 0.0; stats->converged = 1; }
 }
@@ -708,8 +715,9 @@ int32_t kryst_lu_destroy(kryst_lu_t lu) {
     return KRYST_OK;
 }
 
-int32_t kryst_lu_solve_dev(kryst_lu_t lu, kryst_dense_t a, kryst_pc_t, kryst_vec_t b, kryst_vec_t x, kryst_stats_t* stats) {
+int32_t kryst_lu_solve_dev(kryst_lu_t lu, kryst_dense_t a, kryst_pc_t pc, kryst_vec_t b, kryst_vec_t x, kryst_stats_t* stats) {
     KR_ARG(lu && a && a->ctx == lu->ctx, "lu_solve_dev");
+    KR_TRY(dense_check_pc(a, pc));
     KR_TRY(dense_check_square(a, "dense LU"));
     KR_TRY(dense_check_vecs(a, b, x));
     KR_TRY(lu_factor(lu, a));
@@ -718,8 +726,9 @@ int32_t kryst_lu_solve_dev(kryst_lu_t lu, kryst_dense_t a, kryst_pc_t, kryst_vec
     return KRYST_OK;
 }
 
-int32_t kryst_lu_solve(kryst_lu_t lu, kryst_dense_t a, kryst_pc_t, const double* b, double* x, int64_t n, kryst_stats_t* stats) {
+int32_t kryst_lu_solve(kryst_lu_t lu, kryst_dense_t a, kryst_pc_t pc, const double* b, double* x, int64_t n, kryst_stats_t* stats) {
     KR_ARG(lu && a && a->ctx == lu->ctx && ((b && x) || n == 0), "lu_solve");
+    KR_TRY(dense_check_pc(a, pc));
     KR_TRY(dense_check_square(a, "dense LU"));
     KR_ARG(n == a->nrows, "lu_solve: vector length");
     KR_TRY(with_host_vectors(lu->ctx, b, x, n, [&](double* d) -> int32_t {
@@ -768,8 +777,9 @@ int32_t kryst_lu_info(kryst_lu_t lu, int64_t* info, int32_t count) {
     return KRYST_OK;
 }
 
-int32_t kryst_qr_solve_dev(kryst_dense_t a, kryst_pc_t, kryst_vec_t b, kryst_vec_t x, kryst_stats_t* stats) {
+int32_t kryst_qr_solve_dev(kryst_dense_t a, kryst_pc_t pc, kryst_vec_t b, kryst_vec_t x, kryst_stats_t* stats) {
     KR_ARG(a, "qr_solve_dev");
+    KR_TRY(dense_check_pc(a, pc));
     KR_TRY(dense_check_square(a, "dense QR"));
     KR_TRY(dense_check_vecs(a, b, x));
     KR_TRY(qr_run(a, b->d, x->d));
@@ -777,8 +787,9 @@ int32_t kryst_qr_solve_dev(kryst_dense_t a, kryst_pc_t, kryst_vec_t b, kryst_vec
     return KRYST_OK;
 }
 
-int32_t kryst_qr_solve(kryst_dense_t a, kryst_pc_t, const double* b, double* x, int64_t n, kryst_stats_t* stats) {
+int32_t kryst_qr_solve(kryst_dense_t a, kryst_pc_t pc, const double* b, double* x, int64_t n, kryst_stats_t* stats) {
     KR_ARG(a && ((b && x) || n == 0), "qr_solve");
+    KR_TRY(dense_check_pc(a, pc));
     KR_TRY(dense_check_square(a, "dense QR"));
     KR_ARG(n == a->nrows, "qr_solve: vector length");
     KR_TRY(with_host_vectors(a->ctx, b, x, n, [&](double* d) -> int32_t { return qr_run(a, d, d); }));

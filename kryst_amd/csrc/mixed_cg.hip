@@ -240,7 +240,7 @@ extern "C" {
 
 int32_t kryst_cg32_solve_dev(kryst_vec32_t b, kryst_vec32_t x, kryst_csr32_t a, kryst_pc_t pc, const kryst_params_t* params, kryst_stats_t* stats,
                              double* hist, int64_t hist_cap, int64_t* hist_len) {
-    (void)pc;                                                               // cg.rs:115 `let _ = pc;`
+    KR_ARG(!pc || !a || pc->ctx == a->ctx, "solve32: preconditioner belongs to another context");    // ignored (cg.rs:115 `let _ = pc;`), but of this context as for kryst_cg_solve_dev
     return solve32(b, x, a, Solve32IO{nullptr, params, stats, hist, hist_cap, hist_len}, false);
 }
 

@@ -260,6 +260,7 @@ int32_t kryst_pc_destroy(kryst_pc_t pc) {
 
 int32_t kryst_apply_chebyshev(kryst_csr_t a, kryst_vec_t r, kryst_vec_t z, double alpha, double beta, int64_t m) {
     KR_ARG(a && r && z && m >= 0, "apply_chebyshev");
+    KR_ARG(r->ctx == a->ctx && z->ctx == a->ctx, "apply_chebyshev: context mismatch");
     KR_ARG(r->n == a->nrows && z->n == a->nrows && a->nrows == a->xlen, "apply_chebyshev: size mismatch");
     KR_ARG(r != z && r->d != z->d, "apply_chebyshev: r and z alias");
     KR_HIP(hipSetDevice(a->ctx->device));

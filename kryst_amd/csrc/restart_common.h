@@ -123,6 +123,7 @@ struct RestartRun {
     int32_t check(kryst_pc_t applied, const char* restart_msg) const {
         SolveIO seen = io; seen.pc = applied;
         KR_TRY(solve_args_check(seen, bv, xv));
+        KR_ARG(!io.pc || io.pc->ctx == io.a->ctx, "solve: preconditioner belongs to another context");     // (held against the context even where it is ignored)
         KR_ARG(p->restart >= 1 && p->restart <= 4096, restart_msg);
         return KRYST_OK;
     }

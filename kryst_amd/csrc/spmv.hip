@@ -202,6 +202,7 @@ int32_t kryst_csr_pattern_info(kryst_csr_t a, int64_t* info) {
 int32_t kryst_bench_spmv(kryst_csr_t a, kryst_vec_t x, kryst_vec_t y, int32_t fused_dots, int32_t reps, double* avg_ms) {
     KR_ARG(a && x && y && avg_ms && reps >= 1 && fused_dots >= 0 && fused_dots <= 2, "bench_spmv");
     KR_ARG(x->n == a->xlen && y->n == a->nrows, "bench_spmv: size mismatch");
+    KR_ARG(x->ctx == a->ctx && y->ctx == a->ctx, "bench_spmv: context mismatch");
     KR_ARG(fused_dots == 0 || a->nrows == a->xlen, "bench_spmv: fused dots need a square operator");
     kryst_ctx_t ctx = a->ctx;
     KR_HIP(hipSetDevice(ctx->device));

@@ -9,6 +9,7 @@ import pytest
 import kryst_amd as K
 from oracle import oracle as O
 import asm_ref as A
+import device_memory as DM
 import sor_ref as S
 import bjacobi_ref as BR
 import pca_gmres_ref as PR
@@ -180,7 +181,6 @@ def test_setups_and_failed_setups_give_back_their_device_memory(ctx):
     no query for the bytes its pool holds, so the figure is the driver's.  64^3 rows: the pooled kinds' blocks (ILU, additive Schwarz, SOR)
     are over the pool's 1 MiB threshold, so they take the pool_free path; block Jacobi, Jacobi-like vectors and SPAI's M take hipFree.  The
     first round is not measured: it loads the kernels and whatever else the runtime allocates once."""
-    import torch
     a = O.stencil7(64, "poisson")
     n = a.nrows
     d = to_dev(ctx, a)
@@ -203,9 +203,7 @@ def test_setups_and_failed_setups_give_back_their_device_memory(ctx):
             del pc                                                        # destroyed here: CPython drops the last reference
         ctx.synchronize()
 
-    def free_bytes():
-        ctx.synchronize()
-        return torch.cuda.mem_get_info(0)[0]
+    free_bytes = lambda: DM.free_bytes(ctx)                             # (tests/device_memory.py: the figure of every memory test)
 
     free_bytes()                                                          # (the first query brings its own runtime state)
     round_()
