@@ -12,6 +12,7 @@ import pytest
 import kryst_amd as K
 from oracle import oracle as O
 from nonfinite_cases import box_operator as _box_operator
+from knob_cases import deep_factor
 
 pytestmark = pytest.mark.gpu
 
@@ -624,26 +625,8 @@ def test_narrow_level_runs_of_a_deep_factor_bit_exact(ctx, pipe, monkeypatch):
         monkeypatch.setenv("KRYST_ILU_RUN_FREE", "1"); monkeypatch.setenv("KRYST_ILU_FREE_WAVES", pipe[4])
     else:
         monkeypatch.setenv("KRYST_ILU_RUN_FREE", "0"); monkeypatch.setenv("KRYST_ILU_RUN_PIPE", pipe)
-    rng = np.random.default_rng(2024)
-    n, free = 40000, (3000 if wide else 1500)
-    rows = np.repeat(np.arange(free, n), 9)
-    near = rows + rng.integers(-300, 301, len(rows))
-    far = rng.integers(0, n, len(rows))                                   # one entry in ten couples to ANY row: dependencies far below the window
-    cols = np.clip(np.where(rng.random(len(rows)) < 0.1, far, near), 0, n - 1)
-    vals = rng.uniform(-1.0, 1.0, len(rows))
-    chain = n
-    if pipe.endswith("-wide-level-in-the-middle"):
-        # 2 500 more rows that all hang on ONE row half way down the chain: a level of > 2 048 rows between two runs of narrow levels
-        # (a level kernel of its own; the second run's first chunks take their operands "from before the run")
-        rows = np.concatenate([rows, np.arange(n, n + 2500)]); cols = np.concatenate([cols, np.full(2500, 20000)]); vals = np.concatenate([vals, rng.uniform(-1.0, 1.0, 2500)])
-        n += 2500
-    m = sp.csr_matrix((vals, (rows, cols)), shape=(n, n)); m.sum_duplicates()
-    dense_rows = rng.choice(np.arange(free, chain), 50, replace=False)    # rows with ~30 entries: longer than the held eight
-    extra = sp.csr_matrix((rng.uniform(-1.0, 1.0, 50 * 24), (np.repeat(dense_rows, 24), np.clip(np.repeat(dense_rows, 24) + rng.integers(-2000, 2001, 50 * 24), 0, chain - 1))), shape=(n, n))
-    m = (m + extra).tocsr(); m.sum_duplicates()
-    m = m - sp.diags(m.diagonal()) + sp.diags(np.asarray(abs(m).sum(axis=1)).ravel() + 1.0)
-    m = m.tocsr(); m.sort_indices(); m.eliminate_zeros()
-    a = O.Csr(n, n, m.indptr, m.indices, m.data)
+    a = deep_factor(wide_first=wide, wide_middle=pipe.endswith("-wide-level-in-the-middle"))          # (tests/knob_cases.py)
+    n = a.nrows
     d = to_dev(ctx, a)
     for kpc, ofn in ((K.TrueIlu0(), O.Pc.ilu0_true), (K.Ilu0(), O.Pc.ilu0_compat)):
         pc = kpc.setup(d); ref = ofn(a)

@@ -316,6 +316,25 @@ def test_the_tile_stride_and_run_loops(ctx, monkeypatch):
         assert_solve(run32(K.Cg32Solver(1e-30, 3), c.pattern, None, b, zero), ref, setting)
 
 
+@pytest.mark.parametrize("tpw", ["1", "3", "8"])
+def test_tiles_per_workgroup_of_the_pattern_kernel(ctx, monkeypatch, tpw):
+    """KRYST_SPMV32_PATTERN_TPW (4 by default) on the unstaged pattern kernel, six tiles: one tile per workgroup, two workgroups of three, and
+    one workgroup whose run of eight ends at the last tile"""
+    c = case(ctx, "poisson18")
+    n = c.a.nrows
+    assert -(-n // 1024) == 6
+    enter(monkeypatch, c, "stage0")
+    monkeypatch.setenv("KRYST_SPMV32_PATTERN_TPW", tpw)
+    assert c.pattern.encoding() == "pattern"
+    x = MC.vec32(n)
+    got, want = product(ctx, c.pattern, x, n), c.ref.spmv(x)
+    assert same32(got, want), (tpw, int(np.sum(b32(got) != b32(want))))
+    b, zero = R.store(MC.rhs(n)), np.zeros(n, np.float32)
+    ref = R.cg32(c.ref, b, zero, 1e-30, 3)
+    assert ref.iterations == 3
+    assert_solve(run32(K.Cg32Solver(1e-30, 3), c.pattern, None, b, zero), ref, tpw)
+
+
 # ------------------------------------------------------------------------------------------------------------- refinement
 def refine(ctx, d, pc, b, x0, form):
     s = K.RefinementSolver(MC.OUTER_TOL, MC.OUTER_CAP).with_inner(MC.INNER_TOL, MC.INNER_CAP).with_form(form)

@@ -152,6 +152,46 @@ def test_multirank_on_one_gpu(tmp_path, P, N, kind, hostgen):
     assert all(int(r["sess_stats"][0]) == 25 for r in R)
 
 
+# The transport settings: how a solve starts its halo exchange and which paths a new context and a new operator start on.  Two ranks on the
+# smallest grid of the table above.  KRYST_HALO_EARLY is read in every CG / PCG iteration, so its profile changes the solves the worker runs
+# on each transport.  The other two only choose the path a new context / a new operator STARTS on, and the worker switches to RCCL by hand
+# before the solves it reports: for them the witness below is the test, and the numbers show that nothing else moved.  The expectations are
+# those of the default profile, bit for bit.
+TRANSPORT_PROFILES = {"halo-early-0": {"KRYST_HALO_EARLY": "0"}, "halo-mode-rccl": {"KRYST_HALO_MODE": "rccl"},
+                      "scalar-reduce-rccl": {"KRYST_SCALAR_REDUCE": "rccl"}}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("profile", list(TRANSPORT_PROFILES))
+def test_transport_settings_on_two_ranks(tmp_path, profile):
+    from oracle import oracle as O
+    import kryst_amd as K
+    _build_shim()
+    P, N, kind = 2, 10, "aniso"
+    env = dict(os.environ, KRYST_RCCL_LIB=SHIM, KRYST_STENCIL_HOST="1", KRYST_MR_LIGHT="1", **TRANSPORT_PROFILES[profile])
+    R, outs = _run_ranks(tmp_path, P, env, [[os.path.join(ROOT, "tests", "multirank_worker.py"), str(r), str(P), str(tmp_path), str(N), kind]
+                                            for r in range(P)], timeout=300)
+    # the witnesses first: what a new context / a new operator started on (scalar_reduce("query"), halo_mode("query")), and that both hipIpc
+    # transports could still be switched on by hand
+    assert all(int(r["default_halo_peer"][0]) == (0 if profile == "halo-mode-rccl" else 1) for r in R), [int(r["default_halo_peer"][0]) for r in R]
+    assert all(int(r["default_scalar_ipc"][0]) == (0 if profile == "scalar-reduce-rccl" else 1) for r in R), [int(r["default_scalar_ipc"][0]) for r in R]
+    assert all(int(r["ipc_active"][0]) == 1 and int(r["peer_active"][0]) == 1 for r in R)
+    offs = K.partition_rows(N ** 3, P, N * N)
+    a = O.stencil7(N, kind)
+    assert [int(r["nloc"][0]) for r in R] == [int(offs[i + 1] - offs[i]) for i in range(P)]
+    b = a.spmv(np.ones(a.nrows))
+    assert np.array_equal(np.concatenate([r["b"] for r in R]), b)
+    rs = O.Reduce.tiled(*K.reduce_spec(), part_off=offs)
+    assert all(float(r["bnorm"][0]) == O.norm(b, rs) for r in R)
+    for name, pc in (("cg", None), ("pcg", O.Pc.jacobi(a))):
+        ref = O.solve(name, a, b, pc=pc, rs=rs, tol=1e-9, max_iters=300)
+        for r in R:
+            st = r[name + "_stats"]
+            assert (int(st[0]), bool(st[1]), float(st[2])) == (ref.iterations, ref.converged, ref.final_residual), (profile, name, st, ref)
+            assert np.array_equal(r[name + "_hist"], ref.history), (profile, name)
+        assert np.array_equal(np.concatenate([r[name + "_x"] for r in R]), ref.x), (profile, name)
+
+
 # ------------------------------------------------------------------------------------------------------------------------------------------
 # The newer solvers on several ranks, the termination rule at batch boundaries and every refusal (tests/multirank_ext_cases.py holds the
 # tables and the references, tests/multirank_ext_worker.py is one rank).  Separate processes only, at most four ranks.
